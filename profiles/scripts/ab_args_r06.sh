@@ -3,7 +3,7 @@
 #   AB_CFGS="name|--arg1 x --arg2 y;name2|..." (the base line is always run first in each pass)
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/../.." && pwd)}
 cd "$R" && mkdir -p gpurun_out/ab || exit 1
-A="--steps 20 --warmup 5 --no-shard-leg --no-extras --no-cpu-baseline --no-replay"
+A="--full --steps 20 --warmup 5 --no-shard-leg --no-extras --no-cpu-baseline --no-replay"
 IFS=';' read -ra CFGS <<< "base|;${AB_CFGS}"
 for r in 1 2; do
   for v in "${CFGS[@]}"; do

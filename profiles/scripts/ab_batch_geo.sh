@@ -8,7 +8,7 @@ for g in $GEOS; do
   CMVE_BATCH_GEO=$g timeout -k 10 200 python -u -m pytest -x -q --timeout 120 --timeout-method thread tests/test_gpu_retrieval.py -k "batch" > gpurun_out/abg_test_$g.log 2>&1 || { tail -30 gpurun_out/abg_test_$g.log; exit 1; }
   echo "tests geo $g: $(tail -1 gpurun_out/abg_test_$g.log)"
 done
-ARGS="--steps 20 --warmup 5 --no-shard-leg --no-extras --no-cpu-baseline --no-c3-sharded --no-c5 ${BATCH_ARGS:---batch 10 --inflight 2}"
+ARGS="--full --steps 20 --warmup 5 --no-shard-leg --no-extras --no-cpu-baseline --no-c3-sharded --no-c5 ${BATCH_ARGS:---batch 10 --inflight 2}"
 for r in 1 2; do
   for g in $GEOS; do
     CMVE_BATCH_GEO=$g timeout -k 10 120 python bench.py $ARGS > gpurun_out/abgeo_${g}_$r.log 2>&1 || exit 1

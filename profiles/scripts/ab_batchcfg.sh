@@ -2,7 +2,7 @@
 # round 4: the headline over batch sizes / streams in flight (the kernels changed since round 3's sweep)
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/../.." && pwd)}
 cd "$R" && mkdir -p gpurun_out/bcfg || exit 1
-A="--steps 20 --warmup 5 --no-shard-leg --no-extras --no-cpu-baseline --no-replay"
+A="--full --steps 20 --warmup 5 --no-shard-leg --no-extras --no-cpu-baseline --no-replay"
 for r in 1 2; do
   for cfg in ${CFGS:-"8 3 24" "8 2 24" "8 4 24" "12 3 24" "12 2 24" "6 3 24" "16 2 32"}; do
     set -- $cfg

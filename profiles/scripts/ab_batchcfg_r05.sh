@@ -3,7 +3,7 @@
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/../.." && pwd)}
 cd "$R" && mkdir -p gpurun_out/ab_batchcfg_r05 || exit 1
 O=gpurun_out/ab_batchcfg_r05
-A="--steps 20 --warmup 5 --no-shard-leg --no-extras --no-cpu-baseline --no-replay"
+A="--full --steps 20 --warmup 5 --no-shard-leg --no-extras --no-cpu-baseline --no-replay"
 for pass in 1 2; do
 for cfg in "b8s3|--batch 8 --inflight 3" "b12s3|--batch 12 --inflight 3 --input-sets 24" "b16s2|--batch 16 --inflight 2 --input-sets 32" "b8s2|--batch 8 --inflight 2" "b10s3|--batch 10 --inflight 3 --input-sets 30" "b6s4|--batch 6 --inflight 4"; do
   n=${cfg%%|*}; f=${cfg#*|}

@@ -25,7 +25,7 @@ for r in csv.DictReader(open(sys.argv[1])):
         print(n[:60], r["Calls"], "avg ms %.3f" % (float(r["AverageNs"]) / 1e6), "tot ms %.2f" % (float(r["TotalDurationNs"]) / 1e6))
 PY
 cd "$R"
-A="--steps 20 --warmup 5 --no-shard-leg --no-extras --no-cpu-baseline --no-replay"
+A="--full --steps 20 --warmup 5 --no-shard-leg --no-extras --no-cpu-baseline --no-replay"
 for cfg in "c1|--chain 1" "c0|--chain 0" "c1b|--chain 1" "c0b|--chain 0" "c1s4|--chain 1 --inflight 4" "c1s2|--chain 1 --inflight 2"; do
   n=${cfg%%|*}; f=${cfg#*|}
   timeout -k 10 200 python bench.py $A $f > $O/b_$n.json 2> $O/b_$n.err || { echo "$n failed"; tail -5 $O/b_$n.err; exit 1; }

@@ -3,7 +3,7 @@
 # optional, relative to the repo); prints the headline (3 / 1 streams) and the batch's isolated launch durations
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/../.." && pwd)}
 cd "$R" && mkdir -p gpurun_out/ab || exit 1
-A="--steps 20 --warmup 5 --no-shard-leg --no-extras --no-cpu-baseline --no-replay ${AB_ARGS:-}"
+A="--full --steps 20 --warmup 5 --no-shard-leg --no-extras --no-cpu-baseline --no-replay ${AB_ARGS:-}"
 for r in 1 2; do
   for v in "base||" $AB_VARS; do
     n=${v%%|*}; rest=${v#*|}; e=${rest%%|*}; l=${rest#*|}

@@ -3,7 +3,7 @@
 # chunk's fix-up behind the next chunk's G256 launch), alternating, two passes: AB_LIBS="name|lib ..."
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/../.." && pwd)}
 cd "$R" && mkdir -p gpurun_out/ab1m || exit 1
-A="--steps 3 --warmup 1 --evals-per-step 8 --no-extras --no-cpu-baseline --no-replay --no-c3-sharded --no-c5 --no-gallery-shard"
+A="--full --steps 3 --warmup 1 --evals-per-step 8 --no-extras --no-cpu-baseline --no-replay --no-c3-sharded --no-c5 --no-gallery-shard"
 for r in 1 2; do
   for v in "base|cross-modal-video-engine_amd/cmve/libcmve.so" $AB_LIBS; do
     n=${v%%|*}; l=${v#*|}

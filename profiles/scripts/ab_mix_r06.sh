@@ -3,7 +3,7 @@
 #   AB_MIX="name|lib|args;name2|lib2|args2" (lib relative to the repo, empty = the product library)
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/../.." && pwd)}
 cd "$R" && mkdir -p gpurun_out/abm || exit 1
-A="--steps 20 --warmup 5 --no-shard-leg --no-extras --no-cpu-baseline --no-replay"
+A="--full --steps 20 --warmup 5 --no-shard-leg --no-extras --no-cpu-baseline --no-replay"
 IFS=';' read -ra V <<< "base||;${AB_MIX}"
 for r in 1 2; do
   for v in "${V[@]}"; do

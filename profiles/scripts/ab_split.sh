@@ -2,7 +2,7 @@
 # round 4: the headline with the batches' preps on their own CUs (--cu-split N) vs every launch on every CU
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/../.." && pwd)}
 cd "$R" && mkdir -p gpurun_out/split || exit 1
-A="--steps 20 --warmup 5 --no-shard-leg --no-extras --no-cpu-baseline --no-replay"
+A="--full --steps 20 --warmup 5 --no-shard-leg --no-extras --no-cpu-baseline --no-replay"
 for r in 1 2; do
   for n in ${SPLITS:-0 96 112 128}; do
     timeout -k 10 150 python bench.py $A --cu-split $n ${SPLIT_ARGS:-} > gpurun_out/split/s$n.log 2>&1 || { echo "split $n failed"; tail -5 gpurun_out/split/s$n.log; exit 1; }

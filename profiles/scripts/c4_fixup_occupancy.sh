@@ -14,7 +14,7 @@ d=json.loads(open('$O/c4_$n.json').read().strip().splitlines()[-1])
 r=d['ranking']; print('$n', 'rank ms %.2f' % r['ms'], 'mism', r['fp64_sample']['mismatches'], 'R1 %.4f' % r['recall_at_1_5_10_50'][0])
 "
 done
-A="--steps 2 --warmup 1 --evals-per-step 8 --no-extras --no-cpu-baseline --no-replay --no-c3-sharded --no-c5"
+A="--full --steps 2 --warmup 1 --evals-per-step 8 --no-extras --no-cpu-baseline --no-replay --no-c3-sharded --no-c5"
 for cfg in "s|0|0" "s_pf|1|0" "s_b128|0|128"; do
   IFS='|' read n pf bpx <<< "$cfg"
   CMVE_FIX_PF=$pf CMVE_FIX_BPX=$bpx timeout -k 10 300 python bench.py $A > $O/b_$n.json 2> $O/b_$n.err || { echo "$n failed"; tail -5 $O/b_$n.err; exit 1; }

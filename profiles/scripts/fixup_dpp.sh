@@ -10,7 +10,7 @@ for cfg in "base|" "dpp|$R/scratch/libcmve_dpp.so" "base2|" "dpp2|$R/scratch/lib
   n=${cfg%%|*}; lib=${cfg#*|}
   if [ -n "$lib" ]; then export CMVE_LIB=$lib; else unset CMVE_LIB; fi
   timeout -k 10 240 python tools/fusion_bench.py --loop-q 0 --sample 64 > $O/c4_$n.json 2> $O/c4_$n.err || { echo "c4 $n failed"; tail -5 $O/c4_$n.err; exit 1; }
-  timeout -k 10 300 python bench.py --steps 2 --warmup 1 --evals-per-step 8 --no-extras --no-cpu-baseline --no-replay --no-c3-sharded --no-c5 --g1m-chunks 1 > $O/b_$n.json 2> $O/b_$n.err || { echo "b $n failed"; tail -5 $O/b_$n.err; exit 1; }
+  timeout -k 10 300 python bench.py --full --steps 2 --warmup 1 --evals-per-step 8 --no-extras --no-cpu-baseline --no-replay --no-c3-sharded --no-c5 --g1m-chunks 1 > $O/b_$n.json 2> $O/b_$n.err || { echo "b $n failed"; tail -5 $O/b_$n.err; exit 1; }
   python3 -c "
 import json
 d=json.loads(open('$O/c4_$n.json').read().strip().splitlines()[-1]); r=d['ranking']

@@ -8,7 +8,7 @@ rc=$?; tail -2 $O/tests.txt; [ $rc -ne 0 ] && exit $rc
 for cfg in "x1|0" "x2|1" "x1b|0" "x2b|1"; do
   n=${cfg%%|*}; v=${cfg#*|}
   CMVE_FIX_X2=$v timeout -k 10 240 python tools/fusion_bench.py --loop-q 0 --sample 64 > $O/c4_$n.json 2> $O/c4_$n.err || { echo "c4 $n failed"; tail -5 $O/c4_$n.err; exit 1; }
-  CMVE_FIX_X2=$v timeout -k 10 300 python bench.py --steps 2 --warmup 1 --evals-per-step 8 --no-extras --no-cpu-baseline --no-replay --no-c3-sharded --no-c5 --g1m-chunks 1 > $O/b_$n.json 2> $O/b_$n.err || { echo "b $n failed"; tail -5 $O/b_$n.err; exit 1; }
+  CMVE_FIX_X2=$v timeout -k 10 300 python bench.py --full --steps 2 --warmup 1 --evals-per-step 8 --no-extras --no-cpu-baseline --no-replay --no-c3-sharded --no-c5 --g1m-chunks 1 > $O/b_$n.json 2> $O/b_$n.err || { echo "b $n failed"; tail -5 $O/b_$n.err; exit 1; }
   python3 -c "
 import json
 d=json.loads(open('$O/c4_$n.json').read().strip().splitlines()[-1]); r=d['ranking']

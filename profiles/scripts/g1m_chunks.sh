@@ -3,7 +3,7 @@
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/../.." && pwd)}
 cd "$R" && mkdir -p gpurun_out/g1m_chunks || exit 1
 O=gpurun_out/g1m_chunks
-A="--steps 2 --warmup 1 --evals-per-step 8 --no-extras --no-cpu-baseline --no-replay --no-c3-sharded --no-c5"
+A="--full --steps 2 --warmup 1 --evals-per-step 8 --no-extras --no-cpu-baseline --no-replay --no-c3-sharded --no-c5"
 for c in 1 4 8 2; do
   timeout -k 10 300 python bench.py $A --chunks $c > $O/b_c$c.json 2> $O/b_c$c.err || { echo "c$c failed"; tail -5 $O/b_c$c.err; exit 1; }
   python3 -c "

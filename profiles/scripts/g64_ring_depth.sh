@@ -4,7 +4,7 @@
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/../.." && pwd)}
 cd "$R" && mkdir -p gpurun_out/g64_ring_depth || exit 1
 O=gpurun_out/g64_ring_depth
-A="--steps 4 --warmup 2 --no-shard-leg --no-extras --no-cpu-baseline --no-replay"
+A="--full --steps 4 --warmup 2 --no-shard-leg --no-extras --no-cpu-baseline --no-replay"
 for cfg in "s4|0|" "s6|0|$R/scratch/libcmve_g64s6.so" "s8|0|$R/scratch/libcmve_g64s8.so" "s8i|1|$R/scratch/libcmve_g64s8.so" "s4i|1|" "s8b|0|$R/scratch/libcmve_g64s8.so" "s4b|0|"; do
   IFS='|' read n inl lib <<< "$cfg"
   if [ -n "$lib" ]; then export CMVE_LIB=$lib; else unset CMVE_LIB; fi

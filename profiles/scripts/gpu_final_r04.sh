@@ -6,7 +6,8 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout
 rc=$?; tail -2 gpurun_out/final/gpu_tests.txt; [ $rc -ne 0 ] && exit $rc
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/final/smoke.txt 2>&1 || { tail -5 gpurun_out/final/smoke.txt; exit 1; }
 tail -1 gpurun_out/final/smoke.txt
-timeout -k 10 600 python bench.py > gpurun_out/final/bench.json 2> gpurun_out/final/bench.err || { tail -20 gpurun_out/final/bench.err; exit 1; }
+O=$(dirname "$(ls -d */final/smoke.txt)")  # (beside the smoke log)
+timeout -k 10 600 python bench.py --full > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
 python3 -c "
 import json
 d = json.loads(open('gpurun_out/final/bench.json').read().strip().splitlines()[-1])

@@ -8,7 +8,7 @@ rc=$?; tail -2 $O/gpu_tests.txt; [ $rc -ne 0 ] && exit $rc
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.txt 2>&1 || { tail -5 $O/smoke.txt; exit 1; }
 tail -1 $O/smoke.txt
 [ -n "$NO_BENCH" ] && exit 0
-timeout -k 10 600 python bench.py > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
+timeout -k 10 600 python bench.py --full > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
 python3 -c "
 import json
 d = json.loads(open('$O/bench.json').read().strip().splitlines()[-1])

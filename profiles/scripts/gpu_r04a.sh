@@ -4,7 +4,7 @@
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/../.." && pwd)}
 cd "$R" && mkdir -p gpurun_out/r04a || exit 1
 O=gpurun_out/r04a
-HB="--no-shard-leg --no-extras --no-cpu-baseline"
+HB="--full --no-shard-leg --no-extras --no-cpu-baseline"
 timeout -k 10 300 bash profiles/scripts/calib.sh > $O/calib.log 2>&1 || { echo "calib failed"; tail -20 $O/calib.log; exit 1; }
 cat $O/calib.log
 timeout -k 10 300 python bench.py $HB > $O/bench3.log 2>&1 || { echo "bench3 failed"; tail -20 $O/bench3.log; exit 1; }

@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/../.." && pwd)}
 TAG=${1:-r05a}
 cd "$R" && mkdir -p gpurun_out/$TAG || exit 1
 O=gpurun_out/$TAG
-HB="--no-shard-leg --no-extras --no-cpu-baseline"
+HB="--full --no-shard-leg --no-extras --no-cpu-baseline"
 timeout -k 10 600 python -u -m pytest ${TESTS:-tests/test_gpu_retrieval.py} -x -q --timeout 300 --timeout-method thread > $O/tests.log 2>&1
 rc=$?; tail -3 $O/tests.log; [ $rc -ne 0 ] && { grep -E "Error|assert" $O/tests.log | head -20; exit $rc; }
 timeout -k 10 300 python bench.py $HB > $O/bench3.log 2>&1 || { echo "bench3 failed"; tail -20 $O/bench3.log; exit 1; }

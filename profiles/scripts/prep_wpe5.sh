@@ -4,7 +4,7 @@
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/../.." && pwd)}
 cd "$R" && mkdir -p gpurun_out/prep_wpe5 || exit 1
 O=gpurun_out/prep_wpe5
-A="--steps 20 --warmup 5 --no-shard-leg --no-extras --no-cpu-baseline --no-replay"
+A="--full --steps 20 --warmup 5 --no-shard-leg --no-extras --no-cpu-baseline --no-replay"
 for cfg in "w4|" "w5|$R/scratch/libcmve_pw5.so" "w4b|" "w5b|$R/scratch/libcmve_pw5.so"; do
   n=${cfg%%|*}; lib=${cfg#*|}
   if [ -n "$lib" ]; then export CMVE_LIB=$lib; else unset CMVE_LIB; fi

@@ -3,7 +3,7 @@
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/../.." && pwd)}
 cd /tmp && export TMPDIR=/tmp && cd "$R" && mkdir -p gpurun_out || exit 1
 T=${TAG:-b}
-ARGS="--steps 20 --warmup 5 --no-shard-leg --no-extras --no-cpu-baseline --no-c3-sharded --no-c5 ${BATCH_ARGS:---batch 10 --inflight 1}"
+ARGS="--full --steps 20 --warmup 5 --no-shard-leg --no-extras --no-cpu-baseline --no-c3-sharded --no-c5 ${BATCH_ARGS:---batch 10 --inflight 1}"
 rm -rf gpurun_out/prof_$T gpurun_out/pmc_$T
 timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_$T -o run -- python3 bench.py $ARGS > gpurun_out/prof_$T.log 2>&1 || exit 1
 timeout -s KILL 150 rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum TCC_EA0_RDREQ_sum --output-format csv -d gpurun_out/pmc_$T -o run -- python3 bench.py $ARGS --steps 5 --warmup 2 > gpurun_out/pmc_$T.log 2>&1 || exit 1

@@ -7,7 +7,7 @@ set -euo pipefail
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 TAG=${1:-r01}
 ARGS=${BENCH_ARGS:-"--steps 10 --warmup 3 --no-extras --no-c3-sharded --no-c5 --no-cpu-baseline"}
-X=${PROFILE_EXTRA:-}  # appended to every pass (e.g. --gallery-total 0: the gallery_shard launches only)
+X="--full ${PROFILE_EXTRA:-}"  # appended to every pass (e.g. --gallery-total 0: the gallery_shard launches only)
 OUT=$R/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp

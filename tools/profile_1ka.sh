@@ -5,12 +5,12 @@
 set -euo pipefail
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 TAG=${1:-r02}
-ARGS="--steps 200 --warmup 5 --no-shard-leg --no-extras --no-cpu-baseline"
+ARGS="--steps 200 --warmup 5 --full --no-shard-leg --no-extras --no-cpu-baseline"
 OUT=$R/gpurun_out/prof1ka_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o run -- python3 "$R/bench.py" $ARGS > "$OUT/bench_trace.log" 2>&1
-timeout -s KILL 200 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/fetch" -o run -- python3 "$R/bench.py" --steps 20 --warmup 2 --no-shard-leg --no-extras --no-cpu-baseline > "$OUT/bench_fetch.log" 2>&1
-timeout -s KILL 200 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/write" -o run -- python3 "$R/bench.py" --steps 20 --warmup 2 --no-shard-leg --no-extras --no-cpu-baseline > "$OUT/bench_write.log" 2>&1
+timeout -s KILL 200 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/fetch" -o run -- python3 "$R/bench.py" --steps 20 --warmup 2 --full --no-shard-leg --no-extras --no-cpu-baseline > "$OUT/bench_fetch.log" 2>&1
+timeout -s KILL 200 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/write" -o run -- python3 "$R/bench.py" --steps 20 --warmup 2 --full --no-shard-leg --no-extras --no-cpu-baseline > "$OUT/bench_write.log" 2>&1
 python3 "$R/tools/traffic_1ka.py" "$OUT" "$TAG" > "$OUT/traffic.log" 2>&1
 echo "profile 1ka done: $OUT"
