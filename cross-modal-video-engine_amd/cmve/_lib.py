@@ -137,6 +137,9 @@ SIGNATURES = {
     "cmve_layernorm_pack": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _f64, _P(Rows)]),
     "cmve_pairwise": (C.c_int, [_vp, _vp, _i32, _i64, _i64, _vp, _i32, _i64, _i64, _i64, _i32, _f64, _f64, _vp,
                                 _i32, _i64]),
+    "cmve_pairwise_bwd_workspace": (C.c_int, [_i64, _i64, _i32, _P(_i64)]),
+    "cmve_pairwise_bwd": (C.c_int, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _i32, _f64, _vp, _i64, _vp, _i64,
+                                    _vp, _i64, _vp, _i64]),
     "cmve_bn_train_fwd": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _f64, _f64, _vp, _vp, _vp, _i64, _vp, _vp]),
     "cmve_bn_train_bwd": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _i64, _i64, _vp, _f64, _vp, _i64, _vp, _vp]),
     "cmve_gemm_f32_ex": (C.c_int, [_vp, _i32, _i32, _i64, _i64, _i64, _f32, _vp, _i64, _vp, _i64, _f32, _vp, _i64,

@@ -269,6 +269,37 @@ def pairwise(a: torch.Tensor, b: torch.Tensor, metric: int, alpha: float = 1.0, 
     return out
 
 
+def pairwise_bwd_workspace(na: int, nb: int, metric: int) -> int:
+    """Bytes of workspace ``cmve_pairwise_bwd`` needs (host only: no launch, no GPU)."""
+    n = C.c_int64()
+    check(lib.cmve_pairwise_bwd_workspace(na, nb, metric, C.byref(n)), "cmve_pairwise_bwd_workspace")
+    return n.value
+
+
+def pairwise_bwd(a: torch.Tensor, b: torch.Tensor, metric: int, alpha: float, ds: torch.Tensor,
+                 need_a: bool = True, need_b: bool = True):
+    """(dA, dB) of ``sum(ds * pairwise(a, b, metric, alpha, beta))`` for fp32 rows (K17); a side that is not
+    needed is None and is not computed."""
+    if a.dim() != 2 or b.dim() != 2 or a.shape[1] != b.shape[1] or ds.shape != (a.shape[0], b.shape[0]):
+        raise ValueError(f"pairwise_bwd: shapes {tuple(a.shape)}, {tuple(b.shape)}, {tuple(ds.shape)} do not match")
+    if a.dtype != torch.float32 or b.dtype != torch.float32 or ds.dtype != torch.float32:
+        raise TypeError("pairwise_bwd: float32 only")
+    if not (a.is_cuda and b.is_cuda and ds.is_cuda):
+        raise ValueError("pairwise_bwd: device tensors only")
+    a = a if a.stride(1) == 1 and a.stride(0) >= a.shape[1] else a.contiguous()
+    b = b if b.stride(1) == 1 and b.stride(0) >= b.shape[1] else b.contiguous()
+    ds = ds if ds.stride(1) == 1 and ds.stride(0) >= ds.shape[1] else ds.contiguous()
+    na, nb, d = a.shape[0], b.shape[0], a.shape[1]
+    nbytes = pairwise_bwd_workspace(na, nb, metric)
+    ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=a.device)
+    da = torch.empty((na, d), dtype=torch.float32, device=a.device) if need_a else None
+    db = torch.empty((nb, d), dtype=torch.float32, device=a.device) if need_b else None
+    check(lib.cmve_pairwise_bwd(handle(a.device), _ptr(a), a.stride(0), na, _ptr(b), b.stride(0), nb, d, metric,
+                                float(alpha), _ptr(ds), max(ds.stride(0), nb), _ptr(da), d, _ptr(db), d, _ptr(ws),
+                                nbytes), "cmve_pairwise_bwd")
+    return da, db
+
+
 def csr(lists: Sequence[Sequence[int]], device) -> Tuple[torch.Tensor, torch.Tensor]:
     """Python GT lists -> (offsets int64 [n+1], indices int32) device tensors."""
     lens = np.fromiter((len(l) for l in lists), dtype=np.int64, count=len(lists))

@@ -4,6 +4,7 @@
 //                                            -jaccard (torch fp32)
 //   LINAS-engine/loss.py:13-73               order / euclidean / L1 / L1_norm / L2 / L2_norm /
 //                                            jaccard training similarities
+//                                            (their backward under TripletLoss: K17, pairwise_bwd.hip)
 // out[i, j] = alpha * f(a_i, b_j) + beta with
 //   SQ_L2   f = sum_k (a_k - b_k)^2              L2   f = sqrt(SQ_L2)
 //   L1      f = sum_k |a_k - b_k|                ORDER f = sqrt(sum_k max(0, b_k - a_k)^2)

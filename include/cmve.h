@@ -618,6 +618,25 @@ int cmve_pairwise(cmve_handle_t h, const void* A, int32_t a_dtype, int64_t lda, 
                   int32_t b_dtype, int64_t ldb, int64_t nb, int64_t d, int32_t metric, double alpha, double beta,
                   void* out, int32_t out_dtype, int64_t ldo);
 
+/* K17: the backward of K10 for the measures LINAS-engine/loss.py:93-108 hands to TripletLoss (its autograd
+ * through order_sim / euclidean_sim / L1_sim / L1_sim_norm / L2_sim / L2_sim_norm / jaccard_sim, loss.py:13-73,
+ * reached from trainer.py:42 --measure by model.py:531-532).  score = alpha * f(A_i, B_j) + beta, dS [na, nb] =
+ * dL/dscore (f32, device), w_ij = alpha * dS_ij:
+ *   dA[i, k] = sum_j w_ij * df/da_k        dB[j, k] = sum_i w_ij * df/db_k        (f32 [na, d] / [nb, d], device)
+ *   CMVE_PW_SQ_L2   df/da_k = 2 (a_k - b_k)         CMVE_PW_L1  sign(a_k - b_k), 0 at a tie
+ *   CMVE_PW_ORDER   t_k = b_k - a_k: -t_k / f where t_k >= 0, exactly 0 where t_k < 0; a pair at distance 0
+ *                   contributes NaN where t_k == 0 (w / f is 0 / 0 or x / 0, as torch's sqrt backward)
+ *   CMVE_PW_JACCARD m_k / U - I M_k / U^2 (I = sum min, U = sum max; m_k = 1 if a_k < b_k, 1/2 if equal, else 0;
+ *                   M_k likewise for a_k > b_k: torch.min / torch.max halve the gradient at a tie)
+ *   df/db_k is the same expression with a and b swapped.  CMVE_PW_L2 / CMVE_PW_DOT are refused (no loss.py user).
+ * A, B are f32 rows.  dA or dB may be NULL (that side is not computed).  fp64 accumulation in a fixed order, one
+ * rounding to f32, no atomics: two calls give the same bits.  No na x nb x d intermediate: ws holds the per-pair
+ * coefficients (cmve_pairwise_bwd_workspace bytes -- host only, no launch -- 8-byte aligned, need not be zeroed). */
+int cmve_pairwise_bwd_workspace(int64_t na, int64_t nb, int32_t metric, int64_t* bytes);
+int cmve_pairwise_bwd(cmve_handle_t h, const float* A, int64_t lda, int64_t na, const float* B, int64_t ldb,
+                      int64_t nb, int64_t d, int32_t metric, double alpha, const float* dS, int64_t ldd,
+                      float* dA, int64_t ldda, float* dB, int64_t lddb, void* ws, int64_t ws_bytes);
+
 /* ---- training step of the projection heads ---------------
  * K11: what LINAS-engine/model.py:984-1004 (train_emb, style 'GT') runs around the GEMMs (K3 forward,
  * cmve_gemm_f32 backward) and the losses (K6/K7).  Device pointers, fp32 rows; statistics in fp64.
