@@ -140,6 +140,12 @@ SIGNATURES = {
     "cmve_pairwise_bwd_workspace": (C.c_int, [_i64, _i64, _i32, _P(_i64)]),
     "cmve_pairwise_bwd": (C.c_int, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _i32, _f64, _vp, _i64, _vp, _i64,
                                     _vp, _i64, _vp, _i64]),
+    "cmve_pairwise_positions_workspace": (C.c_int, [_i64, _i64, _i64, _i64, _i32, _P(_i64)]),
+    "cmve_pairwise_positions": (C.c_int, [_vp, _vp, _i32, _i64, _i64, _vp, _i32, _i64, _i64, _i64, _i32, _f64, _f64,
+                                          _i32, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i64]),
+    "cmve_pairwise_topk_workspace": (C.c_int, [_i64, _i64, _i32, _i32, _P(_i64), _P(_i64)]),
+    "cmve_pairwise_topk": (C.c_int, [_vp, _vp, _i32, _i64, _i64, _vp, _i32, _i64, _i64, _i64, _i32, _f64, _f64, _i32,
+                                     _i32, _i32, _vp, _i64, _vp, _vp]),
     "cmve_bn_train_fwd": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _f64, _f64, _vp, _vp, _vp, _i64, _vp, _vp]),
     "cmve_bn_train_bwd": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _i64, _i64, _vp, _f64, _vp, _i64, _vp, _vp]),
     "cmve_gemm_f32_ex": (C.c_int, [_vp, _i32, _i32, _i64, _i64, _i64, _f32, _vp, _i64, _vp, _i64, _f32, _vp, _i64,

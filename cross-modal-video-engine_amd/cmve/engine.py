@@ -300,6 +300,157 @@ def pairwise_bwd(a: torch.Tensor, b: torch.Tensor, metric: int, alpha: float, ds
     return da, db
 
 
+def pairwise_positions_workspace(na: int, nb: int, row_items: int, col_items: int, metric: int) -> int:
+    """Bytes of workspace ``cmve_pairwise_positions`` needs: the item scores (host only: no launch, no GPU)."""
+    n = C.c_int64()
+    check(lib.cmve_pairwise_positions_workspace(na, nb, row_items, col_items, metric, C.byref(n)),
+          "cmve_pairwise_positions_workspace")
+    return n.value
+
+
+def pairwise_topk_workspace(n_q: int, n_g: int, k: int, metric: int) -> Tuple[int, int]:
+    """(minimum, recommended) bytes of workspace for ``cmve_pairwise_topk`` (host only: no launch, no GPU)."""
+    lo, rec = C.c_int64(), C.c_int64()
+    check(lib.cmve_pairwise_topk_workspace(n_q, n_g, int(k), metric, C.byref(lo), C.byref(rec)),
+          "cmve_pairwise_topk_workspace")
+    return lo.value, rec.value
+
+
+def _pw_rows(x, name: str) -> torch.Tensor:
+    """A pairwise operand: f32 / f64 device rows, row-strided views as they are."""
+    t = x if isinstance(x, torch.Tensor) else to_device(x)
+    if t.dim() != 2:
+        raise ValueError(f"{name}: a 2-d operand is needed, got shape {tuple(t.shape)}")
+    if not t.is_cuda:
+        t = to_device(t)
+    _dtype_code(t)
+    return t if t.stride(1) == 1 and t.stride(0) >= t.shape[1] else t.contiguous()
+
+
+def _pw_ld(t: torch.Tensor) -> int:
+    """Row stride of a pairwise operand (torch leaves the stride of a one-row tensor's row dimension arbitrary)."""
+    return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
+
+
+class _PairwisePositions:
+    """One ``cmve_pairwise_positions`` call: per direction the 0-based positions, the item scores and the offsets."""
+
+    def __init__(self, a, b, metric, alpha, beta, score_dtype, row_lists=None, col_lists=None):
+        a, b = _pw_rows(a, "pairwise_gt_positions"), _pw_rows(b, "pairwise_gt_positions")
+        if a.shape[1] != b.shape[1]:
+            raise ValueError(f"pairwise_gt_positions: shapes {tuple(a.shape)} and {tuple(b.shape)} do not match")
+        na, nb, dev = a.shape[0], b.shape[0], a.device
+        if row_lists is not None and len(row_lists) != na:
+            raise ValueError(f"pairwise_gt_positions: {len(row_lists)} row lists for {na} rows")
+        if col_lists is not None and len(col_lists) != nb:
+            raise ValueError(f"pairwise_gt_positions: {len(col_lists)} column lists for {nb} rows")
+        self.n = (nb, na)  # the length of a row / of a column
+        self.lists = (row_lists, col_lists)
+        sides = []
+        for lists in self.lists:
+            if lists is None:
+                sides.append((None, None, 0, None))
+                continue
+            off, idx = csr(lists, dev)
+            items = sum(len(l) for l in lists)
+            sides.append((off, idx, items, torch.empty(max(items, 1), dtype=torch.int32, device=dev)))
+        (roff, ridx, ritems, rpos), (coff, cidx, citems, cpos) = sides
+        nbytes = pairwise_positions_workspace(na, nb, ritems, citems, metric)
+        ws = torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=dev)
+        code = _lib.CMVE_F64 if score_dtype == torch.float64 else _lib.CMVE_F32
+        check(lib.cmve_pairwise_positions(handle(dev), _ptr(a), _dtype_code(a), _pw_ld(a), na, _ptr(b),
+                                          _dtype_code(b), _pw_ld(b), nb, a.shape[1], metric, float(alpha),
+                                          float(beta), code, _ptr(roff), _ptr(ridx), ritems, _ptr(rpos), _ptr(coff),
+                                          _ptr(cidx), citems, _ptr(cpos), _ptr(ws), nbytes),
+              "cmve_pairwise_positions")
+        sc = ws.cpu().numpy()
+        self.pos, self.nan = [], []
+        start = 0
+        for (_, _, items, pos) in sides:
+            self.pos.append(None if pos is None else pos[:items].cpu().numpy().astype(np.int64))
+            self.nan.append(np.isnan(sc[start:start + items]))
+            start += items
+
+    def positions(self, side: int):
+        """1-based positions as a list of int64 arrays aligned with the lists (None: direction not asked for)."""
+        lists = self.lists[side]
+        if lists is None:
+            return None
+        p = self.pos[side] + 1
+        offs = np.zeros(len(lists) + 1, np.int64)
+        np.cumsum([len(l) for l in lists], out=offs[1:])
+        return [p[offs[i]:offs[i + 1]] for i in range(len(lists))]
+
+    def ranks(self, side: int):
+        """1-based best-GT ranks with rank_from_matrix's rules: 1 + the least position over the non-NaN items;
+        an empty list ranks n + 1, a list whose items all score NaN ranks n."""
+        lists = self.lists[side]
+        if lists is None:
+            return None
+        n_m = self.n[side]
+        lens = np.fromiter((len(l) for l in lists), np.int64, count=len(lists))
+        big = np.iinfo(np.int64).max
+        best = np.full(len(lists), big, np.int64)
+        np.minimum.at(best, np.repeat(np.arange(len(lists)), lens), np.where(self.nan[side], big, self.pos[side]))
+        ranks = np.where(best == big, n_m - 1, best) + 1
+        ranks[lens == 0] = n_m + 1
+        return ranks
+
+
+def pairwise_gt_positions(a, b, metric: int, alpha: float, beta: float, score_dtype, row_lists=None, col_lists=None):
+    """(row_positions, col_positions): 1-based positions of every listed item under a non-cosine measure, as
+    ``metrics.gt_positions`` gives them on ``pairwise(a, b, ...)`` and on its transpose -- without the matrix (K18).
+    row_lists[i]: rows of b listed for row i of a; col_lists[j]: rows of a listed for row j of b."""
+    r = _PairwisePositions(a, b, metric, alpha, beta, score_dtype, row_lists, col_lists)
+    return r.positions(0), r.positions(1)
+
+
+def pairwise_gt_ranks(a, b, metric: int, alpha: float, beta: float, score_dtype, row_lists=None, col_lists=None):
+    """(row_ranks, col_ranks) == ``rank_from_matrix`` on ``pairwise(a, b, ...)`` in both orientations (K18)."""
+    r = _PairwisePositions(a, b, metric, alpha, beta, score_dtype, row_lists, col_lists)
+    return r.ranks(0), r.ranks(1)
+
+
+def pairwise_gt_eval(a, b, metric: int, alpha: float, beta: float, score_dtype, row_lists=None, col_lists=None):
+    """((row_positions, row_ranks), (col_positions, col_ranks)) from ONE ``cmve_pairwise_positions`` call: what
+    cal_perf needs (both directions' ranks and every mAP position)."""
+    r = _PairwisePositions(a, b, metric, alpha, beta, score_dtype, row_lists, col_lists)
+    return (r.positions(0), r.ranks(0)), (r.positions(1), r.ranks(1))
+
+
+def pairwise_topk(q, g, metric: int, alpha: float, beta: float, score_dtype, k: int, to_host: bool = True,
+                  ws: Optional[torch.Tensor] = None, ws_bytes: Optional[int] = None, geometry: int = 0):
+    """The k rows of g with the smallest error per row of q under a non-cosine measure, by (error asc, index asc),
+    NaN last -- a stable argsort of ``pairwise(q, g, ...)`` cut at k, without the matrix (K18).  Returns
+    (idx int64 [n_q, k], errors fp64 [n_q, k]); k is clamped to the gallery.  ws: a caller-held uint8 device
+    workspace (at least the minimum of ``pairwise_topk_workspace``; default: the recommended size); ws_bytes
+    sizes a fresh one."""
+    q, g = _pw_rows(q, "pairwise_topk"), _pw_rows(g, "pairwise_topk")
+    if q.shape[1] != g.shape[1]:
+        raise ValueError(f"pairwise_topk: shapes {tuple(q.shape)} and {tuple(g.shape)} do not match")
+    n_q, n_g = q.shape[0], g.shape[0]
+    k = int(min(k, n_g))
+    if k < 1:
+        return np.zeros((n_q, 0), np.int64), np.zeros((n_q, 0))
+    if k > _lib.TOPK_MAX:
+        raise ValueError(f"pairwise_topk: k <= {_lib.TOPK_MAX}")
+    lo, rec = pairwise_topk_workspace(n_q, n_g, k, metric)
+    if ws is None:
+        ws = torch.empty(max(rec if ws_bytes is None else int(ws_bytes), 8), dtype=torch.uint8, device=q.device)
+    if ws.numel() * ws.element_size() < lo:
+        raise ValueError(f"pairwise_topk: workspace of {ws.numel() * ws.element_size()} bytes < minimum {lo}")
+    idx = torch.empty((n_q, k), dtype=torch.int64, device=q.device)
+    err = torch.empty((n_q, k), dtype=torch.float64, device=q.device)
+    code = _lib.CMVE_F64 if score_dtype == torch.float64 else _lib.CMVE_F32
+    check(lib.cmve_pairwise_topk(handle(q.device), _ptr(q), _dtype_code(q), _pw_ld(q), n_q, _ptr(g), _dtype_code(g),
+                                 _pw_ld(g), n_g, q.shape[1], metric, float(alpha), float(beta), code, k,
+                                 int(geometry), _ptr(ws), ws.numel() * ws.element_size(), _ptr(idx), _ptr(err)),
+          "cmve_pairwise_topk")
+    if not to_host:
+        return idx, err
+    return idx.cpu().numpy(), err.cpu().numpy()
+
+
 def csr(lists: Sequence[Sequence[int]], device) -> Tuple[torch.Tensor, torch.Tensor]:
     """Python GT lists -> (offsets int64 [n+1], indices int32) device tensors."""
     lens = np.fromiter((len(l) for l in lists), dtype=np.int64, count=len(lists))

@@ -27,9 +27,13 @@ class ErrorMatrix(np.ndarray):
     """ndarray of errors that carries the packed (captions, videos) sets it was made from."""
 
     _cmve = None  # (captions RowSet, videos RowSet, sign) -- dropped by any view/transform
+    # non-cosine measures: (captions, videos, measure) -- the device-resident rows in the measure's input dtype; the
+    # metrics rank them matrix-free (K18).  Separate from _cmve, whose sign logic is cosine's; dropped likewise.
+    _cmve_pw = None
 
     def __array_finalize__(self, obj):
         self._cmve = None
+        self._cmve_pw = None
 
 
 def _as_error_matrix(arr: np.ndarray, caps, vids, sign):
@@ -59,32 +63,57 @@ def _cosine(videos, captions, sign):
     return _as_error_matrix(out.cpu().numpy(), caps, vids, sign)
 
 
-# scipy cdist branches of evaluation.py:22-33 / 56-67: measure -> (metric, alpha(D), beta), fp64 out
-_CDIST = {
-    'euclidean': (PW_L2, lambda D: 1.0, 0.0),
-    'l2': (PW_L2, lambda D: 1.0, 0.0),
-    'l1': (PW_L1, lambda D: 1.0, 0.0),
-    'l1_norm': (PW_L1, lambda D: -1.0 / D, -1.0),
-    'l2_norm': (PW_L2, lambda D: -1.0 / D, -1.0),
+# evaluation.py:22-35 / 56-71: measure -> (metric, alpha(D), beta, input dtype, score dtype).  The scipy cdist
+# branches work in fp64 whatever the input dtype; jaccard goes through torch.Tensor(...) (fp32 inputs) and returns
+# -jaccard_sim in fp32.  The ONE table of the matrix path (K10) and the matrix-free paths (K18).
+MEASURES = {
+    'euclidean': (PW_L2, lambda D: 1.0, 0.0, torch.float64, torch.float64),
+    'l2': (PW_L2, lambda D: 1.0, 0.0, torch.float64, torch.float64),
+    'l1': (PW_L1, lambda D: 1.0, 0.0, torch.float64, torch.float64),
+    'l1_norm': (PW_L1, lambda D: -1.0 / D, -1.0, torch.float64, torch.float64),
+    'l2_norm': (PW_L2, lambda D: -1.0 / D, -1.0, torch.float64, torch.float64),
+    'jaccard': (PW_JACCARD, lambda D: -1.0, 0.0, torch.float32, torch.float32),
 }
 
 
+def measure_spec(measure, D):
+    """(metric, alpha, beta, input dtype, score dtype) of a non-cosine evaluation measure at dimension D."""
+    if measure not in MEASURES:
+        raise ValueError(f"cmve.cal_error: unknown measure {measure!r}")
+    metric, alpha, beta, in_dt, sc_dt = MEASURES[measure]
+    return metric, alpha(D), beta, in_dt, sc_dt
+
+
+def measure_rows(x, measure, device=None):
+    """Rows resident on the device in the measure's input dtype (fp64 for the cdist branches, fp32 for jaccard)."""
+    in_dt = measure_spec(measure, 1)[3]
+    if torch.is_tensor(x):
+        return engine.to_device(x if x.dim() == 2 else x[None, :], device, in_dt)
+    return engine.to_device(np.atleast_2d(np.asarray(x)), device, in_dt)
+
+
+def _as_measure_matrix(arr: np.ndarray, caps, vids, measure):
+    out = arr.view(ErrorMatrix)
+    out._cmve_pw = (caps, vids, measure)
+    return out
+
+
 def _measure(videos, captions, measure):
-    dev = engine.default_device()
-    if measure in _CDIST:  # cdist works in fp64 whatever the input dtype
-        metric, alpha, beta = _CDIST[measure]
-        c = engine.to_device(np.asarray(captions), dev, torch.float64)
-        v = engine.to_device(np.asarray(videos), dev, torch.float64)
-        return engine.pairwise(c, v, metric, alpha(v.shape[1]), beta, torch.float64).cpu().numpy()
-    if measure == 'jaccard':  # torch.Tensor(...) -> fp32 inputs, -jaccard_sim, returned as a torch tensor
-        c = engine.to_device(np.asarray(captions), dev, torch.float32)
-        v = engine.to_device(np.asarray(videos), dev, torch.float32)
-        return engine.pairwise(c, v, PW_JACCARD, -1.0, 0.0, torch.float32).cpu()
-    raise ValueError(f"cmve.cal_error: unknown measure {measure!r}")
+    c, v = measure_rows(captions, measure), measure_rows(videos, measure)
+    metric, alpha, beta, _, sc_dt = measure_spec(measure, v.shape[1])
+    out = engine.pairwise(c, v, metric, alpha, beta, sc_dt).cpu()
+    if measure == 'jaccard':  # a torch tensor, as the reference returns: no attribute to carry the rows
+        return out
+    return _as_measure_matrix(out.numpy(), c, v, measure)
 
 
 def cal_error(videos, captions, measure='cosine'):
-    """errors[N_c, N_v] (evaluation.py:17-36): -cos, or the cdist / jaccard branches."""
+    """errors[N_c, N_v] (evaluation.py:17-36): -cos, or the cdist / jaccard branches.
+
+    Under the five cdist measures the ndarray remembers the device-resident rows and the measure, so that
+    ``cal_perf`` / ``eval_q2m`` / ``t2v_map`` / ``v2t_map`` rank them matrix-free (K18) instead of uploading the
+    matrix again.  ``cal_error(..., 'jaccard')`` returns a torch tensor, as the reference does: it cannot carry
+    that attribute and stays on the matrix path (``cal_error_batch`` returns the ndarray that does)."""
     if measure == 'cosine':
         return _cosine(videos, captions, -1)
     return _measure(videos, captions, measure)
@@ -94,8 +123,11 @@ def cal_error_batch(videos, captions, measure='cosine', batch_size=2000):
     """evaluation.py:41-72 -- the caption batching only bounds the reference's jaccard memory;
     the all-pairs kernel never materialises the [N_c, N_v, D] broadcast, so one call covers it
     (the jaccard result is a float32 ndarray here, as np.append makes it in the reference)."""
-    out = cal_error(videos, captions, measure)
-    return out.numpy() if measure == 'jaccard' else out
+    if measure != 'jaccard':
+        return cal_error(videos, captions, measure)
+    c, v = measure_rows(captions, measure), measure_rows(videos, measure)
+    metric, alpha, beta, _, sc_dt = measure_spec(measure, v.shape[1])
+    return _as_measure_matrix(engine.pairwise(c, v, metric, alpha, beta, sc_dt).cpu().numpy(), c, v, measure)
 
 
 def cal_simi(captions, videos, measure='cosine'):

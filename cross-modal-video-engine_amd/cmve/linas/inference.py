@@ -20,11 +20,13 @@ reference's ``student_support_set_8/`` and ``dataset/``):
      model.embed_vis_distill, ...) on the GPU, written back to ``video_data.pt``
   3. vocabularies dataset/<train collection>/TextData/vocabulary/{bow,rnn}/<vocab>.pkl (restricted
      unpickler) -> process_cap(--input) -> embed_txt_distill
-  4. exact top-K of the cosine errors on HBM (GalleryScorer), printed as the id list
+  4. exact top-K of the errors on HBM (GalleryScorer; under the checkpoint's opt.measure: cosine on the packed
+     gallery, a cdist / jaccard measure through the matrix-free top-k of K18), printed as the id list
 ``--gpu`` is exported as HIP_VISIBLE_DEVICES before the GPU is touched (the reference's
 CUDA_VISIBLE_DEVICES, inference.py:47); its default is '0' rather than the reference's '5', which
 would hide every GPU of a box with fewer than six.  ``--query-emb`` (a .npy caption embedding)
-and ``--gallery`` (an .npz with video_embs / video_ids) bypass steps 3 and 1-2 respectively.
+and ``--gallery`` (an .npz with video_embs / video_ids) bypass steps 3 and 1-2 respectively; ``--measure``
+overrides the checkpoint's opt.measure (with both bypasses no checkpoint is read: cosine unless given).
 """
 from __future__ import annotations
 
@@ -39,12 +41,23 @@ from .._lib import SIM_F16
 
 
 class GalleryScorer:
-    """A video gallery resident in HBM, normalised once (LINAS l2norm, no eps)."""
+    """A video gallery resident in HBM, normalised once (LINAS l2norm, no eps).
 
-    def __init__(self, video_embs, video_ids=None, with_lo=True):
+    ``measure``: 'cosine', or a cdist / jaccard measure of evaluation.py:22-35 -- the gallery then stays resident
+    UNNORMALISED in the measure's input dtype (fp64 for the cdist branches, fp32 for jaccard) and every query
+    batch is served by the matrix-free exact top-k of K18 (``engine.pairwise_topk``): the ids of
+    ``np.argsort(cal_error(video_embs, cap_emb, measure)[i], kind='stable')[:topK]``."""
+
+    def __init__(self, video_embs, video_ids=None, with_lo=True, measure='cosine'):
+        self.measure = measure
+        self.video_ids = list(video_ids) if video_ids is not None else None
+        self._ws = None
+        if measure != 'cosine':
+            from .evaluation import measure_rows
+            self.gallery = measure_rows(video_embs, measure)
+            return
         emb = video_embs if hasattr(video_embs, "data_ptr") else np.asarray(video_embs)
         self.gallery = engine.RowSet(emb, eps=0.0, with_lo=with_lo)
-        self.video_ids = list(video_ids) if video_ids is not None else None
         self._ws = None
         self._q = {}    # resident query sets by (rows, dim, dtype): re-packed in place per call
         self._out = {}  # resident top-k outputs by (rows, k)
@@ -52,6 +65,8 @@ class GalleryScorer:
     def topk_indices(self, cap_embs, topK=10):
         """[N_q, topK] gallery indices, best first (== np.argsort(cal_error(...)[i])[:topK])."""
         import torch
+        if self.measure != 'cosine':
+            return self._measure_topk(cap_embs, topK)
         if not torch.is_tensor(cap_embs):
             cap_embs = np.atleast_2d(np.asarray(cap_embs))
         elif cap_embs.dim() == 1:
@@ -76,6 +91,20 @@ class GalleryScorer:
         idx, _ = engine.topk(q, self.gallery, topK, mode=SIM_F16, scores_ws=self._ws, out=out)
         return idx
 
+    def _measure_topk(self, cap_embs, topK):
+        import torch
+        from .evaluation import measure_rows, measure_spec
+        g = self.gallery
+        q = measure_rows(cap_embs, self.measure, g.device)
+        metric, alpha, beta, _, sc_dt = measure_spec(self.measure, g.shape[1])
+        k = min(int(topK), g.shape[0])
+        if 1 <= k <= engine._lib.TOPK_MAX:  # the workspace stays resident between calls, grown when a call needs more
+            need = engine.pairwise_topk_workspace(q.shape[0], g.shape[0], k, metric)[1]
+            if self._ws is None or self._ws.numel() < need:
+                self._ws = torch.empty(need, dtype=torch.uint8, device=g.device)
+        idx, _ = engine.pairwise_topk(q, g, metric, alpha, beta, sc_dt, k, ws=self._ws)
+        return idx
+
     def topk_ids(self, cap_emb, topK=10):
         inds = self.topk_indices(cap_emb, topK)[0]
         return [self.video_ids[i] for i in inds]
@@ -95,6 +124,8 @@ def parse_args(argv=None):
                    help='.npz with video_embs [N,D] and video_ids instead of the cache / BigFile')
     p.add_argument('--query-emb', default=None, type=str,
                    help='.npy caption embedding [1,D] instead of encoding --input')
+    p.add_argument('--measure', default=None, type=str,
+                   help="similarity measure (default: the checkpoint's opt.measure, cosine without a checkpoint)")
     p.add_argument('--rnn-vocab', default=None, type=str, help='rnn vocabulary (default: the checkpoint opt path)')
     p.add_argument('--bow-vocab', default=None, type=str, help='bow vocabulary (default: the checkpoint opt path)')
     return p.parse_args(argv)
@@ -143,15 +174,18 @@ def main(argv=None):
         vocab = T.load_vocab(opt.rnn_vocab or os.path.join(voc, 'rnn', options.vocab + '.pkl'))
         bow2vec = T.get_text_encoder('bow')(bow_vocab)
         cap_emb = model.embed_txt_distill(T.process_cap(opt.input, vocab, bow2vec)).cpu().numpy()
-    measure = getattr(options, 'measure', 'cosine') if options is not None else 'cosine'
-    if measure == 'cosine':
-        results = GalleryScorer(video_embs, [str(v) for v in video_ids]).topk_ids(cap_emb, opt.topK)
-    else:  # inference.py:78-80 with a cdist / jaccard measure: the all-pairs kernel, then argsort
-        from .evaluation import cal_error
-        errors = np.asarray(cal_error(video_embs, cap_emb, measure))
-        results = [video_ids[i] for i in np.argsort(errors[0])[:opt.topK]]
+    measure = opt.measure or (getattr(options, 'measure', 'cosine') if options is not None else 'cosine')
+    results = _retrieve(video_embs, video_ids, cap_emb, measure, opt.topK)
     print(results)
     return results
+
+
+def _retrieve(video_embs, video_ids, cap_emb, measure, topK):
+    """inference.py:78-80 under any measure: cosine on the packed gallery, a cdist / jaccard measure on the
+    unnormalised resident gallery through the matrix-free top-k (K18) -- no errors[1, N] row on the host."""
+    if measure == 'cosine':
+        return GalleryScorer(video_embs, [str(v) for v in video_ids]).topk_ids(cap_emb, topK)
+    return GalleryScorer(video_embs, list(video_ids), measure=measure).topk_ids(cap_emb, topK)
 
 
 if __name__ == '__main__':

@@ -7,7 +7,9 @@
 The per-row argsort of the reference is replaced by rank counting on the GPU:
 position of item k in np.argsort(row) == #{j : e_j < e_k} on tie-free rows.
 ``scores`` that are an ``ErrorMatrix`` from cmve.linas.evaluation.cal_error are ranked
-by the fused exact path (fp64 decisions, no matrix re-read).
+by the fused exact path (fp64 decisions, no matrix re-read).  Errors of a non-cosine measure that carry
+their device-resident rows (``ErrorMatrix._cmve_pw``) are ranked matrix-free by K18: the same words the
+matrix path gives, without the upload.
 """
 from __future__ import annotations
 
@@ -54,6 +56,27 @@ def _fused_sets(scores):
     return meta
 
 
+def _measure_sets(errors):
+    """(captions, videos, measure) of errors that carry their non-cosine rows, else None."""
+    return getattr(errors, '_cmve_pw', None) if isinstance(errors, ErrorMatrix) else None
+
+
+def measure_eval(caps, vids, measure, row_lists=None, col_lists=None):
+    """((t2v positions, t2v ranks), (v2t positions, v2t ranks)) under a non-cosine measure from ONE
+    cmve_pairwise_positions call over the device-resident rows; a direction without lists gives (None, None)."""
+    from .evaluation import measure_spec
+    metric, alpha, beta, _, sc_dt = measure_spec(measure, vids.shape[1])
+    return engine.pairwise_gt_eval(caps, vids, metric, alpha, beta, sc_dt, row_lists, col_lists)
+
+
+def maps_from_positions(t2v_pos, v2t_pos):
+    """(t2v_map, v2t_map) of metrics.py:61-102 from every GT item's position: the t2v AP scores the FIRST GT video
+    of each caption alone (1 / its position), the v2t AP all GT captions of each video."""
+    t2v = float(np.mean([ap_from_positions(p[:1]) for p in t2v_pos]))
+    v2t = float(np.mean([ap_from_positions(p) for p in v2t_pos]))
+    return t2v, v2t
+
+
 def gt_ranks(scores, q2m_gts):
     """1-based best-GT rank per query (metrics.py:137-147)."""
     n_q, n_m = scores.shape
@@ -64,6 +87,9 @@ def gt_ranks(scores, q2m_gts):
         if sign < 0:  # errors = -cos: rank by cos descending
             r, _, _ = engine.gt_rank_counts(caps, vids, row_gts=lists)
             return r.astype(np.int32)
+    pw = _measure_sets(scores)
+    if pw is not None:
+        return measure_eval(*pw, row_lists=lists)[0][1].astype(np.int32)
     return engine.rank_from_matrix(scores, lists).astype(np.int32)
 
 
@@ -105,6 +131,10 @@ def t2v_map(c2i, t2v_gts):
         caps, vids, _ = meta
         r, _, _ = engine.gt_rank_counts(caps, vids, row_gts=firsts)
         return float(np.mean(1.0 / r))
+    pw = _measure_sets(c2i)
+    if pw is not None:
+        pos = measure_eval(*pw, row_lists=firsts)[0][0]
+        return float(np.mean([ap_from_positions(p) for p in pos]))
     pos = gt_positions(c2i, firsts)
     return float(np.mean([ap_from_positions(p) for p in pos]))
 
@@ -120,6 +150,10 @@ def v2t_map(c2i, v2t_gts):
             _, c, _ = engine.gt_rank_counts(caps, vids, col_gts=lists)
             return float(np.mean([1.0 / c[j] if lists[j] else 0.0 for j in range(n_v)]))
         pos = engine.gt_positions_fused(vids, caps, lists)
+        return float(np.mean([ap_from_positions(p) for p in pos]))
+    pw = _measure_sets(c2i)
+    if pw is not None:
+        pos = measure_eval(*pw, col_lists=lists)[1][0]
         return float(np.mean([ap_from_positions(p) for p in pos]))
     pos = gt_positions(c2i, lists, transposed=True)
     return float(np.mean([ap_from_positions(p) for p in pos]))

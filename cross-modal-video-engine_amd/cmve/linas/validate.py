@@ -49,6 +49,12 @@ def cal_perf(t2v_all_errors, v2t_gt, t2v_gt, tb_logger=None, model=None):
             v2t_map_score = float(np.mean([1.0 / v2t_ranks[j] if v2t_lists[j] else 0.0 for j in range(n_v)]))
         else:
             v2t_map_score = metrics.v2t_map(t2v_all_errors, v2t_gt)
+    elif metrics._measure_sets(t2v_all_errors) is not None:
+        # a non-cosine measure with its rows on the device: both directions' ranks and every mAP position from one
+        # matrix-free pass (K18)
+        caps, vids, measure = metrics._measure_sets(t2v_all_errors)
+        (t2v_pos, t2v_ranks), (v2t_pos, v2t_ranks) = metrics.measure_eval(caps, vids, measure, t2v_lists, v2t_lists)
+        t2v_map_score, v2t_map_score = metrics.maps_from_positions(t2v_pos, v2t_pos)
     else:
         t2v_ranks = engine.rank_from_matrix(t2v_all_errors, t2v_lists)
         v2t_ranks = engine.rank_from_matrix(t2v_all_errors, v2t_lists, transposed=True)
@@ -70,10 +76,19 @@ def cal_perf(t2v_all_errors, v2t_gt, t2v_gt, tb_logger=None, model=None):
             (t2v_r1, t2v_r5, t2v_r10, t2v_medr, t2v_meanr, t2v_map_score))
 
 
-def cal_perf_embeddings(video_embs, cap_embs, video_ids, caption_ids):
+def cal_perf_embeddings(video_embs, cap_embs, video_ids, caption_ids, measure='cosine'):
     """tester.py:133-139 in one call: get_gt -> fused two-direction rank -> cal_perf tuples,
-    without materialising the N_c x N_v error matrix on host."""
+    without materialising the N_c x N_v error matrix on host.  A non-cosine ``measure`` (the cdist branches and
+    jaccard of evaluation.py:22-35) never forms the matrix at all, on the device or the host (K18)."""
     v2t_gt, t2v_gt = metrics.get_gt(video_ids, caption_ids)
+    if measure != 'cosine':
+        from .evaluation import measure_rows
+        caps, vids = measure_rows(cap_embs, measure), measure_rows(video_embs, measure)
+        t2v_lists = metrics._lists(t2v_gt, caps.shape[0])
+        (t2v_pos, t2v_ranks), (v2t_pos, v2t_ranks) = metrics.measure_eval(caps, vids, measure, t2v_lists, v2t_gt)
+        t2v_map, v2t_map = metrics.maps_from_positions(t2v_pos, v2t_pos)
+        return (metrics.metrics_from_ranks(v2t_ranks.astype(np.int32)) + (v2t_map,),
+                metrics.metrics_from_ranks(t2v_ranks.astype(np.int32)) + (t2v_map,))
     caps = engine.RowSet(np.asarray(cap_embs), eps=0.0, with_lo=False)
     vids = engine.RowSet(np.asarray(video_embs), eps=0.0, with_lo=False)
     n_c, n_v = caps.n, vids.n

@@ -15,91 +15,26 @@
 // slabs (converted to fp64 once on the way in), fp64 accumulation -- the reference's scipy path
 // is fp64 (encode_* buffers are fp64, evaluation.py:102); its torch paths are fp32 and agree to
 // fp32 rounding.
-#include "cmve_internal.h"
+#include "pairwise_tile.h"
 
 namespace cmve {
 
-// Block tile 64 (A rows) x 128 (B rows), 256 threads as 16 x 16; thread (tx, ty) owns A rows
-// {2ty + 32u + e} and B rows {2tx + 32v + e} (u < 2, v < 4, e < 2): 4 x 8 = 32 outputs from 2 + 4
-// ds_read_b128 per k (16-B pairs, consecutive across the 16 lanes of a row group: conflict-free),
-// against 8 ds_read_b64 per 16 outputs in a 4 x 4 layout -- the LDS port no longer matches the
-// fp64 VALU rate.
-constexpr int PW_TA = 64, PW_TB = 128, PW_K = 32, PW_PA = PW_TA + 2, PW_PB = PW_TB + 2;
-
-template <int METRIC>
-__device__ __forceinline__ void pw_acc(double a, double b, double& s0, double& s1) {
-  if constexpr (METRIC == CMVE_PW_SQ_L2 || METRIC == CMVE_PW_L2) {
-    const double t = a - b;
-    s0 = fma(t, t, s0);
-  } else if constexpr (METRIC == CMVE_PW_L1) {
-    s0 += fabs(a - b);
-  } else if constexpr (METRIC == CMVE_PW_ORDER) {
-    const double t = fmax(b - a, 0.0);
-    s0 = fma(t, t, s0);
-  } else if constexpr (METRIC == CMVE_PW_DOT) {
-    s0 = fma(a, b, s0);
-  } else {  // JACCARD
-    s0 += fmin(a, b);
-    s1 += fmax(a, b);
-  }
-}
-
-template <int METRIC>
-__device__ __forceinline__ double pw_final(double s0, double s1) {
-  if constexpr (METRIC == CMVE_PW_L2 || METRIC == CMVE_PW_ORDER) return sqrt(s0);
-  else if constexpr (METRIC == CMVE_PW_JACCARD) return s0 / s1;
-  else return s0;
-}
-
+// Block tile 64 (A rows) x 128 (B rows), 256 threads as 16 x 16 (PwWide, pairwise_tile.h): thread (tx, ty) owns
+// A rows {2ty + 32u + e} and B rows {2tx + 32v + e} (u < 2, v < 4, e < 2): 4 x 8 = 32 outputs.  The stage-and-
+// accumulate loop and the finalisation are the shared chain of pairwise_tile.h (K18 runs the same one).
 template <typename TA, typename TB, typename TO, int METRIC>
 __global__ __launch_bounds__(256) void pairwise_kernel(const TA* __restrict__ A, int64_t lda, int64_t na,
                                                        const TB* __restrict__ B, int64_t ldb, int64_t nb, int64_t d,
                                                        double alpha, double beta, TO* __restrict__ out,
                                                        int64_t ldo) {
-  __shared__ __attribute__((aligned(16))) double sa[PW_K][PW_PA];  // [k][row], converted to fp64 once
-  __shared__ __attribute__((aligned(16))) double sb[PW_K][PW_PB];
+  __shared__ __attribute__((aligned(16))) double sa[PW_K][PwWide::PA];  // [k][row], converted to fp64 once
+  __shared__ __attribute__((aligned(16))) double sb[PW_K][PwWide::PB];
   constexpr bool JAC = METRIC == CMVE_PW_JACCARD;
   const int tid = threadIdx.x;
   const int tx = tid & 15, ty = tid >> 4;
   const int64_t i0 = (int64_t)blockIdx.y * PW_TA, j0 = (int64_t)blockIdx.x * PW_TB;
   double s0[4][8] = {}, s1[JAC ? 4 : 1][JAC ? 8 : 1] = {};
-  for (int64_t k0 = 0; k0 < d; k0 += PW_K) {
-    for (int e = tid; e < PW_TA * PW_K; e += 256) {  // coalesced along k
-      const int r = e / PW_K, k = e % PW_K;
-      const int64_t kk = k0 + k;
-      sa[k][r] = (i0 + r < na && kk < d) ? (double)A[(i0 + r) * lda + kk] : 0.0;
-    }
-    for (int e = tid; e < PW_TB * PW_K; e += 256) {
-      const int r = e / PW_K, k = e % PW_K;
-      const int64_t kk = k0 + k;
-      sb[k][r] = (j0 + r < nb && kk < d) ? (double)B[(j0 + r) * ldb + kk] : 0.0;
-    }
-    __syncthreads();
-    const int kn = (int)min<int64_t>(PW_K, d - k0);  // zero padding would bias L1 / jaccard: stop at d
-    for (int k = 0; k < kn; ++k) {
-      double av[4], bv[8];
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        const double2 t = *(const double2*)&sa[k][2 * ty + 32 * u];
-        av[2 * u] = t.x;
-        av[2 * u + 1] = t.y;
-      }
-#pragma unroll
-      for (int v = 0; v < 4; ++v) {
-        const double2 t = *(const double2*)&sb[k][2 * tx + 32 * v];
-        bv[2 * v] = t.x;
-        bv[2 * v + 1] = t.y;
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-#pragma unroll
-        for (int v = 0; v < 8; ++v) {
-          double dummy = 0.0;
-          pw_acc<METRIC>(av[u], bv[v], s0[u][v], JAC ? s1[JAC ? u : 0][JAC ? v : 0] : dummy);
-        }
-    }
-    __syncthreads();
-  }
+  pw_tile_loop<PwWide, METRIC>(A, lda, na, B, ldb, nb, d, i0, j0, sa, sb, s0, s1);
 #pragma unroll
   for (int u = 0; u < 4; ++u) {
     const int64_t i = i0 + 2 * ty + 32 * (u >> 1) + (u & 1);
@@ -108,8 +43,7 @@ __global__ __launch_bounds__(256) void pairwise_kernel(const TA* __restrict__ A,
     for (int v = 0; v < 8; ++v) {
       const int64_t j = j0 + 2 * tx + 32 * (v >> 1) + (v & 1);
       if (j < nb)
-        out[i * ldo + j] =
-            (TO)(alpha * pw_final<METRIC>(s0[u][v], JAC ? s1[JAC ? u : 0][JAC ? v : 0] : 0.0) + beta);
+        out[i * ldo + j] = (TO)pw_score<METRIC>(s0[u][v], JAC ? s1[JAC ? u : 0][JAC ? v : 0] : 0.0, alpha, beta);
     }
   }
 }

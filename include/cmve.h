@@ -637,6 +637,56 @@ int cmve_pairwise_bwd(cmve_handle_t h, const float* A, int64_t lda, int64_t na, 
                       int64_t nb, int64_t d, int32_t metric, double alpha, const float* dS, int64_t ldd,
                       float* dA, int64_t ldda, float* dB, int64_t lddb, void* ws, int64_t ws_bytes);
 
+/* K18: retrieval under the non-cosine measures without the na x nb error matrix.  A pair's score e(i, j) is the
+ * value cmve_pairwise stores for the same (metric, alpha, beta, out_dtype = score_dtype): the same fp64 chain
+ * (csrc/pairwise_tile.h), rounded to score_dtype -- so every count below equals, word for word, what
+ * cmve_gt_positions_from_matrix / cmve_rank_from_matrix return on cmve_pairwise's output, ties and NaN included.
+ *
+ * cmve_pairwise_positions -- positions of every listed item in both directions from ONE pass over the pairs.
+ * Replaces: LINAS-engine/evaluation.py:22-35,46-71 (cal_error / cal_error_batch under euclidean / l1 / l2 / l1_norm /
+ * l2_norm / jaccard) followed by util/metrics.py:61-102,124-157 (t2v_map, v2t_map, eval_q2m's argsort loop) -- the
+ * validate.py:15-54 cal_perf of tester.py:137 and validate.py:71.
+ *   A [na, d] (captions: rows of the error matrix), B [nb, d] (videos); f32 / f64 rows (device), row strides lda / ldb.
+ *   row_off [na + 1] / row_idx [row_items] (device): CSR lists of B items per A row;
+ *       row_pos[p] = #{ j < nb : e(i, j) < e(i, row_idx[p]) }   for p in [row_off[i], row_off[i + 1])
+ *   col_off [nb + 1] / col_idx [col_items]: CSR lists of A items per B row; col_pos the mirror over i < na.
+ *   A NaN item gets cmve_gt_positions_from_matrix's value: n - (NaN items of its list) + (its place among them).
+ *   row_pos / col_pos: int32 (device); either may be NULL (that direction is skipped).  row_items / col_items are the
+ *   host's copies of row_off[na] / col_off[nb].  The best-GT rank of a list is 1 + min over its non-NaN items.
+ *   ws: cmve_pairwise_positions_workspace bytes (host only, no launch) = 8 * (row_items + col_items): the items'
+ *   scores, nothing proportional to na * nb; 8-byte aligned, need not be zeroed.  Integer atomics only: two calls
+ *   give the same words. */
+int cmve_pairwise_positions_workspace(int64_t na, int64_t nb, int64_t row_items, int64_t col_items, int32_t metric,
+                                      int64_t* bytes);
+int cmve_pairwise_positions(cmve_handle_t h, const void* A, int32_t a_dtype, int64_t lda, int64_t na, const void* B,
+                            int32_t b_dtype, int64_t ldb, int64_t nb, int64_t d, int32_t metric, double alpha,
+                            double beta, int32_t score_dtype, const int64_t* row_off, const int32_t* row_idx,
+                            int64_t row_items, int32_t* row_pos, const int64_t* col_off, const int32_t* col_idx,
+                            int64_t col_items, int32_t* col_pos, void* ws, int64_t ws_bytes);
+/* cmve_pairwise_topk -- the k gallery rows of smallest error per query, ordered by (error asc, index asc), NaN last:
+ * a stable ascending argsort of cmve_pairwise's row, cut at k.
+ * Replaces: LINAS-engine/inference.py:78-80 (cal_error(video_embs, cap_emb, measure) then
+ * np.argsort(errors[0])[:topK]) under a non-cosine measure.
+ *   Q [n_q, d], G [n_g, d]: f32 / f64 rows (device).  out_idx int64 [n_q, k] (global gallery ids; -1 past the
+ *   gallery when k > n_g), out_err fp64 [n_q, k] (the errors, rounded to score_dtype; NaN in an empty slot).
+ *   1 <= k <= 2048.  Gallery chunks are scored into ws as -error and merged into the running best by
+ *   cmve_topk_dense_merge (K12f); geometry: 0 = 8-row tiles for n_q <= 8 (inference.py's single caption), 64-row
+ *   tiles beyond; 1 / 2 force the 64-row / 8-row tiles (the same words either way).
+ *   cmve_pairwise_topk_workspace (host only, no launch): min_bytes = the two best-lists (32 * n_q * k) + one
+ *   128-column chunk of scores; rec_bytes = the best-lists + the whole gallery's scores or 256 MiB of them
+ *   (whichever is smaller; at least one chunk).  cmve_pairwise_topk takes any ws_bytes >= min_bytes
+ *   (8-byte aligned) and sizes its chunks to it.  Below 256 queries K12f's one block per query would bound the
+ *   call, so the chunk is cut into S <= 63 column segments of >= k columns, each (segment, query) a K12f row, and
+ *   the segments' lists are joined with the running best by the k-way merge of cmve_merge_topk; rec_bytes then
+ *   holds those lists instead ((2 S + 4) * 8 * n_q * k bytes) and a workspace too small for them runs the plain
+ *   chunk loop: the same words either way. */
+int cmve_pairwise_topk_workspace(int64_t n_q, int64_t n_g, int32_t k, int32_t metric, int64_t* min_bytes,
+                                 int64_t* rec_bytes);
+int cmve_pairwise_topk(cmve_handle_t h, const void* Q, int32_t q_dtype, int64_t ldq, int64_t n_q, const void* G,
+                       int32_t g_dtype, int64_t ldg, int64_t n_g, int64_t d, int32_t metric, double alpha, double beta,
+                       int32_t score_dtype, int32_t k, int32_t geometry, void* ws, int64_t ws_bytes, int64_t* out_idx,
+                       double* out_err);
+
 /* ---- training step of the projection heads ---------------
  * K11: what LINAS-engine/model.py:984-1004 (train_emb, style 'GT') runs around the GEMMs (K3 forward,
  * cmve_gemm_f32 backward) and the losses (K6/K7).  Device pointers, fp32 rows; statistics in fp64.
