@@ -143,6 +143,11 @@ SIGNATURES = {
     "cmve_pairwise_positions_workspace": (C.c_int, [_i64, _i64, _i64, _i64, _i32, _P(_i64)]),
     "cmve_pairwise_positions": (C.c_int, [_vp, _vp, _i32, _i64, _i64, _vp, _i32, _i64, _i64, _i64, _i32, _f64, _f64,
                                           _i32, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i64]),
+    "cmve_pairwise_item_scores": (C.c_int, [_vp, _vp, _i32, _i64, _i64, _vp, _i32, _i64, _i64, _i64, _i32, _f64, _f64,
+                                            _i32, _vp, _vp, _i64, _i64, _i32, _i64, _vp]),
+    "cmve_pairwise_count": (C.c_int, [_vp, _vp, _i32, _i64, _i64, _vp, _i32, _i64, _i64, _i64, _i32, _f64, _f64, _i32,
+                                      _vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _i64, _vp]),
+    "cmve_pairwise_list_ranks": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _vp]),
     "cmve_pairwise_topk_workspace": (C.c_int, [_i64, _i64, _i32, _i32, _P(_i64), _P(_i64)]),
     "cmve_pairwise_topk": (C.c_int, [_vp, _vp, _i32, _i64, _i64, _vp, _i32, _i64, _i64, _i64, _i32, _f64, _f64, _i32,
                                      _i32, _i32, _vp, _i64, _vp, _vp]),

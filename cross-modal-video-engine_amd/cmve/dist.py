@@ -16,11 +16,26 @@ The top-k path all-gathers each shard's exact local top-k (score, global id) and
 (score desc, global id asc) on the device (cmve_merge_topk).  The reference never shards
 (SURVEY.md section 0.2).
 
+``ShardedGallery(..., measure=)`` under euclidean / l1 / l2 / l1_norm / l2_norm / jaccard (evaluation.py:17-36): the
+shard keeps its rows unnormalised in the measure's input dtype and K18's launches (csrc/pairwise_rank.hip) do the
+arithmetic.  A position counts with a strict < and no index tie-break, so it is the plain sum over the shards of
+their counts against the same item score:
+  1. all-gather of the captions, as above;
+  2. every rank builds the same CSR of all captions' GT videos (global ids) and scores the items whose video it
+     holds (cmve_pairwise_item_scores, the all-zero word elsewhere); ONE all-reduce(SUM) of the scores' int64 words
+     gives every rank every item's score bit for bit -- errors are unbounded, so no sentinel is safe inside a MAX;
+     the v2t items are local;
+  3. ONE cmve_pairwise_count pass over (all captions) x (this shard) counts both directions; rank 0 alone passes
+     n_global for the NaN items' positions;
+  4. ONE all-reduce(SUM) carrying the t2v positions and this shard's v2t R@K sums (cmve_pairwise_list_ranks).
+Top-k merges the shards' local lists on score = -error.  The words are those of the unsharded K18.
+
 Collectives go through a communicator object: ``TorchComm`` is the torch.distributed process
 group (backend "nccl" = RCCL on the GPU, gloo in the CPU tests); ``LocalGroup`` runs N shards in
 ONE process, one thread and HIP stream per shard (a host driving several shards -- on one GPU or
 several -- with the same coordination code).  ``ShardedGallery``'s shard-local arithmetic is a
-handful of methods (``_pack``, ``_row_gt``, ``_col_gt``, ``_count``, ``_ranks``, ``_positions``)
+handful of methods (``_pack``, ``_row_gt``, ``_col_gt``, ``_count``, ``_ranks``, ``_positions``; under a
+measure ``_pw_rows``, ``_pw_items``, ``_pw_count``, ``_pw_ranks``, ``_pw_topk``)
 over the HIP kernels; the coordination above them is shared by every communicator.
 """
 from __future__ import annotations
@@ -460,15 +475,23 @@ def ap_from_positions(positions) -> float:
 class ShardedGallery:
     """This rank's gallery shard [offset, offset + n) of an n_global-video gallery, packed in HBM.
 
-    ``comm``: a communicator (default: TorchComm over torch.distributed's process group)."""
+    ``comm``: a communicator (default: TorchComm over torch.distributed's process group).
+    ``measure``: 'cosine' (the default: packed rows, the fp16 MFMA rank GEMM) or one of evaluation.py's
+    non-cosine measures: the rows stay resident unnormalised in the measure's input dtype, every method keeps its
+    return types, ``mode`` arguments are ignored and top-k returns errors (ascending)."""
 
     def __init__(self, local_embs, offset: int, n_global: int, with_lo: bool = False, eps: float = 0.0,
-                 device: Optional[torch.device] = None, with_f16: bool = True, comm=None, cap: int = 1 << 22):
+                 device: Optional[torch.device] = None, with_f16: bool = True, comm=None, cap: int = 1 << 22,
+                 measure: str = 'cosine'):
         self.comm = _comm(comm)
         self.rank, self.world = self.comm.rank, self.comm.world
         self.offset = int(offset)
         self.n_global = int(n_global)
-        self._setup(local_embs, with_lo, eps, device, with_f16, cap)
+        self.measure = measure
+        if measure == 'cosine':
+            self._setup(local_embs, with_lo, eps, device, with_f16, cap)
+        else:
+            self._pw_setup(local_embs, device)
 
     def _setup(self, local_embs, with_lo, eps, device, with_f16, cap):
         self.shard = engine.RowSet(local_embs, eps=eps, with_lo=with_lo, device=device, with_f16=with_f16)
@@ -519,13 +542,153 @@ class ShardedGallery:
         """1-based positions of every GT caption of every shard video among all captions (v2t mAP)."""
         return engine.gt_positions_fused(self.shard, q, lists, mode=mode)
 
+    # ---- a non-cosine measure: shard-local arithmetic (HIP kernels: K18's launches, csrc/pairwise_rank.hip) ----
+    def _pw_setup(self, local_embs, device):
+        from .linas.evaluation import measure_spec
+        measure_spec(self.measure, 1)  # ValueError on an unknown measure
+        self._pw_device = device
+        self.shard = self._pw_rows(local_embs)  # resident, unnormalised, in the measure's input dtype
+        self.device = self.shard.device
+        self.n = int(self.shard.shape[0])
+
+    def _pw_spec(self):
+        from .linas.evaluation import measure_spec
+        metric, alpha, beta, _, sc_dt = measure_spec(self.measure, int(self.shard.shape[1]))
+        return metric, alpha, beta, sc_dt
+
+    def _pw_rows(self, x) -> torch.Tensor:
+        """Rows on the device in the measure's input dtype (fp64; fp32 for jaccard)."""
+        from .linas.evaluation import measure_rows
+        return measure_rows(x, self.measure, self._pw_device)
+
+    def _pw_items(self, q, csr, n_items: int, col_dir: bool, idx_base: int) -> torch.Tensor:
+        """fp64 [n_items]: the scores of the listed items this shard owns, the all-zero word elsewhere."""
+        off, idx = csr
+        return engine.pairwise_item_scores(q, self.shard, *self._pw_spec(), off, idx, n_items, col_dir, idx_base)
+
+    def _pw_count(self, q, row, col):
+        """ONE pass over (all captions) x (this shard): (row positions | None, column positions | None), int32."""
+        return engine.pairwise_count(q, self.shard, *self._pw_spec(), row=row, col=col)
+
+    def _pw_ranks(self, off, sc, pos, n_m: int) -> torch.Tensor:
+        return engine.pairwise_list_ranks(off, sc, pos, n_m)
+
+    def _pw_topk(self, q, k: int):
+        """This shard's (local ids int64, errors fp64) [n_q, k] on the device, (error asc, id asc), NaN last."""
+        return engine.pairwise_topk(q, self.shard, *self._pw_spec(), k, to_host=False)
+
+    # ---- a non-cosine measure: coordination (every communicator) ----
+    def _pw_csr(self, lists, n_other: Optional[int], what: str):
+        """(off, idx, items, end) of GT lists with GLOBAL ids, end = the largest id + 1 (a host int: _pw_pass checks
+        it where the other side's size is known).  An id outside [0, n_other) has no owner: ValueError."""
+        off = np.zeros(len(lists) + 1, np.int64)
+        np.cumsum(np.fromiter((len(l) for l in lists), np.int64, count=len(lists)), out=off[1:])
+        items = int(off[-1])
+        ids = np.fromiter((g for l in lists for g in l), np.int64, count=items)  # int64: no wrap before the check
+        end = int(ids.max()) + 1 if items else 0
+        if items and (ids.min() < 0 or end > (1 << 31 if n_other is None else n_other)):
+            raise ValueError(f"ShardedGallery: a {what} id outside [0, {'2^31' if n_other is None else n_other})")
+        idx = ids.astype(np.int32) if items else np.zeros(1, np.int32)
+        return torch.from_numpy(off).to(self.device), torch.from_numpy(idx).to(self.device), items, end
+
+    def _pw_pass(self, q, n_q: int, row, col):
+        """One evaluation of the gathered captions q against every shard under the measure, no host
+        synchronisation.  row: _pw_csr of every caption's GT videos (global ids, the same on every rank) or
+        None; col: _pw_csr of this shard's videos' GT captions (gathered order) or None.  Returns
+        (t2v ranks | None, t2v 0-based positions int32 [items] | None -- both global, equal on every rank; v2t ranks
+        | None, v2t positions | None -- this shard's videos; v2t recall sums int64 [4] of all shards | None)."""
+        # an item outside the other side would get the zero word, a legitimate score: refuse it (host ints, no sync)
+        if row is not None and row[3] > self.n_global:
+            raise ValueError(f"ShardedGallery: a GT video id outside [0, {self.n_global})")
+        if col is not None and col[3] > n_q:
+            raise ValueError(f"ShardedGallery: a GT caption id outside [0, {n_q})")
+        solo = _solo(self.comm)
+        row_side = col_side = None
+        if row is not None:
+            off, idx, items = row[:3]
+            # each item is scored where its video lives; the other shards hold the zero word, so the SUM of the
+            # scores' integer words is the owner's word on every rank (NaN, +-inf and -0.0 as they are)
+            row_sc = self._pw_items(q, (off, idx), items, False, self.offset)
+            if not solo and items:
+                self.comm.all_reduce(row_sc.view(torch.int64), "sum")
+            # the NaN items' n_global - ... comes from ONE rank (the count entry applies it on an empty shard too)
+            row_side = (off, row_sc, self.n_global if self.rank == 0 else 0)
+        if col is not None:
+            coff, cidx, citems = col[:3]
+            # a shard video's GT captions are all here after the gather: scores and positions are rank-local
+            col_side = (coff, self._pw_items(q, (coff, cidx), citems, True, 0), n_q)
+        rpos, cpos = self._pw_count(q, row_side, col_side)
+        v2t = self._pw_ranks(col_side[0], col_side[1], cpos, n_q) if col is not None else None
+        rec = recall_counts_device(v2t) if col is not None else torch.zeros(4, dtype=torch.int64, device=self.device)
+        parts = ([rpos.to(torch.int64)] if row is not None else []) + [rec.to(torch.int64)]
+        # ONE all-reduce(SUM): the t2v positions and the v2t R@K sums
+        both = reduce_counts(torch.cat(parts), self.comm)
+        t2v = t2v_pos = None
+        if row is not None:
+            t2v_pos = both[:-4].to(torch.int32)
+            t2v = self._pw_ranks(row_side[0], row_side[1], t2v_pos, self.n_global)
+        return t2v, t2v_pos, v2t, cpos, (both[-4:] if col is not None else None)
+
+    def _pw_evaluate_gathered(self, q, n_q: int, t2v_gts, v2t_gts):
+        """(t2v ranks, t2v positions, v2t ranks of ALL videos, this shard's v2t positions) on the host from one
+        _pw_pass."""
+        row = self._pw_csr(t2v_gts, self.n_global, "GT video") if t2v_gts is not None else None
+        col = self._pw_csr(self.local_v2t_lists(v2t_gts), n_q, "GT caption") if v2t_gts is not None else None
+        t2v, t2v_pos, v2t, v2t_pos, _ = self._pw_pass(q, n_q, row, col)
+        if v2t is not None:
+            self._check_layout()
+            v2t = all_gather_var(v2t, self.comm).cpu().numpy().astype(np.int64)
+            v2t_pos = v2t_pos.cpu().numpy().astype(np.int64)
+        if t2v is not None:
+            t2v, t2v_pos = t2v.cpu().numpy().astype(np.int64), t2v_pos.cpu().numpy().astype(np.int64)
+        return t2v, t2v_pos, v2t, v2t_pos
+
+    def _pw_cal_perf(self, q_local, v2t_gt, t2v_gt):
+        q_all = all_gather_var(q_local, self.comm)
+        n_q = q_all.shape[0]
+        t2v_lists = [t2v_gt[i] for i in range(n_q)]  # KeyError on a caption without GT, like metrics.py:142
+        v2t_lists = [v2t_gt[j] for j in range(self.n_global)]
+        t2v, t2v_pos, v2t, v2t_pos = self._pw_evaluate_gathered(self._pw_rows(q_all), n_q, t2v_lists, v2t_lists)
+        # both mAPs from the positions of that one pass: the first GT's position is among every item's
+        firsts = np.cumsum([0] + [len(l) for l in t2v_lists])[:-1]
+        t2v_map = float(np.mean([1.0 / (t2v_pos[f] + 1) if l else 0.0 for f, l in zip(firsts, t2v_lists)]))
+        offs = np.cumsum([0] + [len(l) for l in self.local_v2t_lists(v2t_lists)])
+        aps = [ap_from_positions(v2t_pos[offs[j]:offs[j + 1]] + 1) for j in range(self.n)]
+        s = torch.tensor([float(np.sum(aps))], dtype=torch.float64, device=self.device)
+        v2t_map = float(reduce_counts(s, self.comm).item()) / self.n_global
+        return (tuple(metrics_from_ranks(v2t)) + (v2t_map,), tuple(metrics_from_ranks(t2v)) + (t2v_map,))
+
+    def _pw_topk_merged(self, q_local, k: int):
+        q = self._pw_rows(all_gather_var(q_local, self.comm))  # a single caption may sit on one rank alone
+        k = int(min(k, self.n_global))  # as cmve_pairwise_topk clamps k to the gallery
+        if k < 1:
+            return np.zeros((q.shape[0], 0), np.int64), np.zeros((q.shape[0], 0))
+        if k > _lib.TOPK_MAX:
+            raise ValueError(f"ShardedGallery.topk: k <= {_lib.TOPK_MAX}")
+        if self.n < 1:  # an empty shard: k empty slots
+            idx = torch.full((q.shape[0], k), -1, dtype=torch.int64, device=self.device)
+            sc = torch.full((q.shape[0], k), float("nan"), dtype=torch.float64, device=self.device)
+        else:
+            idx, err = self._pw_topk(q, min(k, self.n))
+            idx = torch.where(idx >= 0, idx + self.offset, idx)
+            idx, sc = pad_topk(idx, -err, k)  # the merge orders by score descending: score = -error
+        ids, sc = merge_topk(idx, sc, k, self.comm, to_host=False)
+        return ids.cpu().numpy(), (-sc).cpu().numpy()
+
     # ---- GT lists restricted to this shard ----
     def local_gt_csr(self, gts_global: Sequence[Sequence[int]]):
-        """t2v: every caption's GT videos inside this shard, re-indexed locally."""
+        """t2v: every caption's GT videos inside this shard, re-indexed locally.  Under a non-cosine measure:
+        (off, idx, items, end) of ALL of them with global ids -- the same on every rank (the items are scored where
+        they live)."""
+        if self.measure != 'cosine':
+            return self._pw_csr(gts_global, self.n_global, "GT video")
         return self._csr(local_gt_lists(gts_global, self.offset, self.offset + self.n))
 
     def local_v2t_csr(self, v2t_gts_global: Sequence[Sequence[int]]):
-        """v2t: the GT captions (gathered order) of this shard's videos."""
+        """v2t: the GT captions (gathered order) of this shard's videos (a measure: (off, idx, items, end); the
+        caption ids are checked against n_q where it is known, in the evaluation)."""
+        if self.measure != 'cosine':
+            return self._pw_csr(self.local_v2t_lists(v2t_gts_global), None, "GT caption")
         return self._csr(self.local_v2t_lists(v2t_gts_global))
 
     def local_v2t_lists(self, v2t_gts_global):
@@ -550,8 +713,12 @@ class ShardedGallery:
         gt_csr: (off, idx) from ``local_gt_csr`` for the GATHERED query order.  The overflow flag of
         the undecided-pair list rides the counts' all-reduce, so every rank sees the same flag: all of
         them grow their lists and redo the batch together (a rank that trusted its own flag alone would
-        return incomplete counts while another waited in the next all-gather)."""
+        return incomplete counts while another waited in the next all-gather).  Under a non-cosine measure
+        gt_csr is ``local_gt_csr``'s global-id lists and nothing can overflow."""
         q_all = self.all_gather_rows(q_local)
+        if self.measure != 'cosine':
+            ranks, _ = self.rank_queries_device(q_all, gt_csr, n_q)
+            return ranks.cpu().numpy().astype(np.int64) if return_host else ranks
         for _attempt in range(4):
             ranks, ovf = self.rank_queries_device(q_all, gt_csr, n_q, mode, events, chunks)
             if not bool(ovf.item()):
@@ -567,7 +734,11 @@ class ShardedGallery:
                             chunks: int = 1):
         """rank_queries on already-gathered queries with no host synchronisation: returns
         (ranks int64 [n_q] on the device, overflow flag bool [] on the device).  A set flag means the
-        undecided-pair list overflowed and the counts are incomplete: grow the workspace and redo."""
+        undecided-pair list overflowed and the counts are incomplete: grow the workspace and redo (never set
+        under a non-cosine measure)."""
+        if self.measure != 'cosine':
+            t2v = self._pw_pass(self._pw_rows(q_all), n_q, gt_csr, None)[0]
+            return t2v, torch.zeros((), dtype=torch.bool, device=self.device)
         q = self._pack(q_all, mode)
         sgt = merge_gt_scores(self._row_gt(q, gt_csr, mode), self.comm)
         cnt, _, ovf = self._count(q, mode, sgt, None, events=events, chunks=chunks)
@@ -584,7 +755,13 @@ class ShardedGallery:
         col_csr: this shard's v2t GT lists into the gathered captions (``local_v2t_csr``) or None.
         Returns (t2v ranks int64 [n_q] | None -- global, equal on every rank; v2t ranks int64 [n] | None
         -- this shard's videos; v2t recall sums int64 [4] | None -- all shards; overflow bool []).  q: the
-        captions already packed (``_pack(q_all, mode)``), reused across passes over the same captions."""
+        captions already packed (``_pack(q_all, mode)``), reused across passes over the same captions.
+        Under a non-cosine measure row_csr / col_csr are ``local_gt_csr``'s / ``local_v2t_csr``'s tuples (a GT
+        video id outside the gallery or a GT caption id outside [0, n_q) raises ValueError),
+        q the captions' rows (``_pw_rows``), and the flag is never set."""
+        if self.measure != 'cosine':
+            t2v, _, v2t, _, rec = self._pw_pass(self._pw_rows(q_all) if q is None else q, n_q, row_csr, col_csr)
+            return t2v, v2t, rec, torch.zeros((), dtype=torch.bool, device=self.device)
         if q is None:
             q = self._pack(q_all, mode)
         sgt_r = merge_gt_scores(self._row_gt(q, row_csr, mode), self.comm) if row_csr is not None else None
@@ -612,6 +789,9 @@ class ShardedGallery:
         (global) of gathered caption i; v2t_gts[v] = GT caption ids (gathered order) of global video v.
         Returns (t2v ranks [n_q] | None, v2t ranks [n_global] | None)."""
         q_all = all_gather_var(q_local, self.comm)
+        if self.measure != 'cosine':
+            t2v, _, v2t, _ = self._pw_evaluate_gathered(self._pw_rows(q_all), q_all.shape[0], t2v_gts, v2t_gts)
+            return t2v, v2t
         return self._evaluate_gathered(q_all, self._pack(q_all, mode), t2v_gts, v2t_gts, mode)
 
     def _evaluate_gathered(self, q_all, q, t2v_gts, v2t_gts, mode: int):
@@ -651,7 +831,10 @@ class ShardedGallery:
         6-tuples (v2t (r1, r5, r10, medr, meanr, mAP), t2v (...)) on every rank.  v2t_gt: list over the
         n_global videos of GT caption ids (gathered order); t2v_gt: dict or list over the captions of GT
         video ids (metrics.get_gt's outputs).  t2v mAP is the AP of each caption's FIRST GT
-        (metrics.py:61-79); v2t mAP is over every GT caption of a video (metrics.py:83-102)."""
+        (metrics.py:61-79); v2t mAP is over every GT caption of a video (metrics.py:83-102).  Under a
+        non-cosine measure ranks and both mAPs come from the positions of ONE pass, multi-GT lists included."""
+        if self.measure != 'cosine':
+            return self._pw_cal_perf(q_local, v2t_gt, t2v_gt)
         # the captions are gathered and packed ONCE; every pass below (both directions, the first-GT t2v pass, the
         # v2t GT positions) reuses them
         q_all = all_gather_var(q_local, self.comm)
@@ -676,7 +859,11 @@ class ShardedGallery:
         return (tuple(metrics_from_ranks(v2t)) + (v2t_map,), tuple(metrics_from_ranks(t2v)) + (t2v_map,))
 
     def topk(self, q_local: torch.Tensor, k: int, mode: int = _lib.SIM_F16):
-        """Global exact top-k (global ids, fp64 cosines) of all gathered queries."""
+        """Global exact top-k (global ids, fp64 cosines) of all gathered queries.  Under a non-cosine measure:
+        (ids int64, ERRORS fp64) ordered (error asc, global id asc), NaN last, k clamped to the gallery -- the
+        order of cmve_pairwise_topk on the whole gallery (inference.py:78-80)."""
+        if self.measure != 'cosine':
+            return self._pw_topk_merged(q_local, k)
         q_all = self.all_gather_rows(q_local)
         q = engine.RowSet(q_all, with_lo=self.shard.has_lo, with_f16=self.shard.has_f16, device=self.device)
         kk = min(k, self.shard.n)

@@ -418,6 +418,78 @@ def pairwise_gt_eval(a, b, metric: int, alpha: float, beta: float, score_dtype, 
     return (r.positions(0), r.ranks(0)), (r.positions(1), r.ranks(1))
 
 
+def _pw_pair(a, b, name: str):
+    a, b = _pw_rows(a, name), _pw_rows(b, name)
+    if a.shape[1] != b.shape[1]:
+        raise ValueError(f"{name}: shapes {tuple(a.shape)} and {tuple(b.shape)} do not match")
+    return a, b
+
+
+def _pw_code(score_dtype) -> int:
+    return _lib.CMVE_F64 if score_dtype == torch.float64 else _lib.CMVE_F32
+
+
+def pairwise_item_scores(a, b, metric: int, alpha: float, beta: float, score_dtype, off: torch.Tensor,
+                         idx: torch.Tensor, n_items: int, col_dir: bool = False, idx_base: int = 0) -> torch.Tensor:
+    """fp64 [n_items] on the device: the score of every listed item this call owns (``cmve_pairwise_item_scores``,
+    K18's launch 1 for a gallery sharded by rows).  (off, idx): one CSR side on the device (``csr``) -- the lists of
+    a's rows naming GLOBAL rows of b (col_dir: of b's rows naming global rows of a), of which the operand given here
+    is [idx_base, idx_base + n).  An item outside that range gets the all-zero word: the int64 SUM over the shards of
+    ``out.view(torch.int64)`` is every item's score, bit for bit.  No host copy, no synchronisation."""
+    a, b = _pw_pair(a, b, "pairwise_item_scores")
+    if idx.numel() < int(n_items) or idx.dtype != torch.int32 or off.dtype != torch.int64:
+        raise ValueError(f"pairwise_item_scores: {n_items} items need int64 offsets and as many int32 indices")
+    out = torch.empty(max(int(n_items), 1), dtype=torch.float64, device=a.device)
+    check(lib.cmve_pairwise_item_scores(handle(a.device), _ptr(a), _dtype_code(a), _pw_ld(a), a.shape[0], _ptr(b),
+                                        _dtype_code(b), _pw_ld(b), b.shape[0], a.shape[1], metric, float(alpha),
+                                        float(beta), _pw_code(score_dtype), _ptr(off), _ptr(idx),
+                                        off.numel() - 1, int(n_items), 1 if col_dir else 0, int(idx_base), _ptr(out)),
+          "cmve_pairwise_item_scores")
+    return out[:int(n_items)]
+
+
+def pairwise_count(a, b, metric: int, alpha: float, beta: float, score_dtype, row=None, col=None):
+    """(row_pos, col_pos): int32 device tensors of 0-based positions counted over THIS call's pairs against the
+    caller's item scores (``cmve_pairwise_count``, K18's launch 2).  row = (off [na + 1], scores fp64 [items], n):
+    a non-NaN item's word is #{ j : e(i, j) < score }; a NaN item's is n - (NaN items of its list) + (its place
+    among them) when n > 0 and 0 when n == 0 (one shard passes the global n).  col: the mirror; a direction left
+    None gives None.  No host copy, no synchronisation."""
+    a, b = _pw_pair(a, b, "pairwise_count")
+    sides = []
+    for side, n_lists in ((row, a.shape[0]), (col, b.shape[0])):
+        if side is None:
+            sides.append((None, None, 0, 0, None))
+            continue
+        off, sc, n = side
+        if off.numel() != n_lists + 1:
+            raise ValueError(f"pairwise_count: {off.numel() - 1} lists for {n_lists} rows")
+        if sc.dtype != torch.float64 or not sc.is_contiguous():
+            raise TypeError("pairwise_count: item scores are contiguous float64")
+        sides.append((off, sc, sc.numel(), int(n), torch.empty(max(sc.numel(), 1), dtype=torch.int32,
+                                                               device=a.device)))
+    (roff, rsc, ritems, rn, rpos), (coff, csc, citems, cn, cpos) = sides
+    check(lib.cmve_pairwise_count(handle(a.device), _ptr(a), _dtype_code(a), _pw_ld(a), a.shape[0], _ptr(b),
+                                  _dtype_code(b), _pw_ld(b), b.shape[0], a.shape[1], metric, float(alpha),
+                                  float(beta), _pw_code(score_dtype), _ptr(roff), _ptr(rsc), ritems, rn, _ptr(rpos),
+                                  _ptr(coff), _ptr(csc), citems, cn, _ptr(cpos)), "cmve_pairwise_count")
+    return (None if rpos is None else rpos[:ritems]), (None if cpos is None else cpos[:citems])
+
+
+def pairwise_list_ranks(off: torch.Tensor, scores: torch.Tensor, pos: torch.Tensor, n_m: int) -> torch.Tensor:
+    """int64 [n_lists] on the device: the 1-based best-GT rank of every list from its items' scores (fp64) and
+    0-based positions (int32) -- ``_PairwisePositions.ranks`` without the host (``cmve_pairwise_list_ranks``)."""
+    n_lists = off.numel() - 1
+    if scores.dtype != torch.float64 or pos.dtype != torch.int32 or scores.numel() != pos.numel():
+        raise TypeError("pairwise_list_ranks: float64 scores and int32 positions of one length")
+    out = torch.empty(max(n_lists, 1), dtype=torch.int64, device=off.device)
+    if scores.numel() == 0:  # every list is empty: the kernel reads neither, but the entry takes no NULL
+        scores, pos = scores.new_zeros(1), pos.new_zeros(1)
+    check(lib.cmve_pairwise_list_ranks(handle(off.device), _ptr(off), _ptr(scores.contiguous()),
+                                       _ptr(pos.contiguous()), n_lists, int(n_m), _ptr(out)),
+          "cmve_pairwise_list_ranks")
+    return out[:n_lists]
+
+
 def pairwise_topk(q, g, metric: int, alpha: float, beta: float, score_dtype, k: int, to_host: bool = True,
                   ws: Optional[torch.Tensor] = None, ws_bytes: Optional[int] = None, geometry: int = 0):
     """The k rows of g with the smallest error per row of q under a non-cosine measure, by (error asc, index asc),

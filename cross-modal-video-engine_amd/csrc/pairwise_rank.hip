@@ -8,7 +8,10 @@
 //   positions: launch 1 scores the listed items (one thread each, O(N_c) of them); launch 2 is K10's 64 x 128
 //              tile loop whose epilogue, instead of storing, counts the tile's outputs below each item score of
 //              the rows and columns it holds: both directions from one pass over the pairs, one integer
-//              atomicAdd per (item, tile) -- bit-reproducible.
+//              atomicAdd per (item, tile) -- bit-reproducible.  The two launches are entries of their own as well
+//              (cmve_pairwise_item_scores with shard ownership, cmve_pairwise_count with the caller's scores) for a
+//              gallery sharded by rows: a position is the plain sum of the shards' counts against one item score,
+//              and cmve_pairwise_list_ranks turns the summed positions into best-GT ranks on the device.
 //   top-k:     gallery chunks scored into the caller's workspace (-error: K12f orders by score descending) and
 //              merged into the running best by K12f (cmve_topk_dense_merge); a small-row geometry of the tile
 //              loop serves n_q <= 8 (inference.py's single caption).  With few queries the chunk is cut into
@@ -20,15 +23,18 @@ namespace cmve {
 __device__ __forceinline__ double pw_round(double x, int f32) { return f32 ? (double)(float)x : x; }
 
 // ---- launch 1: the score of every listed item -------------------------------------------------------------
-// item p of list `owner` (off[owner] <= p < off[owner + 1]) names row idx[p] of the other side; col_dir: the lists
-// belong to B rows and name A rows.  An index outside the other side scores NaN (nothing is read).
+// item p of list `owner` (off[owner] <= p < off[owner + 1]) names row idx[p] - idx_base of the other side; col_dir:
+// the lists belong to B rows and name A rows.  An index outside the other side (nothing is read) scores NaN, or --
+// `shard`: idx holds global rows, this call owns [idx_base, idx_base + n_other) of them -- the all-zero word, so
+// that an integer SUM of the shards' outputs is the owner's word.
 template <int METRIC, typename TA, typename TB>
 __global__ __launch_bounds__(256) void pwr_item_kernel(const TA* __restrict__ A, int64_t lda, int64_t na,
                                                        const TB* __restrict__ B, int64_t ldb, int64_t nb, int64_t d,
                                                        double alpha, double beta, int f32,
                                                        const int64_t* __restrict__ off,
                                                        const int32_t* __restrict__ idx, int64_t n_lists,
-                                                       int64_t n_items, int col_dir, double* __restrict__ sc) {
+                                                       int64_t n_items, int col_dir, int64_t idx_base, int shard,
+                                                       double* __restrict__ sc) {
   const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (p >= n_items) return;
   int64_t lo = 0, hi = n_lists;  // first list whose offset exceeds p, minus one
@@ -36,9 +42,9 @@ __global__ __launch_bounds__(256) void pwr_item_kernel(const TA* __restrict__ A,
     const int64_t mid = (lo + hi) >> 1;
     if (off[mid + 1] > p) hi = mid; else lo = mid + 1;
   }
-  const int64_t owner = lo, other = idx[p];
+  const int64_t owner = lo, other = (int64_t)idx[p] - idx_base;
   const int64_t i = col_dir ? other : owner, j = col_dir ? owner : other;
-  double s = NAN;
+  double s = shard ? 0.0 : (double)NAN;
   if (owner < n_lists && i >= 0 && i < na && j >= 0 && j < nb)
     s = pw_round(pw_pair_score<METRIC>(A + i * lda, B + j * ldb, d, alpha, beta), f32);
   sc[p] = s;
@@ -46,17 +52,21 @@ __global__ __launch_bounds__(256) void pwr_item_kernel(const TA* __restrict__ A,
 
 // ---- launch 2: K10's tile loop with a counting epilogue -----------------------------------------------------
 // row_pos[p] += #{ j in the tile's columns, j < nb : e(i, j) < row_sc[p] } for every item p of every A row i of the
-// tile (col_pos: the mirror over i < na).  A NaN item is never counted (x < NaN is false): the tile of its list in
-// the first block column / row stores cmve_gt_positions_from_matrix's value for it instead, n - (NaN items of the
-// list) + (its place among them).  pos must be zero on entry.
+// tile (col_pos: the mirror over i < na).  The item scores are the caller's.  A NaN item is never counted (x < NaN
+// is false): with row_n > 0 the tile of its list in the first block column / row stores
+// cmve_gt_positions_from_matrix's value for it instead, row_n - (NaN items of the list) + (its place among them)
+// (row_n == 0: its word stays 0 -- another shard of the gallery stores it).  The grid has at least one block row and
+// column, so the rule also runs when na or nb is 0.  pos must be zero on entry.
 template <int METRIC, typename TA, typename TB>
 __global__ __launch_bounds__(256) void pwr_count_kernel(const TA* __restrict__ A, int64_t lda, int64_t na,
                                                         const TB* __restrict__ B, int64_t ldb, int64_t nb, int64_t d,
                                                         double alpha, double beta, int f32,
                                                         const int64_t* __restrict__ row_off,
-                                                        const double* __restrict__ row_sc, int32_t* __restrict__ row_pos,
+                                                        const double* __restrict__ row_sc, int64_t row_n,
+                                                        int32_t* __restrict__ row_pos,
                                                         const int64_t* __restrict__ col_off,
-                                                        const double* __restrict__ col_sc, int32_t* __restrict__ col_pos) {
+                                                        const double* __restrict__ col_sc, int64_t col_n,
+                                                        int32_t* __restrict__ col_pos) {
   using G = PwWide;
   __shared__ __attribute__((aligned(16))) double sa[G::KS][G::PA];
   __shared__ __attribute__((aligned(16))) double sb[G::KS][G::PB];
@@ -98,7 +108,7 @@ __global__ __launch_bounds__(256) void pwr_count_kernel(const TA* __restrict__ A
   if (tx == 0 && mr_max) atomicMax(&s_m[0], mr_max);
   if (ty == 0 && mc_max) atomicMax(&s_m[1], mc_max);
   // NaN items: the last positions of the row / column, in list order (as gtpos_rows_kernel / gtpos_cols_kernel)
-  if (blockIdx.x == 0 && tx == 0) {
+  if (blockIdx.x == 0 && tx == 0 && row_n > 0) {
 #pragma unroll
     for (int u = 0; u < G::NA; ++u) {
       int n_nan = 0, run = 0;
@@ -108,11 +118,11 @@ __global__ __launch_bounds__(256) void pwr_count_kernel(const TA* __restrict__ A
       }
       for (int a = 0; a < mr[u] && n_nan; ++a) {
         const double t = row_sc[ro[u] + a];
-        if (t != t) row_pos[ro[u] + a] = (int32_t)(nb - n_nan + run++);
+        if (t != t) row_pos[ro[u] + a] = (int32_t)(row_n - n_nan + run++);
       }
     }
   }
-  if (blockIdx.y == 0 && ty == 0) {
+  if (blockIdx.y == 0 && ty == 0 && col_n > 0) {
 #pragma unroll
     for (int v = 0; v < G::NB; ++v) {
       int n_nan = 0, run = 0;
@@ -122,7 +132,7 @@ __global__ __launch_bounds__(256) void pwr_count_kernel(const TA* __restrict__ A
       }
       for (int a = 0; a < mc[v] && n_nan; ++a) {
         const double t = col_sc[co[v] + a];
-        if (t != t) col_pos[co[v] + a] = (int32_t)(na - n_nan + run++);
+        if (t != t) col_pos[co[v] + a] = (int32_t)(col_n - n_nan + run++);
       }
     }
   }
@@ -256,6 +266,55 @@ constexpr int PWR_KMAX = 2048;  // K12f's limit (TD_KMAX, topk.hip): TOPK_MAX of
   else if (b_dtype == CMVE_F64) { using TA = float; using TB = double; __VA_ARGS__; }                    \
   else { using TA = float; using TB = float; __VA_ARGS__; }
 
+// ---- the best-GT rank of every list from its items' scores and positions (one thread per list) ------------------
+// 1 + the least position over the non-NaN items; an empty list ranks n_m + 1, a list whose items all score NaN n_m
+// (cmve_rank_from_matrix's rules, metrics.py:137-147)
+__global__ __launch_bounds__(256) void pwr_list_ranks_kernel(const int64_t* __restrict__ off,
+                                                             const double* __restrict__ sc,
+                                                             const int32_t* __restrict__ pos, int64_t n_lists,
+                                                             int64_t n_m, int64_t* __restrict__ ranks) {
+  const int64_t l = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (l >= n_lists) return;
+  const int64_t lo = off[l], hi = off[l + 1];
+  int64_t best = n_m - 1;  // every item NaN
+  bool any = false;
+  for (int64_t p = lo; p < hi; ++p) {
+    const double t = sc[p];
+    if (t != t) continue;
+    const int64_t q = pos[p];
+    best = (any && best < q) ? best : q;
+    any = true;
+  }
+  ranks[l] = hi > lo ? best + 1 : n_m + 1;
+}
+
+// launch 1 of one CSR side on the stream (n_items > 0)
+static void pwr_item_launch(hipStream_t st, const void* A, int32_t a_dtype, int64_t lda, int64_t na, const void* B,
+                            int32_t b_dtype, int64_t ldb, int64_t nb, int64_t d, int32_t metric, double alpha,
+                            double beta, int f32, const int64_t* off, const int32_t* idx, int64_t n_items, int col_dir,
+                            int64_t idx_base, int shard, double* sc) {
+  PW_DISPATCH_METRIC(metric, M, PWR_TYPES(a_dtype, b_dtype, TA, TB, {
+    hipLaunchKernelGGL((pwr_item_kernel<M, TA, TB>), dim3((unsigned)((n_items + 255) / 256)), dim3(256), 0, st,
+                       (const TA*)A, lda, na, (const TB*)B, ldb, nb, d, alpha, beta, f32, off, idx, col_dir ? nb : na,
+                       n_items, col_dir, idx_base, shard, sc);
+  }))
+}
+
+// launch 2 on the stream: THE counting kernel, over at least one block row and column (a direction whose pos is
+// NULL is skipped; pos zeroed by the caller)
+static void pwr_count_launch(hipStream_t st, const void* A, int32_t a_dtype, int64_t lda, int64_t na, const void* B,
+                             int32_t b_dtype, int64_t ldb, int64_t nb, int64_t d, int32_t metric, double alpha,
+                             double beta, int f32, const int64_t* row_off, const double* row_sc, int64_t row_n,
+                             int32_t* row_pos, const int64_t* col_off, const double* col_sc, int64_t col_n,
+                             int32_t* col_pos) {
+  const dim3 grid((unsigned)std::max<int64_t>(1, (nb + PW_TB - 1) / PW_TB),
+                  (unsigned)std::max<int64_t>(1, (na + PW_TA - 1) / PW_TA));
+  PW_DISPATCH_METRIC(metric, M, PWR_TYPES(a_dtype, b_dtype, TA, TB, {
+    hipLaunchKernelGGL((pwr_count_kernel<M, TA, TB>), grid, dim3(256), 0, st, (const TA*)A, lda, na, (const TB*)B, ldb,
+                       nb, d, alpha, beta, f32, row_off, row_sc, row_n, row_pos, col_off, col_sc, col_n, col_pos);
+  }))
+}
+
 }  // namespace cmve
 
 using namespace cmve;
@@ -301,23 +360,87 @@ extern "C" int cmve_pairwise_positions(cmve_handle_t h, const void* A, int32_t a
   double* col_sc = row_sc + row_items;
   if (row_items) CMVE_HIP(hipMemsetAsync(row_pos, 0, sizeof(int32_t) * row_items, st));
   if (col_items) CMVE_HIP(hipMemsetAsync(col_pos, 0, sizeof(int32_t) * col_items, st));
-  if (na == 0 || nb == 0) return CMVE_OK;  // no pair: every count is zero
+  if (na == 0 || nb == 0) return CMVE_OK;  // no pair: every count is zero (and a NaN item's n - ... has n = 0)
   const int f32 = score_dtype == CMVE_F32;
-  const dim3 grid((unsigned)((nb + PW_TB - 1) / PW_TB), (unsigned)((na + PW_TA - 1) / PW_TA));
-  PW_DISPATCH_METRIC(metric, M, PWR_TYPES(a_dtype, b_dtype, TA, TB, {
-    if (row_items)
-      hipLaunchKernelGGL((pwr_item_kernel<M, TA, TB>), dim3((unsigned)((row_items + 255) / 256)), dim3(256), 0, st,
-                         (const TA*)A, lda, na, (const TB*)B, ldb, nb, d, alpha, beta, f32, row_off, row_idx, na,
-                         row_items, 0, row_sc);
-    if (col_items)
-      hipLaunchKernelGGL((pwr_item_kernel<M, TA, TB>), dim3((unsigned)((col_items + 255) / 256)), dim3(256), 0, st,
-                         (const TA*)A, lda, na, (const TB*)B, ldb, nb, d, alpha, beta, f32, col_off, col_idx, nb,
-                         col_items, 1, col_sc);
-    hipLaunchKernelGGL((pwr_count_kernel<M, TA, TB>), grid, dim3(256), 0, st, (const TA*)A, lda, na, (const TB*)B, ldb,
-                       nb, d, alpha, beta, f32, row_off, (const double*)row_sc, row_items ? row_pos : (int32_t*)nullptr,
-                       col_off, (const double*)col_sc, col_items ? col_pos : (int32_t*)nullptr);
-  }))
+  // its own item launches (an index outside the other side scores NaN), then the counting kernel of
+  // cmve_pairwise_count with the whole sides as n
+  if (row_items)
+    pwr_item_launch(st, A, a_dtype, lda, na, B, b_dtype, ldb, nb, d, metric, alpha, beta, f32, row_off, row_idx,
+                    row_items, 0, 0, 0, row_sc);
+  if (col_items)
+    pwr_item_launch(st, A, a_dtype, lda, na, B, b_dtype, ldb, nb, d, metric, alpha, beta, f32, col_off, col_idx,
+                    col_items, 1, 0, 0, col_sc);
+  pwr_count_launch(st, A, a_dtype, lda, na, B, b_dtype, ldb, nb, d, metric, alpha, beta, f32, row_off, row_sc, nb,
+                   row_items ? row_pos : nullptr, col_off, col_sc, na, col_items ? col_pos : nullptr);
   return check_launch("pairwise_positions");
+}
+
+extern "C" int cmve_pairwise_item_scores(cmve_handle_t h, const void* A, int32_t a_dtype, int64_t lda, int64_t na,
+                                         const void* B, int32_t b_dtype, int64_t ldb, int64_t nb, int64_t d,
+                                         int32_t metric, double alpha, double beta, int32_t score_dtype,
+                                         const int64_t* off, const int32_t* idx, int64_t n_lists, int64_t n_items,
+                                         int32_t col_dir, int64_t idx_base, double* out) {
+  CMVE_REQUIRE(h && (A || !na) && (B || !nb) && off && (n_items <= 0 || (idx && out)),
+               "cmve_pairwise_item_scores: NULL argument");
+  CMVE_REQUIRE(na >= 0 && nb >= 0 && na < (1ll << 31) && nb < (1ll << 31) && d > 0 && lda >= d && ldb >= d,
+               "cmve_pairwise_item_scores: bad shape");
+  CMVE_REQUIRE(pwr_dtypes_ok(a_dtype, b_dtype, score_dtype),
+               "cmve_pairwise_item_scores: dtypes must be CMVE_F32/CMVE_F64");
+  CMVE_REQUIRE(metric >= CMVE_PW_SQ_L2 && metric <= CMVE_PW_DOT, "cmve_pairwise_item_scores: unknown metric %d", metric);
+  CMVE_REQUIRE(n_items >= 0 && n_items < (1ll << 31) * 256, "cmve_pairwise_item_scores: bad item count (%lld)",
+               (long long)n_items);
+  CMVE_REQUIRE(col_dir == 0 || col_dir == 1, "cmve_pairwise_item_scores: col_dir must be 0 or 1");
+  CMVE_REQUIRE(n_lists == (col_dir ? nb : na),
+               "cmve_pairwise_item_scores: %lld lists for the %lld rows that own them", (long long)n_lists,
+               (long long)(col_dir ? nb : na));
+  if (n_items == 0) return CMVE_OK;
+  pwr_item_launch(h->stream, A, a_dtype, lda, na, B, b_dtype, ldb, nb, d, metric, alpha, beta,
+                  score_dtype == CMVE_F32, off, idx, n_items, col_dir, idx_base, 1, out);
+  return check_launch("pairwise_item_scores");
+}
+
+extern "C" int cmve_pairwise_count(cmve_handle_t h, const void* A, int32_t a_dtype, int64_t lda, int64_t na,
+                                   const void* B, int32_t b_dtype, int64_t ldb, int64_t nb, int64_t d, int32_t metric,
+                                   double alpha, double beta, int32_t score_dtype, const int64_t* row_off,
+                                   const double* row_sc, int64_t row_items, int64_t row_n, int32_t* row_pos,
+                                   const int64_t* col_off, const double* col_sc, int64_t col_items, int64_t col_n,
+                                   int32_t* col_pos) {
+  CMVE_REQUIRE(h && (A || !na) && (B || !nb), "cmve_pairwise_count: NULL argument");
+  CMVE_REQUIRE(na >= 0 && nb >= 0 && na < (1ll << 31) && nb < (1ll << 31) && d > 0 && lda >= d && ldb >= d,
+               "cmve_pairwise_count: bad shape");
+  CMVE_REQUIRE(pwr_dtypes_ok(a_dtype, b_dtype, score_dtype), "cmve_pairwise_count: dtypes must be CMVE_F32/CMVE_F64");
+  CMVE_REQUIRE(metric >= CMVE_PW_SQ_L2 && metric <= CMVE_PW_DOT, "cmve_pairwise_count: unknown metric %d", metric);
+  if (!row_pos) row_items = 0;
+  if (!col_pos) col_items = 0;
+  CMVE_REQUIRE(row_items >= 0 && col_items >= 0 && row_n >= 0 && col_n >= 0 && row_n < (1ll << 31) &&
+                   col_n < (1ll << 31) && row_items < (1ll << 31) * 256 && col_items < (1ll << 31) * 256,
+               "cmve_pairwise_count: bad counts (%lld, %lld items; n %lld, %lld)", (long long)row_items,
+               (long long)col_items, (long long)row_n, (long long)col_n);
+  CMVE_REQUIRE(!row_pos || (row_off && (row_sc || !row_items)), "cmve_pairwise_count: row lists missing");
+  CMVE_REQUIRE(!col_pos || (col_off && (col_sc || !col_items)), "cmve_pairwise_count: column lists missing");
+  if (row_items + col_items == 0) return CMVE_OK;
+  CMVE_REQUIRE((na + PW_TA - 1) / PW_TA < 65536, "cmve_pairwise_count: too many rows in A (%lld)", (long long)na);
+  const hipStream_t st = h->stream;
+  if (row_items) CMVE_HIP(hipMemsetAsync(row_pos, 0, sizeof(int32_t) * row_items, st));
+  if (col_items) CMVE_HIP(hipMemsetAsync(col_pos, 0, sizeof(int32_t) * col_items, st));
+  // an empty shard has no pair to count; it still runs one block row / column where a direction has items AND an n
+  // to apply: the NaN items' words are the caller's n, not this shard's
+  if ((na == 0 || nb == 0) && !(row_items && row_n) && !(col_items && col_n)) return CMVE_OK;
+  pwr_count_launch(st, A, a_dtype, lda, na, B, b_dtype, ldb, nb, d, metric, alpha, beta, score_dtype == CMVE_F32,
+                   row_off, row_sc, row_n, row_items ? row_pos : nullptr, col_off, col_sc, col_n,
+                   col_items ? col_pos : nullptr);
+  return check_launch("pairwise_count");
+}
+
+extern "C" int cmve_pairwise_list_ranks(cmve_handle_t h, const int64_t* off, const double* sc, const int32_t* pos,
+                                        int64_t n_lists, int64_t n_m, int64_t* ranks) {
+  CMVE_REQUIRE(h && off && sc && pos && (n_lists <= 0 || ranks), "cmve_pairwise_list_ranks: NULL argument");
+  CMVE_REQUIRE(n_lists >= 0 && n_m >= 0 && n_lists < (1ll << 31) * 256,
+               "cmve_pairwise_list_ranks: bad counts (%lld lists, n %lld)", (long long)n_lists, (long long)n_m);
+  if (n_lists == 0) return CMVE_OK;
+  hipLaunchKernelGGL(pwr_list_ranks_kernel, dim3((unsigned)((n_lists + 255) / 256)), dim3(256), 0, h->stream, off, sc,
+                     pos, n_lists, n_m, ranks);
+  return check_launch("pairwise_list_ranks");
 }
 
 extern "C" int cmve_pairwise_topk_workspace(int64_t n_q, int64_t n_g, int32_t k, int32_t metric, int64_t* min_bytes,

@@ -663,6 +663,42 @@ int cmve_pairwise_positions(cmve_handle_t h, const void* A, int32_t a_dtype, int
                             double beta, int32_t score_dtype, const int64_t* row_off, const int32_t* row_idx,
                             int64_t row_items, int32_t* row_pos, const int64_t* col_off, const int32_t* col_idx,
                             int64_t col_items, int32_t* col_pos, void* ws, int64_t ws_bytes);
+/* The two launches of cmve_pairwise_positions as entries of their own, for a gallery sharded by rows over several
+ * GPUs (cmve/dist.py ShardedGallery(measure=)): a position counts with a strict < and no index tie-break, so it is
+ * the plain sum over the shards of their counts against the SAME item score.  Replace, as cmve_pairwise_positions
+ * does: LINAS-engine/evaluation.py:17-36,41-72 + util/metrics.py:61-102,124-157 (validate.py:15-54 cal_perf), and
+ * the inference.py:78-80 ranking over a gallery too large for one GPU.  All three are enqueued on the handle's
+ * stream, allocate nothing and never synchronise; integer atomics only: two calls give the same words.
+ *
+ * cmve_pairwise_item_scores -- launch 1 with shard ownership.  One CSR side: off [n_lists + 1] / idx [n_items];
+ *   col_dir 0: the lists belong to the A rows (n_lists == na) and idx names rows of B, col_dir 1 the mirror
+ *   (n_lists == nb, idx names rows of A).  idx holds GLOBAL rows of the other side, of which this call's operand is
+ *   [idx_base, idx_base + n_other): item p is scored iff 0 <= idx[p] - idx_base < n_other, on the chain above
+ *   (rounded to score_dtype); any other item gets the all-zero 8-byte word.  out: fp64 [n_items] (device).  Each
+ *   item has one owner, so an int64 SUM of the shards' outputs viewed as integer words is the owner's word, NaN,
+ *   +-inf and -0.0 included (a MAX with a sentinel is not: the errors are unbounded).
+ * cmve_pairwise_count -- launch 2 with the CALLER's item scores row_sc [row_items] / col_sc [col_items] (fp64,
+ *   device) over this call's na x nb pairs; row_off [na + 1], col_off [nb + 1]; row_pos / col_pos int32, either NULL
+ *   (that direction is skipped); no workspace.  For a non-NaN item row_pos[p] = #{ j < nb : e(i, j) < row_sc[p] }.
+ *   A NaN item gets row_n - (NaN items of its list) + (its place among them) when row_n > 0 -- the rule of
+ *   cmve_gt_positions_from_matrix with the caller's n -- and 0 when row_n == 0 (col_n likewise): of the shards
+ *   exactly one passes the global n, and the SUM is the unsharded word.  The rule also holds when na or nb is 0.
+ *   cmve_pairwise_positions is its own item launch followed by this kernel with row_n = nb, col_n = na.
+ * cmve_pairwise_list_ranks -- ranks[l] (int64 [n_lists], device) = the 1-based best-GT rank of list l from its
+ *   items' scores sc and 0-based positions pos (device, never NULL): 1 + the least position over the non-NaN items;
+ *   an empty list ranks n_m + 1, a list whose items all score NaN ranks n_m (util/metrics.py:137-147 as
+ *   cmve_rank_from_matrix reads it). */
+int cmve_pairwise_item_scores(cmve_handle_t h, const void* A, int32_t a_dtype, int64_t lda, int64_t na, const void* B,
+                              int32_t b_dtype, int64_t ldb, int64_t nb, int64_t d, int32_t metric, double alpha,
+                              double beta, int32_t score_dtype, const int64_t* off, const int32_t* idx,
+                              int64_t n_lists, int64_t n_items, int32_t col_dir, int64_t idx_base, double* out);
+int cmve_pairwise_count(cmve_handle_t h, const void* A, int32_t a_dtype, int64_t lda, int64_t na, const void* B,
+                        int32_t b_dtype, int64_t ldb, int64_t nb, int64_t d, int32_t metric, double alpha, double beta,
+                        int32_t score_dtype, const int64_t* row_off, const double* row_sc, int64_t row_items,
+                        int64_t row_n, int32_t* row_pos, const int64_t* col_off, const double* col_sc,
+                        int64_t col_items, int64_t col_n, int32_t* col_pos);
+int cmve_pairwise_list_ranks(cmve_handle_t h, const int64_t* off, const double* sc, const int32_t* pos,
+                             int64_t n_lists, int64_t n_m, int64_t* ranks);
 /* cmve_pairwise_topk -- the k gallery rows of smallest error per query, ordered by (error asc, index asc), NaN last:
  * a stable ascending argsort of cmve_pairwise's row, cut at k.
  * Replaces: LINAS-engine/inference.py:78-80 (cal_error(video_embs, cap_emb, measure) then
