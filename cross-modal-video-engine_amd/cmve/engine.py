@@ -332,10 +332,37 @@ def _pw_ld(t: torch.Tensor) -> int:
     return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
 
 
-class _PairwisePositions:
-    """One ``cmve_pairwise_positions`` call: per direction the 0-based positions, the item scores and the offsets."""
+def l2_count_workspace(a: "RowSet", b: "RowSet", band_cap: int) -> int:
+    """Bytes of workspace ``cmve_l2_count`` needs for a band list of ``band_cap`` pairs (host only: no launch)."""
+    n = C.c_int64()
+    check(lib.cmve_l2_count_workspace(C.byref(a.desc), C.byref(b.desc), int(band_cap), C.byref(n)),
+          "cmve_l2_count_workspace")
+    return n.value
 
-    def __init__(self, a, b, metric, alpha, beta, score_dtype, row_lists=None, col_lists=None):
+
+# Auto dispatch of the K19 filter (``filter=None``): the smallest na * nb at which it beats the fp64 route by more
+# than the spread of the repeats.  tools/l2_filter_bench.py measures both routes at na = nb in {256 .. 4096},
+# D = 1024 (profiles/l2_filter.json, "crossover"): up to 2048 x 2048 a call is its host code and launch gaps either
+# way (2.34 ms against 2.37 ms there, 0.17 ms of spread; below it the packs cost the filter 0.05-0.2 ms), at
+# 4096 x 4096 the filter takes 3.53 ms against 4.64 ms with 0.04 ms of spread.
+L2_FILTER_MIN_PAIRS = 4096 * 4096
+
+
+class _PairwisePositions:
+    """One ``cmve_pairwise_positions`` call: per direction the 0-based positions, the item scores and the offsets.
+
+    ``filter``: False -- the fp64 route (K18); True -- the K19 route for ``PW_L2`` with fp64 score words: both sides
+    packed, the item scores from ``cmve_pairwise_item_scores``, the count from ``cmve_l2_count`` (fp16 MFMA filter +
+    canonical re-score of the band: the same words); None -- the filter when it applies and na * nb reaches
+    ``L2_FILTER_MIN_PAIRS``.  The filter is an accelerator: a band list that overflows is redone once with the
+    reported need, and a band above 1/8 of the pairs runs the fp64 route.  ``filter_stats``: the four counters of
+    the last ``cmve_l2_count`` plus ``redone`` / ``fallback``, or None when the filter was not tried."""
+
+    def __init__(self, a, b, metric, alpha, beta, score_dtype, row_lists=None, col_lists=None, filter=None):
+        self.filter_stats = None
+        applies = metric == _lib.PW_L2 and score_dtype == torch.float64
+        if filter and not applies:
+            raise ValueError("pairwise_gt_positions: filter=True needs PW_L2 with float64 score words")
         a, b = _pw_rows(a, "pairwise_gt_positions"), _pw_rows(b, "pairwise_gt_positions")
         if a.shape[1] != b.shape[1]:
             raise ValueError(f"pairwise_gt_positions: shapes {tuple(a.shape)} and {tuple(b.shape)} do not match")
@@ -355,15 +382,67 @@ class _PairwisePositions:
             items = sum(len(l) for l in lists)
             sides.append((off, idx, items, torch.empty(max(items, 1), dtype=torch.int32, device=dev)))
         (roff, ridx, ritems, rpos), (coff, cidx, citems, cpos) = sides
-        nbytes = pairwise_positions_workspace(na, nb, ritems, citems, metric)
-        ws = torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=dev)
-        code = _lib.CMVE_F64 if score_dtype == torch.float64 else _lib.CMVE_F32
-        check(lib.cmve_pairwise_positions(handle(dev), _ptr(a), _dtype_code(a), _pw_ld(a), na, _ptr(b),
-                                          _dtype_code(b), _pw_ld(b), nb, a.shape[1], metric, float(alpha),
-                                          float(beta), code, _ptr(roff), _ptr(ridx), ritems, _ptr(rpos), _ptr(coff),
-                                          _ptr(cidx), citems, _ptr(cpos), _ptr(ws), nbytes),
-              "cmve_pairwise_positions")
-        sc = ws.cpu().numpy()
+        if filter is None:
+            filter = (applies and na * nb >= L2_FILTER_MIN_PAIRS and alpha != 0 and np.isfinite(alpha)
+                      and np.isfinite(beta))
+        sc = None
+        if filter and na and nb and ritems + citems:
+            sc = self._filtered(a, b, alpha, beta, sides)
+        if sc is None:
+            nbytes = pairwise_positions_workspace(na, nb, ritems, citems, metric)
+            ws = torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=dev)
+            code = _lib.CMVE_F64 if score_dtype == torch.float64 else _lib.CMVE_F32
+            check(lib.cmve_pairwise_positions(handle(dev), _ptr(a), _dtype_code(a), _pw_ld(a), na, _ptr(b),
+                                              _dtype_code(b), _pw_ld(b), nb, a.shape[1], metric, float(alpha),
+                                              float(beta), code, _ptr(roff), _ptr(ridx), ritems, _ptr(rpos), _ptr(coff),
+                                              _ptr(cidx), citems, _ptr(cpos), _ptr(ws), nbytes),
+                  "cmve_pairwise_positions")
+            sc = ws.cpu().numpy()
+        self._collect(sides, sc)
+
+    def _filtered(self, a, b, alpha, beta, sides):
+        """The K19 route into the sides' position buffers; the items' scores (host), or None when the band is too
+        large for the filter to pay (the caller then runs the fp64 route)."""
+        (roff, ridx, ritems, rpos), (coff, cidx, citems, cpos) = sides
+        na, nb, dev, h = a.shape[0], b.shape[0], a.device, handle(a.device)
+        ra, rb = RowSet(a, with_lo=False, device=dev), RowSet(b, with_lo=False, device=dev)
+        a, b = ra.raw, rb.raw
+        # the items' scores, then the four counters, in ONE buffer: one copy to the host brings both
+        buf = torch.empty(ritems + citems + 4, dtype=torch.float64, device=dev)
+        start = 0
+        for off, idx, items, col_dir, n_other in ((roff, ridx, ritems, 0, nb), (coff, cidx, citems, 1, na)):
+            if items:
+                out = buf[start:start + items]
+                check(lib.cmve_pairwise_item_scores(h, _ptr(a), _dtype_code(a), _pw_ld(a), na, _ptr(b), _dtype_code(b),
+                                                    _pw_ld(b), nb, a.shape[1], _lib.PW_L2, float(alpha), float(beta),
+                                                    _lib.CMVE_F64, _ptr(off), _ptr(idx), off.numel() - 1, items, col_dir,
+                                                    0, _ptr(out)), "cmve_pairwise_item_scores")
+                # an index outside the other side scores NaN here (the sharded entry gives it the all-zero word)
+                out.masked_fill_((idx[:items] < 0) | (idx[:items] >= n_other), float("nan"))
+            start += items
+        rsc, csc, stats = buf[:ritems], buf[ritems:ritems + citems], buf[ritems + citems:]
+        pairs = na * nb
+        cap = max(1, min(pairs // 8, max(1 << 16, pairs // 128)))
+        for attempt in range(2):
+            nbytes = l2_count_workspace(ra, rb, cap)
+            ws = torch.empty(max(nbytes // 8, 1), dtype=torch.int64, device=dev)
+            check(lib.cmve_l2_count(h, C.byref(ra.desc), C.byref(rb.desc), float(alpha), float(beta),
+                                    _ptr(roff), _ptr(rsc) if ritems else None, ritems, nb, _ptr(rpos),
+                                    _ptr(coff), _ptr(csc) if citems else None, citems, na, _ptr(cpos),
+                                    _ptr(ws), nbytes, _ptr(stats)), "cmve_l2_count")
+            host = buf.cpu().numpy()
+            decided, band, rescored, overflow = (int(v) for v in host[ritems + citems:].view(np.int64))
+            self.filter_stats = {"decided": decided, "band": band, "rescored": rescored, "overflow": overflow,
+                                 "redone": attempt > 0, "fallback": False}
+            if not overflow:
+                return host[:ritems + citems]
+            if attempt or band * 8 > pairs:
+                break
+            cap = band  # the positions are zeroed again by the call itself
+        self.filter_stats["fallback"] = True
+        return None
+
+    def _collect(self, sides, sc):
         self.pos, self.nan = [], []
         start = 0
         for (_, _, items, pos) in sides:
@@ -397,24 +476,27 @@ class _PairwisePositions:
         return ranks
 
 
-def pairwise_gt_positions(a, b, metric: int, alpha: float, beta: float, score_dtype, row_lists=None, col_lists=None):
+def pairwise_gt_positions(a, b, metric: int, alpha: float, beta: float, score_dtype, row_lists=None, col_lists=None,
+                          filter=None):
     """(row_positions, col_positions): 1-based positions of every listed item under a non-cosine measure, as
     ``metrics.gt_positions`` gives them on ``pairwise(a, b, ...)`` and on its transpose -- without the matrix (K18).
     row_lists[i]: rows of b listed for row i of a; col_lists[j]: rows of a listed for row j of b."""
-    r = _PairwisePositions(a, b, metric, alpha, beta, score_dtype, row_lists, col_lists)
+    r = _PairwisePositions(a, b, metric, alpha, beta, score_dtype, row_lists, col_lists, filter)
     return r.positions(0), r.positions(1)
 
 
-def pairwise_gt_ranks(a, b, metric: int, alpha: float, beta: float, score_dtype, row_lists=None, col_lists=None):
+def pairwise_gt_ranks(a, b, metric: int, alpha: float, beta: float, score_dtype, row_lists=None, col_lists=None,
+                      filter=None):
     """(row_ranks, col_ranks) == ``rank_from_matrix`` on ``pairwise(a, b, ...)`` in both orientations (K18)."""
-    r = _PairwisePositions(a, b, metric, alpha, beta, score_dtype, row_lists, col_lists)
+    r = _PairwisePositions(a, b, metric, alpha, beta, score_dtype, row_lists, col_lists, filter)
     return r.ranks(0), r.ranks(1)
 
 
-def pairwise_gt_eval(a, b, metric: int, alpha: float, beta: float, score_dtype, row_lists=None, col_lists=None):
+def pairwise_gt_eval(a, b, metric: int, alpha: float, beta: float, score_dtype, row_lists=None, col_lists=None,
+                     filter=None):
     """((row_positions, row_ranks), (col_positions, col_ranks)) from ONE ``cmve_pairwise_positions`` call: what
     cal_perf needs (both directions' ranks and every mAP position)."""
-    r = _PairwisePositions(a, b, metric, alpha, beta, score_dtype, row_lists, col_lists)
+    r = _PairwisePositions(a, b, metric, alpha, beta, score_dtype, row_lists, col_lists, filter)
     return (r.positions(0), r.ranks(0)), (r.positions(1), r.ranks(1))
 
 

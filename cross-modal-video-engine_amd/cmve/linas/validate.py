@@ -76,16 +76,17 @@ def cal_perf(t2v_all_errors, v2t_gt, t2v_gt, tb_logger=None, model=None):
             (t2v_r1, t2v_r5, t2v_r10, t2v_medr, t2v_meanr, t2v_map_score))
 
 
-def cal_perf_embeddings(video_embs, cap_embs, video_ids, caption_ids, measure='cosine'):
+def cal_perf_embeddings(video_embs, cap_embs, video_ids, caption_ids, measure='cosine', filter=None):
     """tester.py:133-139 in one call: get_gt -> fused two-direction rank -> cal_perf tuples,
     without materialising the N_c x N_v error matrix on host.  A non-cosine ``measure`` (the cdist branches and
-    jaccard of evaluation.py:22-35) never forms the matrix at all, on the device or the host (K18)."""
+    jaccard of evaluation.py:22-35) never forms the matrix at all, on the device or the host (K18); ``filter`` is
+    ``metrics.measure_eval``'s (auto: the Euclidean measures count at the MFMA rate on large sets, K19)."""
     v2t_gt, t2v_gt = metrics.get_gt(video_ids, caption_ids)
     if measure != 'cosine':
         from .evaluation import measure_rows
         caps, vids = measure_rows(cap_embs, measure), measure_rows(video_embs, measure)
         t2v_lists = metrics._lists(t2v_gt, caps.shape[0])
-        (t2v_pos, t2v_ranks), (v2t_pos, v2t_ranks) = metrics.measure_eval(caps, vids, measure, t2v_lists, v2t_gt)
+        (t2v_pos, t2v_ranks), (v2t_pos, v2t_ranks) = metrics.measure_eval(caps, vids, measure, t2v_lists, v2t_gt, filter)
         t2v_map, v2t_map = metrics.maps_from_positions(t2v_pos, v2t_pos)
         return (metrics.metrics_from_ranks(v2t_ranks.astype(np.int32)) + (v2t_map,),
                 metrics.metrics_from_ranks(t2v_ranks.astype(np.int32)) + (t2v_map,))

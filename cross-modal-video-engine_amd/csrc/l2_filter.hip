@@ -1,0 +1,539 @@
+// K19: the count pass of K18 under the Euclidean measures (euclidean / l2 / l2_norm: CMVE_PW_L2, fp64 score words)
+// at the MFMA rate -- what
+//   LINAS-engine/evaluation.py:22-35 + util/metrics.py:61-157   cal_error(measure) -> eval_q2m's argsort loop /
+//                                                               t2v_map / v2t_map
+// decide per pair.  ||a - b||^2 = ||a||^2 + ||b||^2 - 2 ||a|| ||b|| cos(a, b): the cosine comes from an fp16
+// v_mfma_f32_16x16x32_f16 GEMM over the packed unit-vector planes (h16), its error from the rows' err_h16 and the
+// accumulation model of DESIGN s4, and every comparison  e(i, j) < item score  whose two sides are further apart
+// than that error (and than every rounding of the canonical chain, DESIGN s4 "K19") is decided from the MFMA
+// value.  The pairs that are not -- the band -- are appended to a caller-owned list and re-scored by the second
+// kernel on the canonical chain of pairwise_tile.h (one accumulator, k ascending, from zero), so the counts are,
+// word for word, cmve_pairwise_count's.
+//   l2f_main_kernel   128 x 128 tile, 4 waves of 64 x 64, 64-deep K-tiles double-buffered in LDS (register staged,
+//                     XOR-swizzled 16-B chunks); fp64 epilogue: interval test against each item, band append, counts
+//                     (shuffle / LDS partial sums, one integer atomic per (item, tile): bit-reproducible)
+//   l2f_fixup_kernel  a wave takes 64 band pairs: the (a - b) chunks go through LDS transposed (coalesced loads), each
+//                     lane runs its own pair's chain
+//   l2f_nan_kernel    the NaN items' words (cmve_pairwise_count's rule with the caller's n)
+#include "pairwise_tile.h"
+
+namespace cmve {
+namespace {
+
+typedef _Float16 l2f_f16x8 __attribute__((ext_vector_type(8)));
+typedef float l2f_f32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t l2f_u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned long long l2f_u64;
+
+constexpr int L2F_BM = 128, L2F_BN = 128, L2F_BK = 64;
+constexpr int L2F_GM = 16;  // A tiles per group of the block order: 16 x 32 tiles in flight share 48 tiles of rows
+constexpr int L2F_A_BYTES = L2F_BM * L2F_BK * 2, L2F_STAGE = (L2F_BM + L2F_BN) * L2F_BK * 2;
+constexpr double L2F_U = 1.1102230246251565e-16;  // 2^-53
+
+struct L2fArgs {
+  const uint16_t* a16;  // [na_pad, d_pad] fp16 unit rows
+  const uint16_t* b16;
+  const double* a_inv;  // 1 / ||row||
+  const double* b_inv;
+  const float* a_err;   // >= || x_hat - h16 ||
+  const float* b_err;
+  int64_t na, nb, d_pad;
+  double alpha, beta;
+  double gamma;  // the MFMA accumulation term of score_error_bound (DESIGN s4)
+  double theta;  // >= || fl(x * inv_norm) - x / ||x|| ||: the pack's x_hat against the true unit vector
+  double kappa;  // relative slack on ||a||^2 + ||b||^2: the norms' roundings and the epilogue's own fp64 arithmetic
+  double rho;    // relative slack of the canonical chain in distance space
+  const int64_t* row_off;
+  const double* row_sc;
+  int32_t* row_pos;
+  const int64_t* col_off;
+  const double* col_sc;
+  int32_t* col_pos;
+  int2* band;
+  int64_t cap;
+  l2f_u64* stats;  // {decided, band found, band re-scored, overflow}
+  int tiles_a, tiles_b;
+};
+
+// the epilogue's LDS, laid over the staging buffers once the K loop is done
+struct L2fEpi {
+  double an[L2F_BM], ae[L2F_BM], bn[L2F_BN], be[L2F_BN];      // norms and row errors of the tile's rows / columns
+  double rtb[L2F_BM], rtn[L2F_BM], ctb[L2F_BN], ctn[L2F_BN];  // one round's thresholds (below / not-below)
+  int64_t ro[L2F_BM], co[L2F_BN];
+  int mr[L2F_BM], mc[L2F_BN];
+  int rc[L2F_BM], cc[L2F_BN];
+  int s_m[2];
+  int band_cnt;
+  long long band_base;
+};
+static_assert(sizeof(L2fEpi) <= 2 * L2F_STAGE, "the epilogue's LDS fits the staging buffers");
+
+// The item word t mapped back to squared-distance space (DESIGN s4, K19).  A pair of true squared distance D has
+// e(i, j) < t whenever   alpha > 0: D < tb,   alpha < 0: D > tb   and  e(i, j) >= t  whenever  alpha > 0: D > tn,
+// alpha < 0: D < tn.  x = (t - beta) / alpha is the distance at which the real-number score equals t; sig covers the
+// roundings of x itself and of the chain's alpha * x + beta (contracted or not); rho those of the sum, the
+// subtractions and the square root.  A NaN item is never counted: every pair with a finite interval is not-below.
+__device__ __forceinline__ void l2f_thresholds(double t, double alpha, double beta, double rho, double& tb,
+                                               double& tn) {
+  const bool pos = alpha > 0.0;
+  const double inf = __builtin_huge_val();
+  const double none = pos ? -inf : inf;  // tb = tn = none: no pair is below, every finite one is not-below
+  if (t != t) { tb = none; tn = none; return; }
+  if (fabs(t) == inf) {  // a finite pair (the epilogue's overflow guard) is below +inf and not below -inf
+    tb = tn = (t > 0.0) ? -none : none;
+    return;
+  }
+  const double x = (t - beta) / alpha;
+  const double sig = 16.0 * L2F_U * ((fabs(t) + fabs(beta)) / fabs(alpha)) + 1e-290;
+  const double xlo = x - sig, xhi = x + sig;
+  const double l = xlo * (1.0 - rho), h = xhi * (1.0 + 2.0 * rho);
+  const double lo_t = xlo > 0.0 ? (l * l) * (1.0 - 4.0 * L2F_U) : -inf;  // D below it: the distance is below x
+  const double hi_t = xhi > 0.0 ? (h * h) * (1.0 + 4.0 * L2F_U) : 0.0;   // D above it: the distance is above x
+  tb = pos ? lo_t : hi_t;
+  tn = pos ? hi_t : lo_t;
+}
+
+// [dlo, dhi] holds the true squared distance of the pair (NaN, NaN when no such statement can be made)
+__device__ __forceinline__ void l2f_interval(float c, double na_, double ea, double nb_, double eb, double gamma,
+                                             double kappa, double& dlo, double& dhi) {
+  const double sa = na_ * na_, sb = nb_ * nb_, ss = sa + sb, p = 2.0 * na_ * nb_;
+  const double E = ea + (1.0 + ea) * eb + gamma * ((1.0 + ea) * (1.0 + eb)) + 1e-12;
+  const double W = (p * E + ss * kappa) * (1.0 + 1e-9) + 1e-280;
+  const double d2 = ss - p * (double)c;
+  const bool ok = ss < 1e300;  // no overflow anywhere in the canonical chain; false for NaN
+  dlo = ok ? d2 - W : (double)NAN;
+  dhi = ok ? d2 + W : (double)NAN;
+}
+
+__device__ __forceinline__ uint32_t l2f_lds_off(int r, int chunk) {
+  return (uint32_t)(r * (L2F_BK * 2) + ((chunk ^ (r & 7)) << 4));
+}
+
+__global__ __launch_bounds__(256, 2) void l2f_main_kernel(L2fArgs a) {
+  __shared__ __attribute__((aligned(16))) char smem[2 * L2F_STAGE];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1;
+  // block order: groups of L2F_GM A tiles, inside a group the A tile runs fastest
+  int ta, tb_;
+  {
+    const int64_t L = blockIdx.x, per = (int64_t)L2F_GM * a.tiles_b;
+    const int g = (int)(L / per);
+    const int64_t in = L - (int64_t)g * per;
+    const int gs = min(L2F_GM, a.tiles_a - g * L2F_GM);
+    ta = g * L2F_GM + (int)(in % gs);
+    tb_ = (int)(in / gs);
+  }
+  const int64_t i0 = (int64_t)ta * L2F_BM, j0 = (int64_t)tb_ * L2F_BN;
+
+  // ---- the GEMM: c[tm][tn] = 16 x 16 blocks of the wave's 64 x 64 -------------------------------------------------
+  l2f_f32x4 acc[4][4];
+#pragma unroll
+  for (int m = 0; m < 4; ++m)
+#pragma unroll
+    for (int n = 0; n < 4; ++n) acc[m][n] = l2f_f32x4{0.f, 0.f, 0.f, 0.f};
+  const int sc_ = tid & 7, sr = tid >> 3;  // staging: chunk sc_ of rows sr + 32 it
+  const uint16_t* ga = a.a16 + (i0 + sr) * a.d_pad + sc_ * 8;  // rows below n_pad (a multiple of 256): in bounds
+  const uint16_t* gb = a.b16 + (j0 + sr) * a.d_pad + sc_ * 8;
+  const uint32_t soff = l2f_lds_off(sr, sc_);  // (sr + 32 it) & 7 == sr & 7
+  l2f_u32x4 ra[4], rb[4];
+  const int nk = (int)(a.d_pad / L2F_BK);
+#define L2F_LOAD(kt)                                                                     \
+  _Pragma("unroll") for (int it = 0; it < 4; ++it) {                                     \
+    ra[it] = *(const l2f_u32x4*)(ga + (int64_t)(32 * it) * a.d_pad + (kt) * L2F_BK);     \
+    rb[it] = *(const l2f_u32x4*)(gb + (int64_t)(32 * it) * a.d_pad + (kt) * L2F_BK);     \
+  }
+#define L2F_WRITE(buf)                                                                   \
+  _Pragma("unroll") for (int it = 0; it < 4; ++it) {                                     \
+    *(l2f_u32x4*)(smem + (buf) * L2F_STAGE + soff + it * 32 * (L2F_BK * 2)) = ra[it];    \
+    *(l2f_u32x4*)(smem + (buf) * L2F_STAGE + L2F_A_BYTES + soff + it * 32 * (L2F_BK * 2)) = rb[it]; \
+  }
+  L2F_LOAD(0)
+  L2F_WRITE(0)
+  __syncthreads();
+  const int fr = lane & 15, fq = lane >> 4;
+  for (int kt = 0; kt < nk; ++kt) {
+    const int buf = kt & 1;
+    if (kt + 1 < nk) { L2F_LOAD(kt + 1) }
+    const char* pa = smem + buf * L2F_STAGE;
+    const char* pb = pa + L2F_A_BYTES;
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      l2f_f16x8 fa[4], fb[4];
+#pragma unroll
+      for (int m = 0; m < 4; ++m) fa[m] = *(const l2f_f16x8*)(pa + l2f_lds_off(wm * 64 + m * 16 + fr, ks * 4 + fq));
+#pragma unroll
+      for (int n = 0; n < 4; ++n) fb[n] = *(const l2f_f16x8*)(pb + l2f_lds_off(wn * 64 + n * 16 + fr, ks * 4 + fq));
+#pragma unroll
+      for (int m = 0; m < 4; ++m)
+#pragma unroll
+        for (int n = 0; n < 4; ++n)
+          acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fa[m], fb[n], acc[m][n], 0, 0, 0);
+    }
+    if (kt + 1 < nk) { L2F_WRITE(buf ^ 1) }
+    __syncthreads();
+  }
+#undef L2F_LOAD
+#undef L2F_WRITE
+
+  // ---- epilogue ------------------------------------------------------------------------------------------------------
+  // acc[m][n][r] is the pair (A row wm 64 + 16 m + 4 fq + r, B row wn 64 + 16 n + fr) of the tile
+  L2fEpi& E = *(L2fEpi*)smem;
+  if (tid < 2) E.s_m[tid] = 0;
+  if (tid == 2) E.band_cnt = 0;
+  __syncthreads();
+  if (tid < L2F_BM) {
+    const int64_t i = i0 + tid;
+    const bool v = i < a.na;
+    E.an[tid] = v ? 1.0 / a.a_inv[i] : (double)NAN;
+    E.ae[tid] = v ? (double)a.a_err[i] + a.theta : (double)NAN;
+    const int64_t o = (v && a.row_pos) ? a.row_off[i] : 0;
+    const int m = (v && a.row_pos) ? (int)(a.row_off[i + 1] - o) : 0;
+    E.ro[tid] = o;
+    E.mr[tid] = m;
+    E.rc[tid] = 0;
+    if (m) atomicMax(&E.s_m[0], m);
+  } else {
+    const int t = tid - L2F_BM;
+    const int64_t j = j0 + t;
+    const bool v = j < a.nb;
+    E.bn[t] = v ? 1.0 / a.b_inv[j] : (double)NAN;
+    E.be[t] = v ? (double)a.b_err[j] + a.theta : (double)NAN;
+    const int64_t o = (v && a.col_pos) ? a.col_off[j] : 0;
+    const int m = (v && a.col_pos) ? (int)(a.col_off[j + 1] - o) : 0;
+    E.co[t] = o;
+    E.mc[t] = m;
+    E.cc[t] = 0;
+    if (m) atomicMax(&E.s_m[1], m);
+  }
+  __syncthreads();
+  const int rounds = max(E.s_m[0], E.s_m[1]);  // block-uniform
+  const int rbase = wm * 64 + 4 * fq, cbase = wn * 64 + fr;
+  // bit (m * 4 + r) * 4 + n of `valid`: the pair exists
+  uint64_t valid = 0, band = 0;
+#pragma unroll
+  for (int m = 0; m < 4; ++m)
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+      for (int n = 0; n < 4; ++n)
+        if (i0 + rbase + 16 * m + r < a.na && j0 + cbase + 16 * n < a.nb) valid |= 1ull << ((m * 4 + r) * 4 + n);
+
+  // one round: item `it` of every row and column list.  PASS 0 marks the pairs some item cannot decide, PASS 1
+  // counts the decided ones.
+  for (int pass = 0; pass < 2; ++pass) {
+    for (int it = 0; it < rounds; ++it) {
+      if (tid < L2F_BM) {
+        double tb = (double)NAN, tn = (double)NAN;
+        const bool has = it < E.mr[tid];
+        if (has) l2f_thresholds(a.row_sc[E.ro[tid] + it], a.alpha, a.beta, a.rho, tb, tn);
+        E.rtb[tid] = tb;
+        E.rtn[tid] = tn;
+      } else {
+        const int t = tid - L2F_BM;
+        double tb = (double)NAN, tn = (double)NAN;
+        const bool has = it < E.mc[t];
+        if (has) l2f_thresholds(a.col_sc[E.co[t] + it], a.alpha, a.beta, a.rho, tb, tn);
+        E.ctb[t] = tb;
+        E.ctn[t] = tn;
+      }
+      __syncthreads();
+      const bool pos = a.alpha > 0.0;
+      int ccnt[4] = {0, 0, 0, 0};
+#pragma unroll
+      for (int m = 0; m < 4; ++m) {
+        int rpack = 0;  // the four rows' counts, a byte each (<= 4 per thread, <= 64 over the row's 16 lanes)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int row = rbase + 16 * m + r;
+          const double an = E.an[row], ae = E.ae[row], rtb = E.rtb[row], rtn = E.rtn[row];
+          const bool rhas = it < E.mr[row];
+#pragma unroll
+          for (int n = 0; n < 4; ++n) {
+            const int col = cbase + 16 * n;
+            const int bit = (m * 4 + r) * 4 + n;
+            double dlo, dhi;
+            l2f_interval(acc[m][n][r], an, ae, E.bn[col], E.be[col], a.gamma, a.kappa, dlo, dhi);
+            const bool chas = it < E.mc[col];
+            const double ctb = E.ctb[col], ctn = E.ctn[col];
+            const bool rb = pos ? dhi < rtb : dlo > rtb, rn = pos ? dlo > rtn : dhi < rtn;
+            const bool cb = pos ? dhi < ctb : dlo > ctb, cn = pos ? dlo > ctn : dhi < ctn;
+            if (pass == 0) {
+              // also a pair with no item to compare against must have an interval, so that decided + band = pairs
+              const bool okr = rhas ? (rb || rn) : (dlo == dlo);
+              const bool okc = chas ? (cb || cn) : (dlo == dlo);
+              if (!(okr && okc)) band |= 1ull << bit;
+            } else {
+              const bool live = ((valid & ~band) >> bit) & 1;
+              rpack += (live && rhas && rb) ? (1 << (8 * r)) : 0;
+              ccnt[n] += (live && chas && cb) ? 1 : 0;
+            }
+          }
+        }
+        if (pass == 1) {  // rows: the 16 lanes fr = 0..15 of this wave share them
+          rpack += __shfl_xor(rpack, 1, 64);
+          rpack += __shfl_xor(rpack, 2, 64);
+          rpack += __shfl_xor(rpack, 4, 64);
+          rpack += __shfl_xor(rpack, 8, 64);
+          if (fr == 0 && rpack) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const int c = (rpack >> (8 * r)) & 255;
+              if (c) atomicAdd(&E.rc[rbase + 16 * m + r], c);
+            }
+          }
+        }
+      }
+      if (pass == 1) {  // columns: the 4 lane groups fq = 0..3 share them (<= 16 per thread, <= 64 per wave)
+        int cpack = ccnt[0] | (ccnt[1] << 8) | (ccnt[2] << 16) | (ccnt[3] << 24);
+        cpack += __shfl_xor(cpack, 16, 64);
+        cpack += __shfl_xor(cpack, 32, 64);
+        if (fq == 0 && cpack) {
+#pragma unroll
+          for (int n = 0; n < 4; ++n) {
+            const int c = (cpack >> (8 * n)) & 255;
+            if (c) atomicAdd(&E.cc[cbase + 16 * n], c);
+          }
+        }
+      }
+      __syncthreads();
+      if (pass == 1) {  // one integer atomic per (item, tile)
+        if (tid < L2F_BM) {
+          const int c = E.rc[tid];
+          if (c && it < E.mr[tid]) gadd(a.row_pos + E.ro[tid] + it, (int32_t)c);
+          E.rc[tid] = 0;
+        } else {
+          const int t = tid - L2F_BM;
+          const int c = E.cc[t];
+          if (c && it < E.mc[t]) gadd(a.col_pos + E.co[t] + it, (int32_t)c);
+          E.cc[t] = 0;
+        }
+        // (the next round's threshold writes and this read touch different words; its barrier orders the counters)
+      }
+    }
+    if (pass == 0) {
+      if (rounds == 0) {  // no list in this tile: nothing to decide, but the pairs without an interval are band
+#pragma unroll
+        for (int m = 0; m < 4; ++m)
+#pragma unroll
+          for (int r = 0; r < 4; ++r)
+#pragma unroll
+            for (int n = 0; n < 4; ++n) {
+              const int row = rbase + 16 * m + r, col = cbase + 16 * n;
+              double dlo, dhi;
+              l2f_interval(acc[m][n][r], E.an[row], E.ae[row], E.bn[col], E.be[col], a.gamma, a.kappa, dlo, dhi);
+              if (!(dlo == dlo)) band |= 1ull << ((m * 4 + r) * 4 + n);
+            }
+      }
+      // the band pairs, once each, into the caller's list
+      band &= valid;
+      const int nband = __popcll(band);
+      int my = 0;
+      if (nband) my = atomicAdd(&E.band_cnt, nband);
+      __syncthreads();
+      if (tid == 0) {
+        const int total = E.band_cnt;
+        const int nv = (int)(min<int64_t>(L2F_BM, a.na - i0) * min<int64_t>(L2F_BN, a.nb - j0));
+        long long base = 0;
+        if (total) {
+          base = (long long)gadd(a.stats + 1, (l2f_u64)total);
+          if (base + total > a.cap) gmax(a.stats + 3, (l2f_u64)1);
+        }
+        if (nv - total) gadd(a.stats + 0, (l2f_u64)(nv - total));
+        E.band_base = base;
+      }
+      __syncthreads();
+      if (nband) {
+        long long p = E.band_base + my;
+        uint64_t b = band;
+        while (b) {
+          const int bit = __ffsll((long long)b) - 1;
+          b &= b - 1;
+          const int n = bit & 3, r = (bit >> 2) & 3, m = bit >> 4;
+          if (p < a.cap) a.band[p] = make_int2((int)(i0 + rbase + 16 * m + r), (int)(j0 + cbase + 16 * n));
+          ++p;
+        }
+      }
+    }
+  }
+}
+
+// ---- the band pairs on the canonical chain -----------------------------------------------------------------------------
+template <typename TA, typename TB>
+__global__ __launch_bounds__(256) void l2f_fixup_kernel(const TA* __restrict__ A, int64_t lda,
+                                                        const TB* __restrict__ B, int64_t ldb, int64_t d, double alpha,
+                                                        double beta, const int64_t* __restrict__ row_off,
+                                                        const double* __restrict__ row_sc, int32_t* __restrict__ row_pos,
+                                                        const int64_t* __restrict__ col_off,
+                                                        const double* __restrict__ col_sc, int32_t* __restrict__ col_pos,
+                                                        const int2* __restrict__ band, int64_t cap,
+                                                        l2f_u64* __restrict__ stats) {
+  constexpr int KC = 16;
+  __shared__ double sd[4][64][KC + 1];  // [wave][pair][k]: lane p reads row p (17-double stride: conflict-free)
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int64_t n = (int64_t)stats[1];
+  if (n > cap) return;  // the list overflowed: the caller redoes the call with the reported need
+  for (int64_t b0 = (int64_t)blockIdx.x * 256; b0 < n; b0 += (int64_t)gridDim.x * 256) {  // block-uniform
+    const int64_t p = b0 + w * 64 + lane;
+    const bool live = p < n;
+    const int2 ij = band[live ? p : b0];  // an idle lane repeats a pair of the list: its loads stay in bounds
+    double s = 0.0, unused = 0.0;
+    for (int64_t k0 = 0; k0 < d; k0 += KC) {
+#pragma unroll 4
+      for (int it = 0; it < 16; ++it) {
+        const int q = it * 4 + (lane >> 4), k = lane & 15;
+        const int64_t qi = __shfl(ij.x, q, 64), qj = __shfl(ij.y, q, 64);
+        double df = 0.0;
+        if (k0 + k < d) df = (double)A[qi * lda + k0 + k] - (double)B[qj * ldb + k0 + k];
+        sd[w][q][k] = df;
+      }
+      __syncthreads();
+      const int kn = (int)min<int64_t>(KC, d - k0);
+      // the subtraction was done above (exact fp64 either way): pw_acc's own  t - 0  leaves it as it is
+      for (int k = 0; k < kn; ++k) pw_acc<CMVE_PW_L2>(sd[w][lane][k], 0.0, s, unused);
+      __syncthreads();
+    }
+    const double e = pw_score<CMVE_PW_L2>(s, 0.0, alpha, beta);
+    if (live) {
+      if (row_pos) {
+        const int64_t o = row_off[ij.x], m = row_off[ij.x + 1];
+        for (int64_t q = o; q < m; ++q)
+          if (e < row_sc[q]) gadd(row_pos + q, (int32_t)1);
+      }
+      if (col_pos) {
+        const int64_t o = col_off[ij.y], m = col_off[ij.y + 1];
+        for (int64_t q = o; q < m; ++q)
+          if (e < col_sc[q]) gadd(col_pos + q, (int32_t)1);
+      }
+    }
+    const int nl = (int)min<int64_t>(64, max<int64_t>(0, n - (b0 + w * 64)));
+    if (lane == 0 && nl) gadd(stats + 2, (l2f_u64)nl);
+  }
+}
+
+// ---- NaN items: n - (NaN items of the list) + (the item's place among them), in list order -----------------------------
+__global__ __launch_bounds__(256) void l2f_nan_kernel(const int64_t* __restrict__ off, const double* __restrict__ sc,
+                                                      int64_t n_lists, int64_t n, int32_t* __restrict__ pos) {
+  const int64_t l = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (l >= n_lists) return;
+  const int64_t lo = off[l], hi = off[l + 1];
+  int64_t n_nan = 0, run = 0;
+  for (int64_t p = lo; p < hi; ++p) {
+    const double t = sc[p];
+    n_nan += (t != t);
+  }
+  for (int64_t p = lo; p < hi && n_nan; ++p) {
+    const double t = sc[p];
+    if (t != t) pos[p] = (int32_t)(n - n_nan + run++);
+  }
+}
+
+}  // namespace
+}  // namespace cmve
+
+using namespace cmve;
+
+extern "C" int cmve_l2_count_workspace(const cmve_rows_t* a, const cmve_rows_t* b, int64_t band_cap, int64_t* bytes) {
+  CMVE_REQUIRE(a && b && bytes, "cmve_l2_count_workspace: NULL argument");
+  CMVE_REQUIRE(band_cap >= 0 && band_cap <= INT64_MAX / 8, "cmve_l2_count_workspace: bad band capacity (%lld)",
+               (long long)band_cap);
+  CMVE_REQUIRE(a->n >= 0 && b->n >= 0 && a->d > 0 && a->d == b->d,
+               "cmve_l2_count_workspace: bad shape (%lld x %lld, %lld x %lld)", (long long)a->n, (long long)a->d,
+               (long long)b->n, (long long)b->d);
+  *bytes = band_cap * (int64_t)sizeof(int2);  // the band list and nothing else: (i, j) per slot
+  return CMVE_OK;
+}
+
+extern "C" int cmve_l2_count(cmve_handle_t h, const cmve_rows_t* a, const cmve_rows_t* b, double alpha, double beta,
+                             const int64_t* row_off, const double* row_sc, int64_t row_items, int64_t row_n,
+                             int32_t* row_pos, const int64_t* col_off, const double* col_sc, int64_t col_items,
+                             int64_t col_n, int32_t* col_pos, void* ws, int64_t ws_bytes, int64_t* stats) {
+  CMVE_REQUIRE(h && a && b && stats, "cmve_l2_count: NULL argument");
+  CMVE_REQUIRE(alpha != 0.0 && std::isfinite(alpha) && std::isfinite(beta),
+               "cmve_l2_count: alpha must be finite and non-zero, beta finite (%g, %g)", alpha, beta);
+  CMVE_REQUIRE(a->d > 0 && a->d == b->d && a->d_pad == b->d_pad, "cmve_l2_count: dimensions differ (%lld, %lld)",
+               (long long)a->d, (long long)b->d);
+  CMVE_REQUIRE(a->h16 && b->h16 && a->err_h16 && b->err_h16, "cmve_l2_count: a set was packed without its fp16 plane");
+  CMVE_REQUIRE(a->eps == 0.0 && b->eps == 0.0, "cmve_l2_count: the sets must be packed with eps = 0");
+  CMVE_REQUIRE(!(a->flags & CMVE_PACK_RAW) && !(b->flags & CMVE_PACK_RAW),
+               "cmve_l2_count: CMVE_PACK_RAW sets hold no unit rows");
+  const int64_t na = a->n, nb = b->n, d = a->d;
+  CMVE_REQUIRE(na >= 0 && nb >= 0 && na < (1ll << 31) && nb < (1ll << 31) && a->n_pad >= na && b->n_pad >= nb &&
+                   a->n_pad % CMVE_ROW_ALIGN == 0 && b->n_pad % CMVE_ROW_ALIGN == 0 && a->d_pad >= d &&
+                   a->d_pad % CMVE_DIM_ALIGN == 0,
+               "cmve_l2_count: bad shape");
+  CMVE_REQUIRE((a->raw || !na) && (b->raw || !nb) && a->inv_norm && b->inv_norm && a->raw_ld >= d && b->raw_ld >= d,
+               "cmve_l2_count: the sets' raw rows are missing");
+  CMVE_REQUIRE((a->raw_dtype == CMVE_F32 || a->raw_dtype == CMVE_F64) &&
+                   (b->raw_dtype == CMVE_F32 || b->raw_dtype == CMVE_F64),
+               "cmve_l2_count: raw rows must be CMVE_F32/CMVE_F64");
+  if (!row_pos) row_items = 0;
+  if (!col_pos) col_items = 0;
+  CMVE_REQUIRE(row_items >= 0 && col_items >= 0 && row_n >= 0 && col_n >= 0 && row_n < (1ll << 31) &&
+                   col_n < (1ll << 31) && row_items < (1ll << 31) * 256 && col_items < (1ll << 31) * 256,
+               "cmve_l2_count: bad counts (%lld, %lld items; n %lld, %lld)", (long long)row_items,
+               (long long)col_items, (long long)row_n, (long long)col_n);
+  CMVE_REQUIRE(!row_pos || (row_off && (row_sc || !row_items)), "cmve_l2_count: row lists missing");
+  CMVE_REQUIRE(!col_pos || (col_off && (col_sc || !col_items)), "cmve_l2_count: column lists missing");
+  CMVE_REQUIRE(ws_bytes >= 0 && (ws || ws_bytes < 8), "cmve_l2_count: workspace missing");
+  CMVE_REQUIRE((((uintptr_t)ws) & 7) == 0, "cmve_l2_count: workspace must be 8-byte aligned");
+  const int64_t tiles_a = (na + L2F_BM - 1) / L2F_BM, tiles_b = (nb + L2F_BN - 1) / L2F_BN;
+  CMVE_REQUIRE(tiles_a * tiles_b < (1ll << 31), "cmve_l2_count: too many tiles (%lld x %lld)", (long long)tiles_a,
+               (long long)tiles_b);
+  const hipStream_t st = h->stream;
+  CMVE_HIP(hipMemsetAsync(stats, 0, 4 * sizeof(int64_t), st));
+  if (row_items + col_items == 0) return CMVE_OK;
+  if (row_items) CMVE_HIP(hipMemsetAsync(row_pos, 0, sizeof(int32_t) * row_items, st));
+  if (col_items) CMVE_HIP(hipMemsetAsync(col_pos, 0, sizeof(int32_t) * col_items, st));
+  // the NaN items' words are the caller's n, whatever this call's own na / nb
+  if (row_items && row_n && na)
+    hipLaunchKernelGGL(l2f_nan_kernel, dim3((unsigned)((na + 255) / 256)), dim3(256), 0, st, row_off, row_sc, na, row_n,
+                       row_pos);
+  if (col_items && col_n && nb)
+    hipLaunchKernelGGL(l2f_nan_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, col_off, col_sc, nb, col_n,
+                       col_pos);
+  if (na == 0 || nb == 0) return check_launch("l2_count");
+  L2fArgs g;
+  g.a16 = a->h16;
+  g.b16 = b->h16;
+  g.a_inv = a->inv_norm;
+  g.b_inv = b->inv_norm;
+  g.a_err = a->err_h16;
+  g.b_err = b->err_h16;
+  g.na = na;
+  g.nb = nb;
+  g.d_pad = a->d_pad;
+  g.alpha = alpha;
+  g.beta = beta;
+  {  // DESIGN s4 (K19): every constant rounded up generously
+    const double n = (double)a->d_pad * (33.0 / 32.0), u = 1.0 / 8388608.0;
+    g.gamma = n * u / (1.0 - n * u) * (1.0 + 1e-12);
+    g.theta = ((double)d + 20.0) * L2F_U;
+    g.kappa = 16.0 * ((double)d + 32.0) * L2F_U;
+    g.rho = 2.0 * ((double)d + 16.0) * L2F_U;
+  }
+  g.row_off = row_off;
+  g.row_sc = row_sc;
+  g.row_pos = row_items ? row_pos : nullptr;
+  g.col_off = col_off;
+  g.col_sc = col_sc;
+  g.col_pos = col_items ? col_pos : nullptr;
+  g.band = (int2*)ws;
+  g.cap = ws_bytes / (int64_t)sizeof(int2);
+  g.stats = (l2f_u64*)stats;
+  g.tiles_a = (int)tiles_a;
+  g.tiles_b = (int)tiles_b;
+  hipLaunchKernelGGL(l2f_main_kernel, dim3((unsigned)(tiles_a * tiles_b)), dim3(256), 0, st, g);
+  const int fix_blocks = (int)std::max<int64_t>(1, std::min<int64_t>(8 * device_cus(), (g.cap + 255) / 256));
+#define L2F_FIX(TA, TB)                                                                                              \
+  hipLaunchKernelGGL((l2f_fixup_kernel<TA, TB>), dim3((unsigned)fix_blocks), dim3(256), 0, st, (const TA*)a->raw,    \
+                     a->raw_ld, (const TB*)b->raw, b->raw_ld, d, alpha, beta, row_off, row_sc, g.row_pos, col_off,   \
+                     col_sc, g.col_pos, (const int2*)g.band, g.cap, g.stats)
+  if (g.cap > 0) {
+    if (a->raw_dtype == CMVE_F64 && b->raw_dtype == CMVE_F64) L2F_FIX(double, double);
+    else if (a->raw_dtype == CMVE_F64) L2F_FIX(double, float);
+    else if (b->raw_dtype == CMVE_F64) L2F_FIX(float, double);
+    else L2F_FIX(float, float);
+  }
+#undef L2F_FIX
+  return check_launch("l2_count");
+}

@@ -723,6 +723,31 @@ int cmve_pairwise_topk(cmve_handle_t h, const void* Q, int32_t q_dtype, int64_t 
                        int32_t score_dtype, int32_t k, int32_t geometry, void* ws, int64_t ws_bytes, int64_t* out_idx,
                        double* out_err);
 
+/* K19: cmve_pairwise_count for CMVE_PW_L2 with fp64 score words at the MFMA rate (csrc/l2_filter.hip).
+ * Replaces, as its K18 twin does: LINAS-engine/evaluation.py:22-35 (cal_error under euclidean / l2 / l2_norm) +
+ * util/metrics.py:61-157 (t2v_map, v2t_map, eval_q2m's argsort loop).
+ *   a, b: ordinary packed sets (cmve_pack_rows with eps = 0 and the fp16 plane, not CMVE_PACK_RAW) of the captions
+ *   [na, d] and the videos [nb, d]; their raw rows stay the source of every canonical score.  ||a - b||^2 is formed
+ *   from the rows' norms and an fp16 MFMA cosine; a comparison e(i, j) < item score whose sides lie further apart
+ *   than the rigorous error of that value is decided from it, and every other pair -- the band --
+ *   is appended to the list in ws and re-scored on the canonical fp64 chain (csrc/pairwise_tile.h).  row_pos /
+ *   col_pos therefore hold, word for word, what cmve_pairwise_count(metric = CMVE_PW_L2, score_dtype = CMVE_F64)
+ *   gives for the same row_off / row_sc / row_n / col_off / col_sc / col_n (NaN items included, also when na or nb
+ *   is 0); either direction may be NULL.
+ *   ws: cmve_l2_count_workspace(a, b, band_cap) bytes = 8 * band_cap (host only, no launch), 8-byte aligned, need
+ *   not be zeroed; cmve_l2_count takes the capacity from ws_bytes.
+ *   stats: device int64[4] = {pairs decided by the filter, band pairs found, band pairs re-scored, overflow flag}.
+ *   When the band outgrows the list the re-score is skipped, the flag is 1, the positions are NOT valid and
+ *   stats[1] is the whole need: one redo with that capacity suffices.
+ *   Enqueued on the handle's stream; allocates nothing, never synchronises; integer atomics only: two calls give
+ *   the same words.  Refused: alpha 0 or non-finite, beta non-finite, a set without h16, eps != 0, CMVE_PACK_RAW,
+ *   mismatched d. */
+int cmve_l2_count_workspace(const cmve_rows_t* a, const cmve_rows_t* b, int64_t band_cap, int64_t* bytes);
+int cmve_l2_count(cmve_handle_t h, const cmve_rows_t* a, const cmve_rows_t* b, double alpha, double beta,
+                  const int64_t* row_off, const double* row_sc, int64_t row_items, int64_t row_n, int32_t* row_pos,
+                  const int64_t* col_off, const double* col_sc, int64_t col_items, int64_t col_n, int32_t* col_pos,
+                  void* ws, int64_t ws_bytes, int64_t* stats);
+
 /* ---- training step of the projection heads ---------------
  * K11: what LINAS-engine/model.py:984-1004 (train_emb, style 'GT') runs around the GEMMs (K3 forward,
  * cmve_gemm_f32 backward) and the losses (K6/K7).  Device pointers, fp32 rows; statistics in fp64.
