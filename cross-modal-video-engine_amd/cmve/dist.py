@@ -550,6 +550,8 @@ class ShardedGallery:
         self.shard = self._pw_rows(local_embs)  # resident, unnormalised, in the measure's input dtype
         self.device = self.shard.device
         self.n = int(self.shard.shape[0])
+        self._pw_packed = None  # the Euclidean measures: the shard's pack for K20, made by the first top-k
+        self._pw_filter_off = False  # latched by a top-k the filter handed back whole: this shard stays on fp64
 
     def _pw_spec(self):
         from .linas.evaluation import measure_spec
@@ -574,8 +576,20 @@ class ShardedGallery:
         return engine.pairwise_list_ranks(off, sc, pos, n_m)
 
     def _pw_topk(self, q, k: int):
-        """This shard's (local ids int64, errors fp64) [n_q, k] on the device, (error asc, id asc), NaN last."""
-        return engine.pairwise_topk(q, self.shard, *self._pw_spec(), k, to_host=False)
+        """This shard's (local ids int64, errors fp64) [n_q, k] on the device, (error asc, id asc), NaN last.
+        Under a Euclidean measure engine.pairwise_topk may take the K20 filter (auto); what it leaves unresolved is
+        finished on the fp64 route here, on this shard alone: the words are the same and no flag rides a collective."""
+        if self._pw_filter_off:
+            return engine.pairwise_topk(q, self.shard, *self._pw_spec(), k, to_host=False, filter=False)
+        if (self._pw_packed is None and self.measure in ('euclidean', 'l2', 'l2_norm')
+                and engine.l2_topk_auto(q.shape[0], self.n, packed=True)):
+            # packed ONCE, by the first call large enough for the filter; the pack keeps the rows it is given, so
+            # there is no second copy of the shard
+            self._pw_packed = engine.RowSet(self.shard, eps=0.0, with_lo=False, device=self.device)
+        g = self.shard if self._pw_packed is None else self._pw_packed
+        idx, err, st = engine.pairwise_topk(q, g, *self._pw_spec(), k, to_host=False, return_stats=True)
+        self._pw_filter_off = st is not None and st["fallback"]
+        return idx, err
 
     # ---- a non-cosine measure: coordination (every communicator) ----
     def _pw_csr(self, lists, n_other: Optional[int], what: str):

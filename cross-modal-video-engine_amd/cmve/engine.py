@@ -572,24 +572,139 @@ def pairwise_list_ranks(off: torch.Tensor, scores: torch.Tensor, pos: torch.Tens
     return out[:n_lists]
 
 
+L2_TOPK_CAND_MAX = 2048  # cmve_l2_topk's limit on cand_cap, and so on k: what its last launch sorts in LDS
+# the share of unresolved queries above which engine.pairwise_topk answers the whole call on the fp64 route: past it
+# the filter's launches are mostly wasted (rows clustered far from the origin leave EVERY query unresolved)
+L2_TOPK_MAX_UNRESOLVED = 0.25
+# Auto dispatch of the K20 filter (``filter=None``), from tools/l2_topk_bench.py -> profiles/l2_topk.json (top-10,
+# D = 1024, medians of 5 alternating repeats; "wins" = by more than the two spreads together).  Against a gallery that
+# is already packed (a RowSet: GalleryScorer, ShardedGallery) the filter won at every n_q from 1 to 16,384 over 131,072
+# and 1,048,576 rows (0.80 against 0.87 ms at n_q = 1 over 131,072; 7.2 against 148 ms at 1000 over 1,048,576), and over
+# 16,384 rows from 256 queries (0.89 against 1.11 ms) but not at 64 (0.87 against 0.78 ms; below that both routes are
+# launch gaps, 0.59-0.66 ms): a packed gallery takes it from MIN_GALLERY rows or MIN_PAIRS pairs.  A gallery given as
+# plain rows is packed inside the call (0.16 / 0.50 / 3.9 ms at 16,384 / 131,072 / 1,048,576 rows), which the filter
+# earned back from 64 queries over 131,072 rows and 256 over 16,384, not at 16 over 131,072: plain rows take it from
+# MIN_Q queries AND MIN_PAIRS pairs.  Between the measured gallery sizes the pair rule is an interpolation.
+L2_TOPK_FILTER_MIN_Q = 64
+L2_TOPK_FILTER_MIN_PAIRS = 1 << 22
+L2_TOPK_FILTER_MIN_GALLERY = 131072
+
+
+def l2_topk_auto(n_q: int, n_g: int, packed: bool = False) -> bool:
+    """Whether ``pairwise_topk(filter=None)`` takes the K20 filter at this size (given PW_L2 with fp64 words);
+    ``packed``: the gallery is a RowSet already."""
+    if n_q < 1 or n_g < 1:
+        return False
+    if packed:
+        return n_g >= L2_TOPK_FILTER_MIN_GALLERY or n_q * n_g >= L2_TOPK_FILTER_MIN_PAIRS
+    return n_q >= L2_TOPK_FILTER_MIN_Q and n_q * n_g >= L2_TOPK_FILTER_MIN_PAIRS
+
+
+def l2_topk_workspace(q: "RowSet", g: "RowSet", k: int, cand_cap: Optional[int] = None,
+                      sample_rows: Optional[int] = None) -> int:
+    """Bytes of workspace ``cmve_l2_topk`` needs (host only: no launch)."""
+    n = C.c_int64()
+    check(lib.cmve_l2_topk_workspace(C.byref(q.desc), C.byref(g.desc), int(k),
+                                     L2_TOPK_CAND_MAX if cand_cap is None else int(cand_cap),
+                                     int(sample_rows or 0), C.byref(n)), "cmve_l2_topk_workspace")
+    return n.value
+
+
+def l2_topk(q: "RowSet", g: "RowSet", alpha: float, beta: float, k: int, cand_cap: Optional[int] = None,
+            sample_rows: Optional[int] = None, ws: Optional[torch.Tensor] = None):
+    """``cmve_l2_topk`` (K20): (idx int64 [n_q, k], err fp64 [n_q, k]) on the device and the stats dict
+    {excluded, candidates, rescored, unresolved} (one small copy to the host).  An unresolved query has
+    idx[i, 0] == -2 and the rest of its row unwritten.  k must not exceed the gallery.  ws: a caller-held device
+    workspace, used when it holds ``l2_topk_workspace`` bytes (a fresh one otherwise)."""
+    cap = L2_TOPK_CAND_MAX if cand_cap is None else int(cand_cap)
+    nbytes = l2_topk_workspace(q, g, k, cap, sample_rows)
+    dev = g.device
+    if ws is None or ws.numel() * ws.element_size() < nbytes or ws.data_ptr() % 8:
+        ws = torch.empty(max(nbytes // 8, 1), dtype=torch.int64, device=dev)
+    idx = torch.empty((q.n, int(k)), dtype=torch.int64, device=dev)
+    err = torch.empty((q.n, int(k)), dtype=torch.float64, device=dev)
+    st = torch.empty(4, dtype=torch.int64, device=dev)
+    check(lib.cmve_l2_topk(handle(dev), C.byref(q.desc), C.byref(g.desc), float(alpha), float(beta), int(k), cap,
+                           int(sample_rows or 0), _ptr(ws), nbytes, _ptr(idx), _ptr(err), _ptr(st)), "cmve_l2_topk")
+    excluded, found, rescored, unresolved = (int(v) for v in st.cpu().numpy())
+    stats = {"excluded": excluded, "candidates": found, "rescored": rescored, "unresolved": unresolved}
+    return idx, err, stats
+
+
+def _topk_filtered(q, g, alpha, beta, k, cand_cap, sample_rows, ws=None):
+    """The K20 route of ``pairwise_topk``: (idx, err) on the device with the same words as the fp64 route, and the
+    ``topk_stats`` record; idx is None when the whole call has to take the fp64 route."""
+    rq = q if isinstance(q, RowSet) else RowSet(q, with_lo=False, device=g.device)
+    idx, err, stats = l2_topk(rq, g, alpha, beta, k, cand_cap, sample_rows, ws)
+    stats.update(fallback_rows=0, fallback=False)
+    if stats["unresolved"]:
+        if stats["unresolved"] > L2_TOPK_MAX_UNRESOLVED * rq.n:
+            stats.update(fallback_rows=rq.n, fallback=True)
+            return None, None, stats
+        rows = (idx[:, 0] == -2).nonzero().flatten()
+        sub_i, sub_e = pairwise_topk(rq.raw[rows], g.raw, _lib.PW_L2, alpha, beta, torch.float64, k, to_host=False,
+                                     filter=False)
+        idx[rows], err[rows] = sub_i, sub_e
+        stats["fallback_rows"] = int(rows.numel())
+    return idx, err, stats
+
+
 def pairwise_topk(q, g, metric: int, alpha: float, beta: float, score_dtype, k: int, to_host: bool = True,
-                  ws: Optional[torch.Tensor] = None, ws_bytes: Optional[int] = None, geometry: int = 0):
+                  ws: Optional[torch.Tensor] = None, ws_bytes: Optional[int] = None, geometry: int = 0,
+                  filter: Optional[bool] = None, cand_cap: Optional[int] = None, sample_rows: Optional[int] = None,
+                  return_stats: bool = False):
     """The k rows of g with the smallest error per row of q under a non-cosine measure, by (error asc, index asc),
     NaN last -- a stable argsort of ``pairwise(q, g, ...)`` cut at k, without the matrix (K18).  Returns
     (idx int64 [n_q, k], errors fp64 [n_q, k]); k is clamped to the gallery.  ws: a caller-held uint8 device
     workspace (at least the minimum of ``pairwise_topk_workspace``; default: the recommended size); ws_bytes
-    sizes a fresh one."""
-    q, g = _pw_rows(q, "pairwise_topk"), _pw_rows(g, "pairwise_topk")
+    sizes a fresh one.  The K20 route uses ws too when it holds ``l2_topk_workspace`` bytes; a call that then falls
+    back to the fp64 route with a ws below that route's minimum allocates its own.
+
+    ``filter``: False -- the fp64 route (K18); True -- the K20 route for ``PW_L2`` with float64 score words
+    (``cmve_l2_topk``: fp16 MFMA filter, canonical re-score of the candidates: the same words), ValueError for any
+    other measure; None -- the filter when it applies and ``l2_topk_auto`` says it pays (a packed gallery: from
+    ``L2_TOPK_FILTER_MIN_GALLERY`` rows or ``L2_TOPK_FILTER_MIN_PAIRS`` pairs; plain rows: from
+    ``L2_TOPK_FILTER_MIN_Q`` queries and that many pairs).  g (and q) may be a ``RowSet`` packed with eps = 0: a
+    resident gallery is packed once and its ``.raw`` rows are the fp64 route's operand; plain rows are packed per call.  The filter is an
+    accelerator: queries it leaves unresolved are re-run on the fp64 route and scattered back, more than
+    ``L2_TOPK_MAX_UNRESOLVED`` of them (and k > ``L2_TOPK_CAND_MAX``) send the whole call there.  ``cand_cap`` /
+    ``sample_rows``: ``cmve_l2_topk``'s.  ``return_stats``: also return ``topk_stats`` -- {excluded, candidates,
+    rescored, unresolved, fallback_rows, fallback}, or None when the filter was not tried."""
+    g_set = g if isinstance(g, RowSet) else None
+    q_set = q if isinstance(q, RowSet) else None
+    q = q_set.raw if q_set is not None else _pw_rows(q, "pairwise_topk")
+    g = g_set.raw if g_set is not None else _pw_rows(g, "pairwise_topk")
     if q.shape[1] != g.shape[1]:
         raise ValueError(f"pairwise_topk: shapes {tuple(q.shape)} and {tuple(g.shape)} do not match")
     n_q, n_g = q.shape[0], g.shape[0]
+    applies = metric == _lib.PW_L2 and score_dtype == torch.float64
+    if filter and not applies:
+        raise ValueError("pairwise_topk: filter=True needs PW_L2 with float64 score words")
+
+    def result(idx, err, stats):
+        out = (idx.cpu().numpy(), err.cpu().numpy()) if to_host and torch.is_tensor(idx) else (idx, err)
+        return out + (stats,) if return_stats else out
+
     k = int(min(k, n_g))
     if k < 1:
-        return np.zeros((n_q, 0), np.int64), np.zeros((n_q, 0))
+        return result(np.zeros((n_q, 0), np.int64), np.zeros((n_q, 0)), None)
     if k > _lib.TOPK_MAX:
         raise ValueError(f"pairwise_topk: k <= {_lib.TOPK_MAX}")
+    if filter is None:  # auto never hands the entry what it refuses; filter=True does, and the entry says so
+        filter = (applies and l2_topk_auto(n_q, n_g, g_set is not None) and alpha != 0 and np.isfinite(alpha)
+                  and np.isfinite(beta)
+                  and all(s is None or (s.eps == 0.0 and s.has_f16 and not s.desc.flags & _lib.PACK_RAW)
+                          for s in (q_set, g_set)))
+    topk_stats = None
+    if filter and n_q > 0 and k <= L2_TOPK_CAND_MAX:
+        if g_set is None:
+            g_set = RowSet(g, with_lo=False, device=g.device)
+        idx, err, topk_stats = _topk_filtered(q_set if q_set is not None else q, g_set, alpha, beta, k, cand_cap,
+                                              sample_rows, ws)
+        if idx is not None:
+            return result(idx, err, topk_stats)
     lo, rec = pairwise_topk_workspace(n_q, n_g, k, metric)
-    if ws is None:
+    if ws is None or (topk_stats is not None and ws.numel() * ws.element_size() < lo):
         ws = torch.empty(max(rec if ws_bytes is None else int(ws_bytes), 8), dtype=torch.uint8, device=q.device)
     if ws.numel() * ws.element_size() < lo:
         raise ValueError(f"pairwise_topk: workspace of {ws.numel() * ws.element_size()} bytes < minimum {lo}")
@@ -600,9 +715,7 @@ def pairwise_topk(q, g, metric: int, alpha: float, beta: float, score_dtype, k: 
                                  _pw_ld(g), n_g, q.shape[1], metric, float(alpha), float(beta), code, k,
                                  int(geometry), _ptr(ws), ws.numel() * ws.element_size(), _ptr(idx), _ptr(err)),
           "cmve_pairwise_topk")
-    if not to_host:
-        return idx, err
-    return idx.cpu().numpy(), err.cpu().numpy()
+    return result(idx, err, topk_stats)
 
 
 def csr(lists: Sequence[Sequence[int]], device) -> Tuple[torch.Tensor, torch.Tensor]:

@@ -46,15 +46,30 @@ class GalleryScorer:
     ``measure``: 'cosine', or a cdist / jaccard measure of evaluation.py:22-35 -- the gallery then stays resident
     UNNORMALISED in the measure's input dtype (fp64 for the cdist branches, fp32 for jaccard) and every query
     batch is served by the matrix-free exact top-k of K18 (``engine.pairwise_topk``): the ids of
-    ``np.argsort(cal_error(video_embs, cap_emb, measure)[i], kind='stable')[:topK]``."""
+    ``np.argsort(cal_error(video_embs, cap_emb, measure)[i], kind='stable')[:topK]``.
 
-    def __init__(self, video_embs, video_ids=None, with_lo=True, measure='cosine'):
+    Under 'euclidean', 'l2' and 'l2_norm' the gallery is also packed once for the MFMA-filtered top-k of K20
+    (``engine.pairwise_topk(filter=)``: the same ids, the same words): its fp16 and bf16 unit planes stay resident
+    beside the fp64 rows, 2 x 2 bytes per element -- half the fp64 rows' bytes again, plus 20 bytes per row -- and
+    the rows themselves are not copied.  ``filter``: None -- the filter from ``engine.L2_TOPK_FILTER_MIN_GALLERY``
+    gallery rows or ``engine.L2_TOPK_FILTER_MIN_PAIRS`` pairs per call (``engine.l2_topk_auto``); True / False force it / the fp64 route of K18 (False
+    also skips the pack).  The pack's bf16 plane is not read by K20 (the pack kernel always writes it): half of the
+    extra bytes serve the cosine kernels' layout only.  A call that falls back to the fp64 route as a whole turns the
+    automatic filter off for this scorer.  'l1', 'l1_norm' and 'jaccard' have no dot-product form and stay on K18."""
+
+    def __init__(self, video_embs, video_ids=None, with_lo=True, measure='cosine', filter=None):
         self.measure = measure
+        self.filter = filter
         self.video_ids = list(video_ids) if video_ids is not None else None
         self._ws = None
+        self._packed = None
+        self._filter_off = False  # latched by a call the filter handed back whole
         if measure != 'cosine':
             from .evaluation import measure_rows
             self.gallery = measure_rows(video_embs, measure)
+            if measure in ('euclidean', 'l2', 'l2_norm') and filter is not False and self.gallery.shape[0]:
+                self._packed = engine.RowSet(self.gallery, eps=0.0, with_lo=False, device=self.gallery.device)
+                self.gallery = self._packed.raw  # the pack keeps the rows it was given: no second copy
             return
         emb = video_embs if hasattr(video_embs, "data_ptr") else np.asarray(video_embs)
         self.gallery = engine.RowSet(emb, eps=0.0, with_lo=with_lo)
@@ -98,11 +113,25 @@ class GalleryScorer:
         q = measure_rows(cap_embs, self.measure, g.device)
         metric, alpha, beta, _, sc_dt = measure_spec(self.measure, g.shape[1])
         k = min(int(topK), g.shape[0])
-        if 1 <= k <= engine._lib.TOPK_MAX:  # the workspace stays resident between calls, grown when a call needs more
+        # the route this call will take, as engine.pairwise_topk decides it; a gallery whose calls fell back to the
+        # fp64 route as a whole (rows clustered far from the origin) is not asked again under filter=None
+        flt = False
+        if self._packed is not None and q.shape[0] and 1 <= k <= engine.L2_TOPK_CAND_MAX:
+            flt = self.filter is True or (self.filter is None and not self._filter_off
+                                          and engine.l2_topk_auto(q.shape[0], g.shape[0], packed=True))
+        # ONE workspace stays resident between calls, sized for that route only and grown when a call needs more
+        need = 0
+        if flt:
+            q = engine.RowSet(q, eps=0.0, with_lo=False, device=g.device)
+            need = engine.l2_topk_workspace(q, self._packed, k)
+        elif 1 <= k <= engine._lib.TOPK_MAX:
             need = engine.pairwise_topk_workspace(q.shape[0], g.shape[0], k, metric)[1]
-            if self._ws is None or self._ws.numel() < need:
-                self._ws = torch.empty(need, dtype=torch.uint8, device=g.device)
-        idx, _ = engine.pairwise_topk(q, g, metric, alpha, beta, sc_dt, k, ws=self._ws)
+        if need and (self._ws is None or self._ws.numel() < need):
+            self._ws = torch.empty(need, dtype=torch.uint8, device=g.device)
+        idx, _, st = engine.pairwise_topk(q, self._packed if flt else g, metric, alpha, beta, sc_dt, k, ws=self._ws,
+                                          filter=flt, return_stats=True)
+        if st is not None and st["fallback"]:
+            self._filter_off = True
         return idx
 
     def topk_ids(self, cap_emb, topK=10):

@@ -15,20 +15,10 @@
 //   l2f_fixup_kernel  a wave takes 64 band pairs: the (a - b) chunks go through LDS transposed (coalesced loads), each
 //                     lane runs its own pair's chain
 //   l2f_nan_kernel    the NaN items' words (cmve_pairwise_count's rule with the caller's n)
-#include "pairwise_tile.h"
+#include "l2_filter_tile.h"
 
 namespace cmve {
 namespace {
-
-typedef _Float16 l2f_f16x8 __attribute__((ext_vector_type(8)));
-typedef float l2f_f32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t l2f_u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned long long l2f_u64;
-
-constexpr int L2F_BM = 128, L2F_BN = 128, L2F_BK = 64;
-constexpr int L2F_GM = 16;  // A tiles per group of the block order: 16 x 32 tiles in flight share 48 tiles of rows
-constexpr int L2F_A_BYTES = L2F_BM * L2F_BK * 2, L2F_STAGE = (L2F_BM + L2F_BN) * L2F_BK * 2;
-constexpr double L2F_U = 1.1102230246251565e-16;  // 2^-53
 
 struct L2fArgs {
   const uint16_t* a16;  // [na_pad, d_pad] fp16 unit rows
@@ -39,10 +29,7 @@ struct L2fArgs {
   const float* b_err;
   int64_t na, nb, d_pad;
   double alpha, beta;
-  double gamma;  // the MFMA accumulation term of score_error_bound (DESIGN s4)
-  double theta;  // >= || fl(x * inv_norm) - x / ||x|| ||: the pack's x_hat against the true unit vector
-  double kappa;  // relative slack on ||a||^2 + ||b||^2: the norms' roundings and the epilogue's own fp64 arithmetic
-  double rho;    // relative slack of the canonical chain in distance space
+  L2fConsts c;   // gamma, theta, kappa, rho (l2_filter_tile.h)
   const int64_t* row_off;
   const double* row_sc;
   int32_t* row_pos;
@@ -66,114 +53,19 @@ struct L2fEpi {
   int band_cnt;
   long long band_base;
 };
-static_assert(sizeof(L2fEpi) <= 2 * L2F_STAGE, "the epilogue's LDS fits the staging buffers");
-
-// The item word t mapped back to squared-distance space (DESIGN s4, K19).  A pair of true squared distance D has
-// e(i, j) < t whenever   alpha > 0: D < tb,   alpha < 0: D > tb   and  e(i, j) >= t  whenever  alpha > 0: D > tn,
-// alpha < 0: D < tn.  x = (t - beta) / alpha is the distance at which the real-number score equals t; sig covers the
-// roundings of x itself and of the chain's alpha * x + beta (contracted or not); rho those of the sum, the
-// subtractions and the square root.  A NaN item is never counted: every pair with a finite interval is not-below.
-__device__ __forceinline__ void l2f_thresholds(double t, double alpha, double beta, double rho, double& tb,
-                                               double& tn) {
-  const bool pos = alpha > 0.0;
-  const double inf = __builtin_huge_val();
-  const double none = pos ? -inf : inf;  // tb = tn = none: no pair is below, every finite one is not-below
-  if (t != t) { tb = none; tn = none; return; }
-  if (fabs(t) == inf) {  // a finite pair (the epilogue's overflow guard) is below +inf and not below -inf
-    tb = tn = (t > 0.0) ? -none : none;
-    return;
-  }
-  const double x = (t - beta) / alpha;
-  const double sig = 16.0 * L2F_U * ((fabs(t) + fabs(beta)) / fabs(alpha)) + 1e-290;
-  const double xlo = x - sig, xhi = x + sig;
-  const double l = xlo * (1.0 - rho), h = xhi * (1.0 + 2.0 * rho);
-  const double lo_t = xlo > 0.0 ? (l * l) * (1.0 - 4.0 * L2F_U) : -inf;  // D below it: the distance is below x
-  const double hi_t = xhi > 0.0 ? (h * h) * (1.0 + 4.0 * L2F_U) : 0.0;   // D above it: the distance is above x
-  tb = pos ? lo_t : hi_t;
-  tn = pos ? hi_t : lo_t;
-}
-
-// [dlo, dhi] holds the true squared distance of the pair (NaN, NaN when no such statement can be made)
-__device__ __forceinline__ void l2f_interval(float c, double na_, double ea, double nb_, double eb, double gamma,
-                                             double kappa, double& dlo, double& dhi) {
-  const double sa = na_ * na_, sb = nb_ * nb_, ss = sa + sb, p = 2.0 * na_ * nb_;
-  const double E = ea + (1.0 + ea) * eb + gamma * ((1.0 + ea) * (1.0 + eb)) + 1e-12;
-  const double W = (p * E + ss * kappa) * (1.0 + 1e-9) + 1e-280;
-  const double d2 = ss - p * (double)c;
-  const bool ok = ss < 1e300;  // no overflow anywhere in the canonical chain; false for NaN
-  dlo = ok ? d2 - W : (double)NAN;
-  dhi = ok ? d2 + W : (double)NAN;
-}
-
-__device__ __forceinline__ uint32_t l2f_lds_off(int r, int chunk) {
-  return (uint32_t)(r * (L2F_BK * 2) + ((chunk ^ (r & 7)) << 4));
-}
+static_assert(sizeof(L2fEpi) <= L2F_SMEM, "the epilogue's LDS fits the staging buffers");
 
 __global__ __launch_bounds__(256, 2) void l2f_main_kernel(L2fArgs a) {
-  __shared__ __attribute__((aligned(16))) char smem[2 * L2F_STAGE];
+  __shared__ __attribute__((aligned(16))) char smem[L2F_SMEM];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  // block order: groups of L2F_GM A tiles, inside a group the A tile runs fastest
+  const int wm = wave >> 1, wn = wave & 1, fr = lane & 15, fq = lane >> 4;
   int ta, tb_;
-  {
-    const int64_t L = blockIdx.x, per = (int64_t)L2F_GM * a.tiles_b;
-    const int g = (int)(L / per);
-    const int64_t in = L - (int64_t)g * per;
-    const int gs = min(L2F_GM, a.tiles_a - g * L2F_GM);
-    ta = g * L2F_GM + (int)(in % gs);
-    tb_ = (int)(in / gs);
-  }
+  l2f_tile_of_block(blockIdx.x, a.tiles_a, a.tiles_b, ta, tb_);
   const int64_t i0 = (int64_t)ta * L2F_BM, j0 = (int64_t)tb_ * L2F_BN;
 
-  // ---- the GEMM: c[tm][tn] = 16 x 16 blocks of the wave's 64 x 64 -------------------------------------------------
+  // ---- the GEMM: c[tm][tn] = 16 x 16 blocks of the wave's 64 x 64 (rows below n_pad, a multiple of 256: in bounds)
   l2f_f32x4 acc[4][4];
-#pragma unroll
-  for (int m = 0; m < 4; ++m)
-#pragma unroll
-    for (int n = 0; n < 4; ++n) acc[m][n] = l2f_f32x4{0.f, 0.f, 0.f, 0.f};
-  const int sc_ = tid & 7, sr = tid >> 3;  // staging: chunk sc_ of rows sr + 32 it
-  const uint16_t* ga = a.a16 + (i0 + sr) * a.d_pad + sc_ * 8;  // rows below n_pad (a multiple of 256): in bounds
-  const uint16_t* gb = a.b16 + (j0 + sr) * a.d_pad + sc_ * 8;
-  const uint32_t soff = l2f_lds_off(sr, sc_);  // (sr + 32 it) & 7 == sr & 7
-  l2f_u32x4 ra[4], rb[4];
-  const int nk = (int)(a.d_pad / L2F_BK);
-#define L2F_LOAD(kt)                                                                     \
-  _Pragma("unroll") for (int it = 0; it < 4; ++it) {                                     \
-    ra[it] = *(const l2f_u32x4*)(ga + (int64_t)(32 * it) * a.d_pad + (kt) * L2F_BK);     \
-    rb[it] = *(const l2f_u32x4*)(gb + (int64_t)(32 * it) * a.d_pad + (kt) * L2F_BK);     \
-  }
-#define L2F_WRITE(buf)                                                                   \
-  _Pragma("unroll") for (int it = 0; it < 4; ++it) {                                     \
-    *(l2f_u32x4*)(smem + (buf) * L2F_STAGE + soff + it * 32 * (L2F_BK * 2)) = ra[it];    \
-    *(l2f_u32x4*)(smem + (buf) * L2F_STAGE + L2F_A_BYTES + soff + it * 32 * (L2F_BK * 2)) = rb[it]; \
-  }
-  L2F_LOAD(0)
-  L2F_WRITE(0)
-  __syncthreads();
-  const int fr = lane & 15, fq = lane >> 4;
-  for (int kt = 0; kt < nk; ++kt) {
-    const int buf = kt & 1;
-    if (kt + 1 < nk) { L2F_LOAD(kt + 1) }
-    const char* pa = smem + buf * L2F_STAGE;
-    const char* pb = pa + L2F_A_BYTES;
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      l2f_f16x8 fa[4], fb[4];
-#pragma unroll
-      for (int m = 0; m < 4; ++m) fa[m] = *(const l2f_f16x8*)(pa + l2f_lds_off(wm * 64 + m * 16 + fr, ks * 4 + fq));
-#pragma unroll
-      for (int n = 0; n < 4; ++n) fb[n] = *(const l2f_f16x8*)(pb + l2f_lds_off(wn * 64 + n * 16 + fr, ks * 4 + fq));
-#pragma unroll
-      for (int m = 0; m < 4; ++m)
-#pragma unroll
-        for (int n = 0; n < 4; ++n)
-          acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fa[m], fb[n], acc[m][n], 0, 0, 0);
-    }
-    if (kt + 1 < nk) { L2F_WRITE(buf ^ 1) }
-    __syncthreads();
-  }
-#undef L2F_LOAD
-#undef L2F_WRITE
+  l2f_gemm_tile(a.a16, a.b16, a.d_pad, i0, j0, smem, acc);
 
   // ---- epilogue ------------------------------------------------------------------------------------------------------
   // acc[m][n][r] is the pair (A row wm 64 + 16 m + 4 fq + r, B row wn 64 + 16 n + fr) of the tile
@@ -185,7 +77,7 @@ __global__ __launch_bounds__(256, 2) void l2f_main_kernel(L2fArgs a) {
     const int64_t i = i0 + tid;
     const bool v = i < a.na;
     E.an[tid] = v ? 1.0 / a.a_inv[i] : (double)NAN;
-    E.ae[tid] = v ? (double)a.a_err[i] + a.theta : (double)NAN;
+    E.ae[tid] = v ? (double)a.a_err[i] + a.c.theta : (double)NAN;
     const int64_t o = (v && a.row_pos) ? a.row_off[i] : 0;
     const int m = (v && a.row_pos) ? (int)(a.row_off[i + 1] - o) : 0;
     E.ro[tid] = o;
@@ -197,7 +89,7 @@ __global__ __launch_bounds__(256, 2) void l2f_main_kernel(L2fArgs a) {
     const int64_t j = j0 + t;
     const bool v = j < a.nb;
     E.bn[t] = v ? 1.0 / a.b_inv[j] : (double)NAN;
-    E.be[t] = v ? (double)a.b_err[j] + a.theta : (double)NAN;
+    E.be[t] = v ? (double)a.b_err[j] + a.c.theta : (double)NAN;
     const int64_t o = (v && a.col_pos) ? a.col_off[j] : 0;
     const int m = (v && a.col_pos) ? (int)(a.col_off[j + 1] - o) : 0;
     E.co[t] = o;
@@ -225,14 +117,14 @@ __global__ __launch_bounds__(256, 2) void l2f_main_kernel(L2fArgs a) {
       if (tid < L2F_BM) {
         double tb = (double)NAN, tn = (double)NAN;
         const bool has = it < E.mr[tid];
-        if (has) l2f_thresholds(a.row_sc[E.ro[tid] + it], a.alpha, a.beta, a.rho, tb, tn);
+        if (has) l2f_thresholds(a.row_sc[E.ro[tid] + it], a.alpha, a.beta, a.c.rho, tb, tn);
         E.rtb[tid] = tb;
         E.rtn[tid] = tn;
       } else {
         const int t = tid - L2F_BM;
         double tb = (double)NAN, tn = (double)NAN;
         const bool has = it < E.mc[t];
-        if (has) l2f_thresholds(a.col_sc[E.co[t] + it], a.alpha, a.beta, a.rho, tb, tn);
+        if (has) l2f_thresholds(a.col_sc[E.co[t] + it], a.alpha, a.beta, a.c.rho, tb, tn);
         E.ctb[t] = tb;
         E.ctn[t] = tn;
       }
@@ -252,7 +144,7 @@ __global__ __launch_bounds__(256, 2) void l2f_main_kernel(L2fArgs a) {
             const int col = cbase + 16 * n;
             const int bit = (m * 4 + r) * 4 + n;
             double dlo, dhi;
-            l2f_interval(acc[m][n][r], an, ae, E.bn[col], E.be[col], a.gamma, a.kappa, dlo, dhi);
+            l2f_interval(acc[m][n][r], an, ae, E.bn[col], E.be[col], a.c.gamma, a.c.kappa, dlo, dhi);
             const bool chas = it < E.mc[col];
             const double ctb = E.ctb[col], ctn = E.ctn[col];
             const bool rb = pos ? dhi < rtb : dlo > rtb, rn = pos ? dlo > rtn : dhi < rtn;
@@ -320,7 +212,7 @@ __global__ __launch_bounds__(256, 2) void l2f_main_kernel(L2fArgs a) {
             for (int n = 0; n < 4; ++n) {
               const int row = rbase + 16 * m + r, col = cbase + 16 * n;
               double dlo, dhi;
-              l2f_interval(acc[m][n][r], E.an[row], E.ae[row], E.bn[col], E.be[col], a.gamma, a.kappa, dlo, dhi);
+              l2f_interval(acc[m][n][r], E.an[row], E.ae[row], E.bn[col], E.be[col], a.c.gamma, a.c.kappa, dlo, dhi);
               if (!(dlo == dlo)) band |= 1ull << ((m * 4 + r) * 4 + n);
             }
       }
@@ -367,8 +259,7 @@ __global__ __launch_bounds__(256) void l2f_fixup_kernel(const TA* __restrict__ A
                                                         const double* __restrict__ col_sc, int32_t* __restrict__ col_pos,
                                                         const int2* __restrict__ band, int64_t cap,
                                                         l2f_u64* __restrict__ stats) {
-  constexpr int KC = 16;
-  __shared__ double sd[4][64][KC + 1];  // [wave][pair][k]: lane p reads row p (17-double stride: conflict-free)
+  __shared__ double sd[4][64][L2F_KC + 1];  // [wave][pair][k]: lane p reads row p (17-double stride: conflict-free)
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int64_t n = (int64_t)stats[1];
   if (n > cap) return;  // the list overflowed: the caller redoes the call with the reported need
@@ -376,22 +267,7 @@ __global__ __launch_bounds__(256) void l2f_fixup_kernel(const TA* __restrict__ A
     const int64_t p = b0 + w * 64 + lane;
     const bool live = p < n;
     const int2 ij = band[live ? p : b0];  // an idle lane repeats a pair of the list: its loads stay in bounds
-    double s = 0.0, unused = 0.0;
-    for (int64_t k0 = 0; k0 < d; k0 += KC) {
-#pragma unroll 4
-      for (int it = 0; it < 16; ++it) {
-        const int q = it * 4 + (lane >> 4), k = lane & 15;
-        const int64_t qi = __shfl(ij.x, q, 64), qj = __shfl(ij.y, q, 64);
-        double df = 0.0;
-        if (k0 + k < d) df = (double)A[qi * lda + k0 + k] - (double)B[qj * ldb + k0 + k];
-        sd[w][q][k] = df;
-      }
-      __syncthreads();
-      const int kn = (int)min<int64_t>(KC, d - k0);
-      // the subtraction was done above (exact fp64 either way): pw_acc's own  t - 0  leaves it as it is
-      for (int k = 0; k < kn; ++k) pw_acc<CMVE_PW_L2>(sd[w][lane][k], 0.0, s, unused);
-      __syncthreads();
-    }
+    const double s = l2f_chain64(A, lda, B, ldb, d, ij.x, ij.y, sd[w], lane);
     const double e = pw_score<CMVE_PW_L2>(s, 0.0, alpha, beta);
     if (live) {
       if (row_pos) {
@@ -504,13 +380,7 @@ extern "C" int cmve_l2_count(cmve_handle_t h, const cmve_rows_t* a, const cmve_r
   g.d_pad = a->d_pad;
   g.alpha = alpha;
   g.beta = beta;
-  {  // DESIGN s4 (K19): every constant rounded up generously
-    const double n = (double)a->d_pad * (33.0 / 32.0), u = 1.0 / 8388608.0;
-    g.gamma = n * u / (1.0 - n * u) * (1.0 + 1e-12);
-    g.theta = ((double)d + 20.0) * L2F_U;
-    g.kappa = 16.0 * ((double)d + 32.0) * L2F_U;
-    g.rho = 2.0 * ((double)d + 16.0) * L2F_U;
-  }
+  g.c = l2f_consts(d, a->d_pad);  // DESIGN s4 (K19)
   g.row_off = row_off;
   g.row_sc = row_sc;
   g.row_pos = row_items ? row_pos : nullptr;

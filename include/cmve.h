@@ -748,6 +748,44 @@ int cmve_l2_count(cmve_handle_t h, const cmve_rows_t* a, const cmve_rows_t* b, d
                   const int64_t* col_off, const double* col_sc, int64_t col_items, int64_t col_n, int32_t* col_pos,
                   void* ws, int64_t ws_bytes, int64_t* stats);
 
+/* K20: cmve_pairwise_topk for CMVE_PW_L2 with fp64 score words at the MFMA rate (csrc/l2_topk.hip).
+ * Replaces, as its K18 twin does: LINAS-engine/inference.py:78-80 (cal_error(video_embs, cap_emb, measure) then
+ * np.argsort(errors[0])[:topK]) under euclidean / l2 / l2_norm (LINAS-engine/evaluation.py:22-35).
+ *   q, g: packed sets as cmve_l2_count requires (cmve_pack_rows with eps = 0 and the fp16 plane, not CMVE_PACK_RAW,
+ *   raw rows in F32 or F64) of the captions [n_q, d] and the gallery [n_g, d].  out_idx int64 [n_q, k] / out_err fp64
+ *   [n_q, k] hold, word for word, what cmve_pairwise_topk(metric = CMVE_PW_L2, score_dtype = CMVE_F64) writes for the
+ *   raw rows, alpha, beta and k: (error asc, index asc) on the canonical word, NaN last in index order, -0.0 == +0.0,
+ *   ids of g's rows.  1 <= k <= n_g (the caller clamps k to the gallery: there are no empty slots).
+ *   Four launches per round of 1,024 queries: the MFMA pass over the first sample_rows gallery
+ *   rows stores every pair's upper bound on sign(alpha) * ||q - g||^2; the k-th smallest per query, widened by the
+ *   roundings of the canonical chain, is a threshold beyond which a row's word is strictly worse than k rows'; the
+ *   MFMA pass over the whole gallery appends every row that does not clear it (or has no bound: a NaN, zero, huge or
+ *   tiny row) to the query's candidate list; a block per query re-scores its candidates on the canonical fp64 chain
+ *   (csrc/pairwise_tile.h), sorts them and emits k.
+ *   cand_cap: slots of a query's list, k <= cand_cap <= 2048 (what the last launch sorts in LDS).  sample_rows: 0 =
+ *   the default, max(k, 8) / 128 of the gallery within [1024, 65536]; any value is raised to k, rounded up to a
+ *   multiple of 128 and clamped to the gallery.
+ *   A query whose list overflows, or whose sample has fewer than k bounded rows (or no usable threshold: rows
+ *   clustered far from the origin under alpha < 0), is UNRESOLVED: out_idx[i, 0] = -2 and the rest of its row is not
+ *   written; the caller finishes it with cmve_pairwise_topk (engine.pairwise_topk does).
+ *   ws: cmve_l2_topk_workspace bytes (host only, no launch), 8-byte aligned, need not be zeroed: per query of a round
+ *   4 * round_up128(sample) + 4 * cand_cap + 12 bytes, min(1024, round_up128(n_q)) queries -- no n_q * n_g term.
+ *   Its last 4 * min(1024, round_up128(n_q)) bytes are the int32 candidate counters of the round's queries: after
+ *   the call they hold the LAST round's counts -- exact up to cand_cap, any value above it meaning "overflowed" (a
+ *   tile that finds a counter above cand_cap leaves it alone, so that a query whose every gallery row is a candidate
+ *   does not pay n_g atomics on one address).
+ *   stats: device int64[4] = {pairs excluded by the filter, candidates found, candidates re-scored, unresolved
+ *   queries}.  A query without a threshold contributes to neither of the first two; "found" counts every candidate, also
+ *   those past cand_cap.
+ *   Enqueued on the handle's stream; allocates nothing, never synchronises; integer atomics only.  Refused: k < 1,
+ *   k > cand_cap, cand_cap > 2048, k > n_g, alpha 0 or non-finite, beta non-finite, a set without h16, eps != 0,
+ *   CMVE_PACK_RAW, mismatched d, a short workspace. */
+int cmve_l2_topk_workspace(const cmve_rows_t* q, const cmve_rows_t* g, int32_t k, int64_t cand_cap,
+                           int64_t sample_rows, int64_t* bytes);
+int cmve_l2_topk(cmve_handle_t h, const cmve_rows_t* q, const cmve_rows_t* g, double alpha, double beta, int32_t k,
+                 int64_t cand_cap, int64_t sample_rows, void* ws, int64_t ws_bytes, int64_t* out_idx, double* out_err,
+                 int64_t* stats);
+
 /* ---- training step of the projection heads ---------------
  * K11: what LINAS-engine/model.py:984-1004 (train_emb, style 'GT') runs around the GEMMs (K3 forward,
  * cmve_gemm_f32 backward) and the losses (K6/K7).  Device pointers, fp32 rows; statistics in fp64.
