@@ -307,12 +307,10 @@ __device__ __forceinline__ void eval_prep_body(const EvalSide& q, const EvalSide
   if (blockIdx.x == 0 && threadIdx.x < 13) gst(c.stats + threadIdx.x, 0);  // the finish blocks add into it
   if (blockIdx.x == 0 && threadIdx.x == 0 && c.l3_count) gst(c.l3_count, 0u);  // the rank GEMM appends level 3
   float eb[3] = {0.f, 0.f, 0.f};  // this wave's row bounds (lane 0; padding rows 0)
-  if (!(c.dbg & 1)) {
-    if (row < q.n_pad)
-      prep_row<TQ, TG>(q, g, c, row, lane, eb);
-    else if (row < q.n_pad + g.n_pad)
-      prep_row<TG, TQ>(g, q, c, row - q.n_pad, lane, eb);
-  }
+  if (row < q.n_pad)
+    prep_row<TQ, TG>(q, g, c, row, lane, eb);
+  else if (row < q.n_pad + g.n_pad)
+    prep_row<TG, TQ>(g, q, c, row - q.n_pad, lane, eb);
   // err_max shards: the block's max per plane (its 4 rows are one side: n_pad % 4 == 0), one atomic
   // max on the float bits per plane into shard blockIdx % EMAX_SHARDS of its side (bounds are >= 0 or
   // +inf; NaN dropped by fmaxf); 64 shards keep ~8 same-address atomics per shard for a 1k-A prep
@@ -330,8 +328,7 @@ __device__ __forceinline__ void eval_prep_body(const EvalSide& q, const EvalSide
     const int side = (int64_t)blockIdx.x * PREP_NW < q.n_pad ? 0 : 1;
     unsigned* sh = &c.emax[(side * 3 + threadIdx.x) * EMAX_SHARDS + blockIdx.x % EMAX_SHARDS];
     // +inf (a plane the mode does not write) is the largest value: a plain store equals the atomic max
-    if (c.dbg & 2) {  // kernel studies only: no err_max shards (results garbage)
-    } else if (m == INFINITY) gst(sh, __float_as_uint(m));
+    if (m == INFINITY) gst(sh, __float_as_uint(m));
     else if (m > 0.f) gmax(sh, __float_as_uint(m));
   }
   EVAL_STAMP(c, 0, 1);
@@ -354,7 +351,7 @@ __device__ __forceinline__ void eval_prep_pair_body(const EvalSide& q, const Eva
   if (blockIdx.x == 0 && threadIdx.x < 13) gst(c.stats + threadIdx.x, 0);  // the finish blocks add into it
   if (blockIdx.x == 0 && threadIdx.x == 0 && c.l3_count) gst(c.l3_count, 0u);  // the rank GEMM appends level 3
   float ebq[3] = {0.f, 0.f, 0.f}, ebg[3] = {0.f, 0.f, 0.f};
-  if (i < q.n_pad && !(c.dbg & 1)) {
+  if (i < q.n_pad) {
     if (i >= q.n) {  // padding rows of both sides: zero vectors, zero bounds, never counted
       const EvalSide* sides[2] = {&q, &g};
 #pragma unroll
@@ -442,8 +439,7 @@ __device__ __forceinline__ void eval_prep_pair_body(const EvalSide& q, const Eva
 #pragma unroll
     for (int w = 0; w < PREP_NW; ++w) m = fmaxf(m, s_eb[w][threadIdx.x]);
     unsigned* sh = &c.emax[threadIdx.x * EMAX_SHARDS + blockIdx.x % EMAX_SHARDS];  // [side][plane] = tid
-    if (c.dbg & 2) {  // kernel studies only: no err_max shards (results garbage)
-    } else if (m == INFINITY) gst(sh, __float_as_uint(m));
+    if (m == INFINITY) gst(sh, __float_as_uint(m));
     else if (m > 0.f) gmax(sh, __float_as_uint(m));
   }
   EVAL_STAMP(c, 0, 1);
@@ -517,18 +513,15 @@ __device__ __forceinline__ void pack_f16_lo16(const EvalSide& A, int64_t row, co
 // one VGPR offset for every load of the row, the 256-element steps in scalar offsets (per-load 64-bit
 // addresses held ~64 registers and pushed the prep past 128)
 typedef uint32_t prep_u32x4 __attribute__((ext_vector_type(4)));
-#ifndef CMVE_PREP_ROW_AUX
-#define CMVE_PREP_ROW_AUX 0  // the raw rows' cache policy (gfx950 buffer aux bits: 2 = nt, 1 = sc0, 16 = sc1)
-#endif
 typedef double prep_f64x2 __attribute__((ext_vector_type(2)));
 template <int NM>
 __device__ __forceinline__ void load_row_buf(const double* row, int lane, double (&v)[NM][4]) {
   const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc((void*)row, 0, NM * 256 * 8, 0x00020000);
 #pragma unroll
   for (int m = 0; m < NM; ++m) {
-    const prep_f64x2 a = __builtin_bit_cast(prep_f64x2, __builtin_amdgcn_raw_buffer_load_b128(r, lane * 32, m * 2048, CMVE_PREP_ROW_AUX));
+    const prep_f64x2 a = __builtin_bit_cast(prep_f64x2, __builtin_amdgcn_raw_buffer_load_b128(r, lane * 32, m * 2048, 0));
     const prep_f64x2 b =
-        __builtin_bit_cast(prep_f64x2, __builtin_amdgcn_raw_buffer_load_b128(r, lane * 32 + 16, m * 2048, CMVE_PREP_ROW_AUX));
+        __builtin_bit_cast(prep_f64x2, __builtin_amdgcn_raw_buffer_load_b128(r, lane * 32 + 16, m * 2048, 0));
     v[m][0] = a.x;
     v[m][1] = a.y;
     v[m][2] = b.x;
@@ -540,7 +533,7 @@ __device__ __forceinline__ void load_row_buf(const float* row, int lane, double 
   const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc((void*)row, 0, NM * 256 * 4, 0x00020000);
 #pragma unroll
   for (int m = 0; m < NM; ++m) {
-    const cmve_f32x4 a = __builtin_bit_cast(cmve_f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, lane * 16, m * 1024, CMVE_PREP_ROW_AUX));
+    const cmve_f32x4 a = __builtin_bit_cast(cmve_f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, lane * 16, m * 1024, 0));
     v[m][0] = a.x;
     v[m][1] = a.y;
     v[m][2] = a.z;
@@ -561,7 +554,7 @@ __device__ __forceinline__ void eval_prep_pair_f16_body(const EvalSide& q, const
   if (vb == 0 && threadIdx.x < 13) gst(c.stats + threadIdx.x, 0);  // the finish blocks add into it
   if (vb == 0 && threadIdx.x == 0 && c.l3_count) gst(c.l3_count, 0u);  // the rank GEMM appends level 3
   float ebq[3] = {0.f, 0.f, 0.f}, ebg[3] = {0.f, 0.f, 0.f};
-  if (i < q.n_pad && !(c.dbg & 1)) {
+  if (i < q.n_pad) {
     if (i >= q.n) {  // padding rows of both sides: zero vectors, zero bounds, never counted
       const EvalSide* sides[2] = {&q, &g};
 #pragma unroll
@@ -636,8 +629,7 @@ __device__ __forceinline__ void eval_prep_pair_f16_body(const EvalSide& q, const
 #pragma unroll
     for (int w = 0; w < PREP_NW; ++w) m = fmaxf(m, s_eb[w][threadIdx.x]);
     unsigned* sh = &c.emax[threadIdx.x * EMAX_SHARDS + vb % EMAX_SHARDS];  // [side][plane] = tid
-    if (c.dbg & 2) {  // kernel studies only: no err_max shards (results garbage)
-    } else if (m == INFINITY) gst(sh, __float_as_uint(m));
+    if (m == INFINITY) gst(sh, __float_as_uint(m));
     else if (m > 0.f) gmax(sh, __float_as_uint(m));
   }
   EVAL_STAMP(c, 0, 1);
@@ -647,117 +639,16 @@ constexpr int FIX_NT = 256;
 #ifndef CMVE_FIX_BLOCKS
 #define CMVE_FIX_BLOCKS 1024
 #endif
-#ifndef CMVE_FIXB_BLOCKS
-#define CMVE_FIXB_BLOCKS 192  // (x 4 waves x 2 pairs: ~1,600 listed pairs of a 1k-A evaluation in one step)
-#endif
 
-// the fix-up of an evaluation with the level-2 planes (d_pad <= 1024): one flat walk over the buckets, TWO listed
-// pairs per wave per step with every level-2 load of both in flight (one round trip of 16 KiB), the directions
-// whose GT score lies outside s2 +- E2 decided there, fp64 (wave_cos64) for the few left
-// (vb, nvb: this block among the walk's blocks -- blockIdx.x / gridDim.x, or a role's own numbering in a shared
-// launch; MAXB: the bucket capacity of the LDS prefix)
-template <typename TQ, typename TG, int64_t MAXB = FIXUP_MAX_BUCKETS_PER_XCD>
-__device__ __forceinline__ void eval_fix2_walk(const EvalSide& q, const EvalSide& g, const EvalCommon& c, int64_t vb,
-                                               int64_t nvb) {
-  __shared__ int64_t pre[MAXB + 1];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int64_t nb = c.nb, ldk = c.d_pad;
-  if (wave == 0) fixup_prefix(c.cand, nb, c.cap_b, 0, 1, nb, lane, pre);
-  __syncthreads();
-  const int64_t total = pre[nb];
-  const int nw = (int)(blockDim.x >> 6);
-  const int64_t stride = nvb * nw * 2;
-  int64_t kb = 0;
-  auto entry = [&](int64_t cc) -> uint64_t {  // pair cc of the walk (0: none); cc increases call by call
-    if (cc >= total) return 0ull;
-    if (pre[kb + 1] <= cc) {
-      int64_t lo = kb + 1, hi = nb - 1;
-      while (lo < hi) {
-        const int64_t mid = (lo + hi + 1) >> 1;
-        if (pre[mid] <= cc) lo = mid;
-        else hi = mid - 1;
-      }
-      kb = lo;
-    }
-    return gld(c.cand + nb + kb * c.cap_b + (cc - pre[kb]));
-  };
-  const bool dq = q.off != nullptr, dg = g.off != nullptr;
-  for (int64_t c0 = (vb * nw + wave) * 2; c0 < total; c0 += stride) {
-    const uint64_t u[2] = {entry(c0), entry(c0 + 1)};
-    int64_t pi[2], pj[2];
-    uint32_t fl[2];
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      pi[t] = (int64_t)(u[t] & 0x7fffffffull);
-      pj[t] = (int64_t)((u[t] >> 31) & 0x7fffffffull);
-      fl[t] = (uint32_t)(u[t] >> 62) & ((dq ? 1u : 0u) | (dg ? 2u : 0u));
-    }
-    double s2[2] = {0.0, 0.0};
-    const int64_t k = 16 * (int64_t)lane;
-    if (k < ldk) {
-      L16Frag fa[2], fb[2];
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        l16_load(q.h16 + pi[t] * ldk, q.lo16 + pi[t] * ldk, k, fa[t]);  // (a null entry reads row 0: harmless)
-        l16_load(g.h16 + pj[t] * ldk, g.lo16 + pj[t] * ldk, k, fb[t]);
-      }
-#pragma unroll
-      for (int t = 0; t < 2; ++t) s2[t] = l16_partial(fa[t], fb[t], 0.0);
-    }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-      s2[0] += __shfl_xor(s2[0], o, 64);
-      s2[1] += __shfl_xor(s2[1], o, 64);
-    }
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      if (!fl[t]) continue;  // (wave-uniform)
-      const double eq = (double)gld(q.err_lo16 + pi[t]), eg = (double)gld(g.err_lo16 + pj[t]);
-      const double E2 = eq + (1.0 + eq) * eg + 2e-12;
-      const double tq = (fl[t] & 1u) ? gld(q.sgt + pi[t]) : 0.0, tg = (fl[t] & 2u) ? gld(g.sgt + pj[t]) : 0.0;
-      if ((fl[t] & 1u) && (s2[t] - E2 > tq || s2[t] + E2 < tq)) {
-        if (s2[t] - E2 > tq && lane == 0) gadd(q.cnt + pi[t], 1);
-        fl[t] &= ~1u;
-      }
-      if ((fl[t] & 2u) && (s2[t] - E2 > tg || s2[t] + E2 < tg)) {
-        if (s2[t] - E2 > tg && lane == 0) gadd(g.cnt + pj[t], 1);
-        fl[t] &= ~2u;
-      }
-      if (!fl[t]) continue;
-      // level 3: fp64, the fix-up's arithmetic
-      const double sc = wave_cos64((const TQ*)q.raw + pi[t] * q.ld, (const TG*)g.raw + pj[t] * g.ld,
-                                   gld(q.inv + pi[t]), gld(g.inv + pj[t]), c.d, lane);
-      if (lane == 0) {
-        if ((fl[t] & 1u) && sc > tq) gadd(q.cnt + pi[t], 1);
-        if ((fl[t] & 2u) && sc > tg) gadd(g.cnt + pj[t], 1);
-      }
-    }
-  }
-}
-
-// the evaluation's fix-up: the listed undecided pairs -- with the level-2 planes eval_fix2_walk, else fp64
-// (fixup_walk's flat walk)
-template <typename TQ, typename TG>
-__device__ __forceinline__ void eval_fix_body(const EvalSide& q, const EvalSide& g, const EvalCommon& c) {
-  EVAL_STAMP(c, 2, 0);
-  if (c.dbg & 8) {
-  } else if (q.lo16 && g.lo16 && c.nb <= FIXUP_MAX_BUCKETS_PER_XCD) {
-    eval_fix2_walk<TQ, TG>(q, g, c, blockIdx.x, gridDim.x);
-  } else {
-    fixup_walk<TQ, TG, true>((const TQ*)q.raw, q.ld, q.inv, (const TG*)g.raw, g.ld, g.inv, c.d, q.off ? q.sgt : nullptr,
-                             g.off ? g.sgt : nullptr, q.cnt, g.cnt, c.cand, c.nb, c.cap_b,
-                             c.nb <= FIXUP_MAX_BUCKETS_PER_XCD);
-  }
-  EVAL_STAMP(c, 2, 1);
-}
+// the evaluation's fix-up (geometries other than G64, whose rank GEMM lists its undecided pairs): fp64, fixup_walk's
+// flat walk.  (The level-2 planes exist only where the rank GEMM re-scores inline: no launch of this kernel then.)
 template <typename TQ, typename TG>
 __global__ __launch_bounds__(FIX_NT) void eval_fix_kernel(EvalSide q, EvalSide g, EvalCommon c) {
-  eval_fix_body<TQ, TG>(q, g, c);
-}
-template <typename TQ, typename TG>
-__global__ __launch_bounds__(FIX_NT) void eval_fix_batch_kernel(const EvalItem* __restrict__ tab) {
-  const EvalItem& it = tab[blockIdx.y];
-  eval_fix_body<TQ, TG>(it.q, it.g, it.c);
+  EVAL_STAMP(c, 2, 0);
+  fixup_walk<TQ, TG, true>((const TQ*)q.raw, q.ld, q.inv, (const TG*)g.raw, g.ld, g.inv, c.d, q.off ? q.sgt : nullptr,
+                           g.off ? g.sgt : nullptr, q.cnt, g.cnt, c.cand, c.nb, c.cap_b,
+                           c.nb <= FIXUP_MAX_BUCKETS_PER_XCD);
+  EVAL_STAMP(c, 2, 1);
 }
 
 // the pair total / overflow size (cand_finalize_kernel's), one block
@@ -803,7 +694,6 @@ __device__ __forceinline__ void eval_finish_body(const EvalSide& q, const EvalSi
                                                  int64_t nvb) {
   // vb / nvb: this block and the finish's block count (eval_prep_pair_f16_body's convention)
   EVAL_STAMP(c, 1, 0);
-  if (c.dbg & 32) return;
   __shared__ unsigned long long red[9 * FIN_NW];
   const int64_t nrank = nvb - 2;  // the last two blocks: pair total / overflow, err_max
   if (vb >= nrank) {
@@ -955,13 +845,8 @@ template <typename TQ, typename TG, int NM>
 #endif                      // and a launch above 104 fits one wave per SIMD beside the batch rank GEMM's two, not two)
 __global__ __launch_bounds__(PREP_NT, CMVE_PREPFIN_WPE) void eval_prep_fin_batch_kernel(const EvalItem* __restrict__ ptab,
                                                                                     const EvalItem* __restrict__ ftab,
-                                                                                    int nprep, int nfin,
-                                                                                    const EvalItem* __restrict__ xtab,
-                                                                                    int nfix) {
-  static_assert(PREP_NT == FIN_NT && PREP_NT == FIX_NT, "one block size for every role");
-#ifdef CMVE_STUDY_PREP_PRIO  // study: the chained prep's waves at a raised priority beside another stream's rank GEMM
-  __builtin_amdgcn_s_setprio(CMVE_STUDY_PREP_PRIO);
-#endif
+                                                                                    int nprep, int nfin) {
+  static_assert(PREP_NT == FIN_NT, "one block size for both roles");
   const int bx = (int)blockIdx.x;
   if (bx < nprep) {
     const EvalItem& it = ptab[blockIdx.y];
@@ -969,14 +854,6 @@ __global__ __launch_bounds__(PREP_NT, CMVE_PREPFIN_WPE) void eval_prep_fin_batch
   } else if (bx < nprep + nfin) {
     const EvalItem& it = ftab[blockIdx.y];
     eval_finish_body<TQ, TG, true>(it.q, it.g, it.c, bx - nprep, nfin);
-  } else {
-#if CMVE_EVAL_FIX_CHAINED  // study: the previous batch's level-2 / fp64 fix-up as a third role of the launch
-    const EvalItem& it = xtab[blockIdx.y];
-    eval_fix2_walk<TQ, TG, EVAL_FIXC_MAXB>(it.q, it.g, it.c, bx - nprep - nfin, nfix);
-#else
-    (void)xtab;
-    (void)nfix;
-#endif
   }
 }
 
@@ -1002,12 +879,6 @@ static int launch_eval_batch_typed(const EvalSide& q, const EvalSide& g, const E
     cmve::launch(eval_prep_batch_kernel<TQ, TG>, dim3(blocks, (unsigned)count), dim3(PREP_NT), 0u, s, tab);
     return check_launch("eval_prep_batch_kernel");
   }
-  if (phase == 1) {
-    // the batch's fix-up: CMVE_FIXB_BLOCKS blocks of 4 waves per evaluation (~1,600 listed pairs at 1k-A)
-    cmve::launch(eval_fix_batch_kernel<TQ, TG>, dim3((unsigned)CMVE_FIXB_BLOCKS, (unsigned)count), dim3(FIX_NT), 0u,
-                 s, tab);
-    return check_launch("eval_fix_batch_kernel");
-  }
   if (phase == 3) {
     const unsigned blocks = (unsigned)((q.n_pad + PREP_NW - 1) / PREP_NW);
     if (const int nm = prep_f16_nm(q, g, c0)) {
@@ -1025,30 +896,25 @@ static int launch_eval_batch_typed(const EvalSide& q, const EvalSide& g, const E
 
 template <typename TQ, typename TG>
 static int launch_eval_batch_chained_typed(const EvalSide& q, const EvalSide& g, const EvalCommon& c0,
-                                           const EvalItem* ptab, const EvalItem* ftab, int count, hipStream_t s,
-                                           const EvalItem* xtab) {
+                                           const EvalItem* ptab, const EvalItem* ftab, int count, hipStream_t s) {
   const int nm = prep_f16_nm(q, g, c0);
   CMVE_REQUIRE(nm, "launch_eval_batch_chained: the batch does not take the specialised paired prep");
-  CMVE_REQUIRE(!xtab || (CMVE_EVAL_FIX_CHAINED && c0.nb <= EVAL_FIXC_MAXB),
-               "launch_eval_batch_chained: no fix-up role in this build / too many buckets");
   const int nprep = (int)((q.n_pad + PREP_NW - 1) / PREP_NW);
   const int64_t nmax = q.n > g.n ? q.n : g.n;
   const int nfin = ftab ? (int)((nmax + FIN_NT - 1) / FIN_NT) + 2 : 0;
-  const int nfix = xtab ? CMVE_FIXB_BLOCKS : 0;
-  CMVE_PREP_F16(eval_prep_fin_batch_kernel, nm, dim3((unsigned)(nprep + nfin + nfix), (unsigned)count),
-                dim3(PREP_NT), 0u, s, ptab, ftab, nprep, nfin, xtab, nfix);
+  CMVE_PREP_F16(eval_prep_fin_batch_kernel, nm, dim3((unsigned)(nprep + nfin), (unsigned)count), dim3(PREP_NT), 0u, s,
+                ptab, ftab, nprep, nfin);
   return check_launch("eval_prep_fin_batch_kernel");
 }
 
 // the specialised paired prep of `ptab` and the finish of `ftab` (nullptr: none) in one launch; both batches have
 // the shapes of q / g / c0 and `count` evaluations
 int launch_eval_batch_chained(const EvalSide& q, const EvalSide& g, const EvalCommon& c0, const EvalItem* ptab,
-                              const EvalItem* ftab, int count, int q_f64, int g_f64, hipStream_t s,
-                              const EvalItem* xtab) {
-  if (!q_f64 && !g_f64) return launch_eval_batch_chained_typed<float, float>(q, g, c0, ptab, ftab, count, s, xtab);
-  if (!q_f64 && g_f64) return launch_eval_batch_chained_typed<float, double>(q, g, c0, ptab, ftab, count, s, xtab);
-  if (q_f64 && !g_f64) return launch_eval_batch_chained_typed<double, float>(q, g, c0, ptab, ftab, count, s, xtab);
-  return launch_eval_batch_chained_typed<double, double>(q, g, c0, ptab, ftab, count, s, xtab);
+                              const EvalItem* ftab, int count, int q_f64, int g_f64, hipStream_t s) {
+  if (!q_f64 && !g_f64) return launch_eval_batch_chained_typed<float, float>(q, g, c0, ptab, ftab, count, s);
+  if (!q_f64 && g_f64) return launch_eval_batch_chained_typed<float, double>(q, g, c0, ptab, ftab, count, s);
+  if (q_f64 && !g_f64) return launch_eval_batch_chained_typed<double, float>(q, g, c0, ptab, ftab, count, s);
+  return launch_eval_batch_chained_typed<double, double>(q, g, c0, ptab, ftab, count, s);
 }
 
 // whether a batch of these shapes takes launch_eval_batch_chained

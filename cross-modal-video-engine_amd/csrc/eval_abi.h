@@ -52,13 +52,12 @@ struct EvalCommon {
   unsigned* l3_count;
   uint64_t* l3;
   int l3_cap;
-  int dbg;                     // kernel studies only (CMVE_EVAL_DBG): skip parts, results garbage
   unsigned long long* stamps;  // kernel studies only (CMVE_EVAL_DBG & 128): [kernel][block][8] s_memrealtime
                                // (kernel 0 prep, 1 finish, 2 fix-up, 3 the rank GEMM's tiles)
 };
 
-// phase 0: pack + GT scores, phase 1: fix-up, phase 2: err_max + ranks + R@K (the rank GEMM runs between
-// phases 0 and 1, sim.hip); stamp k of block b in kernel kern (0 prep, 1 finish, 2 fix-up) when stamps are on
+// phase 0: pack + GT scores, phase 1: fix-up (one evaluation outside the G64 geometry only), phase 2: err_max +
+// ranks + R@K (the rank GEMM runs between phases 0 and 1, sim.hip); stamp k of block b in kernel kern (0 prep, 1 finish, 2 fix-up) when stamps are on
 #define EVAL_STAMP(cp, kern, k)                                                                                  \
   if ((cp).stamps && threadIdx.x == 0 && blockIdx.x < 1024)                                                     \
   (cp).stamps[((size_t)(kern) * 1024 + blockIdx.x) * 8 + (k)] = __builtin_amdgcn_s_memrealtime()
@@ -69,14 +68,8 @@ struct EvalItem {
   EvalSide q, g;
   EvalCommon c;
 };
-#ifndef CMVE_EVAL_FIX_CHAINED
-#define CMVE_EVAL_FIX_CHAINED 0  // study (with CMVE_EVAL_INLINE_L2=0): a batch's fix-up rides in the next chained launch
-#endif
-constexpr int64_t EVAL_FIXC_MAXB = 1024;  // the chained fix-up role's LDS bucket prefix (a 1k-A evaluation: 256)
-// (xtab: a batch whose fix-up runs as a third role of the launch -- the CMVE_EVAL_FIX_CHAINED study only)
 int launch_eval_batch_chained(const EvalSide& q, const EvalSide& g, const EvalCommon& c0, const EvalItem* ptab,
-                              const EvalItem* ftab, int count, int q_f64, int g_f64, hipStream_t s,
-                              const EvalItem* xtab = nullptr);
+                              const EvalItem* ftab, int count, int q_f64, int g_f64, hipStream_t s);
 bool eval_batch_chainable(const EvalSide& q, const EvalSide& g, const EvalCommon& c0);
 int launch_eval_batch(const EvalSide& q, const EvalSide& g, const EvalCommon& c0, const EvalItem* tab, int count,
                       int q_f64, int g_f64, int phase, hipStream_t s);

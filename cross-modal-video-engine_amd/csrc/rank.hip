@@ -145,10 +145,7 @@ __global__ __launch_bounds__(256) void fixup_kernel(const TQ* __restrict__ qraw,
 // walk is bound by the round trips in flight there (C4 ranking 10.1 -> 8.5 ms; it used to be held to 16 waves per
 // CU by a 32 KiB static LDS prefix).  Wider rows (the 1024-d gallery shards: a query row per pair from the
 // Infinity Cache at ~6 TB/s) keep 128 blocks per XCD: more waves in flight only contend (1M-gallery fix-up 11.6 ->
-// 13.4 ms).  Study builds: CMVE_FIX_BPX (blocks per XCD), CMVE_FIX_PF=1 (GT scores loaded ahead of the dot).
-#ifndef CMVE_FIX_BPX
-#define CMVE_FIX_BPX 0
-#endif
+// 13.4 ms; a bounded grid: profiles/STUDIES.md).  Study build: CMVE_FIX_PF=1 (GT scores loaded ahead of the dot).
 #ifndef CMVE_FIX_PF
 #define CMVE_FIX_PF 0
 #endif
@@ -163,8 +160,7 @@ static void launch_fix(hipStream_t stream, const cmve_rows_t* q, const cmve_rows
     return std::max(1, n);
   }();
   const int64_t row_bytes = q->d * std::max<int64_t>(sizeof(TQ), sizeof(TG));
-  const int bpx = CMVE_FIX_BPX > 0 ? std::min(1024, CMVE_FIX_BPX)
-                  : row_bytes < 4096 ? per_cu * std::max(1, device_cus() / 8) : 128;
+  const int bpx = row_bytes < 4096 ? per_cu * std::max(1, device_cus() / 8) : 128;
   const unsigned lds = (unsigned)(((nb + 7) / 8 + 1) * sizeof(int64_t));  // the walk's bucket prefix
   hipLaunchKernelGGL((fixup_kernel<TQ, TG, PF>), dim3(8u * (unsigned)bpx), dim3(256), lds, stream, (const TQ*)q->raw,
                      q->raw_ld, q->inv_norm, (const TG*)g->raw, g->raw_ld, g->inv_norm, q->d, row_sgt, col_sgt, row_cnt,

@@ -30,48 +30,9 @@
 #ifndef CMVE_SIM_GN
 #define CMVE_SIM_GN 8  // gallery tiles per tile-order group (GN = 2..16 measured within 2%)
 #endif
-#ifndef CMVE_SIM_GEO
-#define CMVE_SIM_GEO 0  // 128: force G128; 2562: the 2-stage G256 loop
-#endif
-#ifndef CMVE_BATCH_GEO
-#define CMVE_BATCH_GEO 0  // K14 batch rank tile: 1288 / 256128 / 64 / 12864 (see batch_geo_force)
-#endif
 #ifndef CMVE_EVAL_DBG
-#define CMVE_EVAL_DBG 0  // K14 kernel studies: skip parts (results garbage) / 128: per-block stamps
+#define CMVE_EVAL_DBG 0  // K14 kernel studies: 128 = per-block stamps (tools/eval_stamps.py, tools/batch_stamps.py)
 #endif
-#ifndef CMVE_EVAL_INLINE_L2
-#define CMVE_EVAL_INLINE_L2 1  // 0: the level-2 re-score in a fix-up launch instead of inside the rank GEMM
-#endif
-#ifndef CMVE_EVAL_NO_L2
-#define CMVE_EVAL_NO_L2 0  // 1: every band pair in fp64 inside the GEMM (no residual plane)
-#endif
-#ifndef CMVE_EVAL_L3_LIST
-#define CMVE_EVAL_L3_LIST 0  // 1: one evaluation lists its level-3 pairs for the finish as batches do
-#endif
-#ifndef CMVE_L2_PIPE
-#define CMVE_L2_PIPE 1  // K14 level-2 re-score: one pair per wave per step, the next pair's rows in flight (0: rounds
-#endif                  // of CMVE_L2_P* pairs per wave, each round one round trip)
-#ifndef CMVE_G64_KG
-#define CMVE_G64_KG 2  // one K14 evaluation's G64 rank GEMM: K groups (2: split-K over two groups of 4 waves)
-#endif
-#ifndef CMVE_EPI_BOTH_ASM
-#define CMVE_EPI_BOTH_ASM 1  // rank epilogue, both directions: hand-scheduled scoring (pair2_count_bits); 0: compiler's
-#endif
-#ifndef CMVE_EPI_T2V_DBL
-#define CMVE_EPI_T2V_DBL 0  // rank epilogue, t2v only: col4_count_bits (band bits by doubling) instead of row4_count_bits
-#endif
-#ifndef CMVE_RING_KROT
-#define CMVE_RING_KROT 0  // the batch ring: K-slice order rotated per tile (study)
-#endif
-#ifndef CMVE_RING_VGPR_STAGE
-#define CMVE_RING_VGPR_STAGE 0  // the batch ring: K-tiles staged through registers instead of LDS-DMA (study)
-#endif
-#ifndef CMVE_RING_READS_FIRST
-// ring loops: a K-tile's fragment reads all issued before its MFMAs (study: the batch rank GEMM alone 41.0 -> 38.4 us,
-// one stream 8.5 -> 8.65e10, but three streams 1.26 -> 1.20e11 -- profiles/r06_ab_reads_first.txt)
-#define CMVE_RING_READS_FIRST 0
-#endif
-
 namespace cmve {
 
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
@@ -152,7 +113,6 @@ struct SimArgs {
   // ghi) and their per-row bounds; a band pair is decided from h16 + lo16 (lo16_elem) when its score clears the
   // GT score by the level-2 bound; the rest go to the level-3 list (EvalCommon::l3, re-scored in fp64 by the
   // finish), or are re-scored here when it is full.  nullptr: every pair in fp64 here
-  int ovf_inline;  // K14 with a fix-up launch: a wave whose pairs overflow its bucket re-scores them itself
   const uint16_t* q_lo16;
   const uint16_t* g_lo16;
   const float* q_el;
@@ -161,33 +121,6 @@ struct SimArgs {
   unsigned long long* l3;
   int l3_cap;
 };
-
-// (L16Frag, l16_load, l16_partial: the level-2 re-score's fragments, cmve_internal.h)
-// the wave's level-2 scores of P pairs (rows qr[p] of the query planes, gc[p] of the gallery planes), every
-// load of all P pairs in flight before the sums; d_pad % 64 == 0 (a lane's 16 elements are all in or all out)
-template <int P>
-__device__ __forceinline__ void l16_scores(const SimArgs& a, const int64_t (&qr)[P], const int64_t (&gc)[P], int lane,
-                                          double (&s2)[P]) {
-#pragma unroll
-  for (int p = 0; p < P; ++p) s2[p] = 0.0;
-  for (int64_t k0 = 0; k0 < a.ldk; k0 += 1024) {
-    const int64_t k = k0 + 16 * lane;
-    if (k < a.ldk) {
-      L16Frag fq[P], fg[P];
-#pragma unroll
-      for (int p = 0; p < P; ++p) {
-        l16_load(a.qhi + qr[p] * a.ldk, a.q_lo16 + qr[p] * a.ldk, k, fq[p]);
-        l16_load(a.ghi + gc[p] * a.ldk, a.g_lo16 + gc[p] * a.ldk, k, fg[p]);
-      }
-#pragma unroll
-      for (int p = 0; p < P; ++p) s2[p] = l16_partial(fq[p], fg[p], s2[p]);
-    }
-  }
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1)
-#pragma unroll
-    for (int p = 0; p < P; ++p) s2[p] += __shfl_xor(s2[p], o, 64);
-}
 
 // bijective XCD remap (xcd_linear, cmve_internal.h) + grouped (GN gallery tiles x all query tiles) logical order
 __device__ __forceinline__ void tile_grouped(int L, int nblk_m, int nblk_n, int GN, int& bm, int& bn);
@@ -202,37 +135,29 @@ __device__ __forceinline__ void tile_grouped(int L, int nblk_m, int nblk_n, int 
   bn = group * GN + (within - bm * gn);
 }
 
-// the LDS image of a staged K-tile of KB (64 or 32) bf16/fp16 columns: row r at r * 2KB bytes, its 16-B chunk k in
-// slot k ^ swz(r) -- conflict-free ds_read_b128 fragment reads (16 rows x one chunk per 16 lanes): 128-B rows
-// (KB = 64, 8 chunks) XOR the row's low 3 bits; 64-B rows (KB = 32, 4 chunks, four rows per 256-B bank line) XOR
-// bits 2-3, so rows r, r + 4, r + 8, r + 12 of one bank offset take four different slots
-template <int KB>
-__host__ __device__ constexpr int lds_swz(int r) {
-  return KB == 64 ? (r & 7) : ((r >> 2) & 3);
-}
+// the LDS image of a staged K-tile of BK = 64 bf16/fp16 columns: row r at r * 128 bytes, its 16-B chunk k in slot
+// k ^ (r & 7) -- conflict-free ds_read_b128 fragment reads (16 rows x one chunk per 16 lanes)
+__host__ __device__ constexpr int lds_swz(int r) { return r & 7; }
 
-// this lane's byte offset inside any staging wave-instruction of a KB-deep K-tile: one instruction's 64 lanes cover
-// RPI whole rows, and the swizzle takes only a row's low bits (KB = 64: r & 7 with RPI = 8; KB = 32: (r >> 2) & 3
-// with RPI = 16), so the offset is the same for every instruction of every wave -- computed once per kernel, the K
-// loop's staging is scalar address math (per-instruction 64-bit lane address math cost ~60 VALU cycles x 8 per wave
-// per K-tile in the batch ring)
-template <int KB>
+// this lane's byte offset inside any staging wave-instruction of a K-tile: one instruction's 64 lanes cover 8 whole
+// rows, and the swizzle takes only a row's low 3 bits, so the offset is the same for every instruction of every
+// wave -- computed once per kernel, the K loop's staging is scalar address math (per-instruction 64-bit lane address
+// math cost ~60 VALU cycles x 8 per wave per K-tile in the batch ring)
 __device__ __forceinline__ uint32_t stage_lane_off(int64_t ldk, int lane) {
-  constexpr int CPR = KB / 8;  // 16-B chunks per row
+  constexpr int CPR = BK / 8;  // 16-B chunks per row
   const int r = lane / CPR, c = lane % CPR;
-  return (uint32_t)(((int64_t)r * ldk + (c ^ lds_swz<KB>(r)) * 8) * 2);
+  return (uint32_t)(((int64_t)r * ldk + (c ^ lds_swz(r)) * 8) * 2);
 }
 
-// issue this wave's share of one ROWS x KB (bf16/fp16) plane: ROWS x 2KB / 1 KiB wave-instructions of 1 KiB; src,
-// ldk, row0, k0 and wave are uniform (the block base is scalar; loff = stage_lane_off<KB>)
-template <int ROWS, int NW, int KB = BK>
+// issue this wave's share of one ROWS x BK (bf16/fp16) plane: ROWS / 8 wave-instructions of 1 KiB; src, ldk, row0,
+// k0 and wave are uniform (the block base is scalar; loff = stage_lane_off)
+template <int ROWS, int NW>
 __device__ __forceinline__ void stage_plane(const uint16_t* __restrict__ src, int64_t ldk, int row0, int k0,
                                             char* lds_plane, int wave, uint32_t loff) {
-  constexpr int CPR = KB / 8;    // 16-B chunks per row
-  constexpr int RPI = 64 / CPR;  // rows per wave-instruction
+  constexpr int RPI = 64 / (BK / 8);  // rows per wave-instruction
   constexpr int PER_WAVE = ROWS / RPI / NW;
   static_assert(PER_WAVE * RPI * NW == ROWS, "plane rows must split evenly over the waves");
-  static_assert(lds_swz<KB>(RPI) == 0 && lds_swz<KB>(RPI - 1) == lds_swz<KB>(2 * RPI - 1), "swizzle period");
+  static_assert(lds_swz(RPI) == 0 && lds_swz(RPI - 1) == lds_swz(2 * RPI - 1), "swizzle period");
   const char* blk = (const char*)(src + ((int64_t)row0 + wave * PER_WAVE * RPI) * ldk + k0);
 #pragma unroll
   for (int it = 0; it < PER_WAVE; ++it)
@@ -240,9 +165,8 @@ __device__ __forceinline__ void stage_plane(const uint16_t* __restrict__ src, in
                                      (lds_void_t*)(lds_plane + (wave * PER_WAVE + it) * 1024), 16, 0, 0);
 }
 
-template <int KB = BK>
 __device__ __forceinline__ s16x8_t read_frag(const char* plane, int row, int chunk) {
-  return *(const s16x8_t*)(plane + row * (KB * 2) + ((chunk ^ lds_swz<KB>(row)) << 4));
+  return *(const s16x8_t*)(plane + row * (BK * 2) + ((chunk ^ lds_swz(row)) << 4));
 }
 
 // LDS atomic add in inline asm: the compiler drains vmcnt before any LDS write it emits while
@@ -343,40 +267,6 @@ __device__ __forceinline__ void pair2_count_bits(float sa, float sb, float hia, 
         [clo] "v"(clo));
 }
 
-// t2v only (the gallery shape): the four scores of one column block (rows r = 3..0 of the lane's four) against
-// their row thresholds; the counts go to c3..c0 and the band bits are appended to u by doubling (bit j * 4 + r, most
-// significant first, as pair2_count_bits): 4 VALU + 1 SALU per score (row4_count_bits: 5 + 1)
-__device__ __forceinline__ void col4_count_bits(float s3, float s2, float s1, float s0, const f32x4_t& hi,
-                                                const f32x4_t& lo, uint32_t& c3, uint32_t& c2, uint32_t& c1,
-                                                uint32_t& c0, uint32_t& u) {
-  unsigned long long m3, m2, m1, m0, l3, l2, l1, l0, cy;
-  asm("v_cmp_gt_f32_e64 %[m3], %[s3], %[h3]\n\t"
-      "v_cmp_gt_f32_e64 %[m2], %[s2], %[h2]\n\t"
-      "v_cmp_gt_f32_e64 %[m1], %[s1], %[h1]\n\t"
-      "v_cmp_gt_f32_e64 %[m0], %[s0], %[h0]\n\t"
-      "v_cmp_ge_f32_e64 %[l3], %[s3], %[o3]\n\t"
-      "v_cmp_ge_f32_e64 %[l2], %[s2], %[o2]\n\t"
-      "v_cmp_ge_f32_e64 %[l1], %[s1], %[o1]\n\t"
-      "v_cmp_ge_f32_e64 %[l0], %[s0], %[o0]\n\t"
-      "v_addc_co_u32_e64 %[c3], %[cy], %[c3], 0, %[m3]\n\t"
-      "v_addc_co_u32_e64 %[c2], %[cy], %[c2], 0, %[m2]\n\t"
-      "v_addc_co_u32_e64 %[c1], %[cy], %[c1], 0, %[m1]\n\t"
-      "v_addc_co_u32_e64 %[c0], %[cy], %[c0], 0, %[m0]\n\t"
-      "s_andn2_b64 %[l3], %[l3], %[m3]\n\t"
-      "s_andn2_b64 %[l2], %[l2], %[m2]\n\t"
-      "s_andn2_b64 %[l1], %[l1], %[m1]\n\t"
-      "s_andn2_b64 %[l0], %[l0], %[m0]\n\t"
-      "v_addc_co_u32_e64 %[u], %[cy], %[u], %[u], %[l3]\n\t"
-      "v_addc_co_u32_e64 %[u], %[cy], %[u], %[u], %[l2]\n\t"
-      "v_addc_co_u32_e64 %[u], %[cy], %[u], %[u], %[l1]\n\t"
-      "v_addc_co_u32_e64 %[u], %[cy], %[u], %[u], %[l0]"
-      : [c3] "+v"(c3), [c2] "+v"(c2), [c1] "+v"(c1), [c0] "+v"(c0), [u] "+v"(u), [m3] "=&s"(m3), [m2] "=&s"(m2),
-        [m1] "=&s"(m1), [m0] "=&s"(m0), [l3] "=&s"(l3), [l2] "=&s"(l2), [l1] "=&s"(l1), [l0] "=&s"(l0),
-        [cy] "=&s"(cy)
-      : [s3] "v"(s3), [s2] "v"(s2), [s1] "v"(s1), [s0] "v"(s0), [h3] "v"(hi[3]), [h2] "v"(hi[2]), [h1] "v"(hi[1]),
-        [h0] "v"(hi[0]), [o3] "v"(lo[3]), [o2] "v"(lo[2]), [o1] "v"(lo[1]), [o0] "v"(lo[0]));
-}
-
 template <int MODE>
 __device__ __forceinline__ f32x4_t mfma(s16x8_t a, s16x8_t b, f32x4_t c) {
   if constexpr (MODE == CMVE_SIM_F16)
@@ -398,81 +288,43 @@ struct Geo {
 
 // staged bytes per K-tile: one plane per operand; the 2-stage G128 loop stages both planes of a
 // split-bf16 operand per K-tile, the phased G256 loop walks the planes along K (plane_of)
-template <int MODE, int BM, int BN, bool PHASED, int KB = BK>
+template <int MODE, int BM, int BN, bool PHASED>
 constexpr size_t stage_bytes() {
-  return (size_t)((MODE == CMVE_SIM_BF16X3 && !PHASED) ? 2 : 1) * (BM + BN) * KB * 2;
+  return (size_t)((MODE == CMVE_SIM_BF16X3 && !PHASED) ? 2 : 1) * (BM + BN) * BK * 2;
 }
 
-// the ring loop's geometries (G64, 128 x 64 and the 8-wave 128 x 128 of the batches); the others take the 2-stage
-// loop (G128) or the phased G256 schedule
-template <int BM, int BN, bool PHASED, int NW = 4>
+// the ring loop's geometries (G64 and the batches' 128 x 64; the batches' 128 x 128 joins them in sim_kernel); the
+// others take the 2-stage loop (G128) or the phased G256 schedule
+template <int BM, int BN, bool PHASED>
 constexpr bool is_ring() {
-  return !PHASED && (((BN == 64 || (BM == 128 && BN == 128 && NW == 8)) && (BM == 64 || BM == 128)) ||
-                     (BM == 256 && BN == 128 && NW == 8));
-}
-// the K14 batches' 256 x 128 tiles (one block of 8 waves of 64 x 64 per CU, up to 256 VGPRs)
-template <int BM, int BN>
-constexpr bool is_big_ring() {
-  return BM == 256 && BN == 128;
+  return !PHASED && BN == 64 && (BM == 64 || BM == 128);
 }
 
-// K-tile depth of a ring geometry's stages: the batches' 8-wave 128 x 128 ring stages 32-deep K-tiles
-// (CMVE_BATCH_KB): at the same LDS, twice as many stages -- three K-tiles in flight instead of one, for a main loop
-// that waits on L2 / Infinity-Cache latency (the stamps: 0.95 us per 64-deep K-tile against ~0.3 us of MFMAs)
-#ifndef CMVE_BATCH_KB
-#define CMVE_BATCH_KB 64
-#endif
-template <int BM, int BN, bool PHASED, int NW>
-constexpr int ring_kb() {
-  return (!PHASED && BM == 128 && BN == 128 && NW == 8) ? CMVE_BATCH_KB : BK;
-}
-
-// staging ring depth of the 2-stage (non-phased) loop: the G64 tiles of small problems keep NS - 1
+// staging ring depth of the non-phased loops: the G64 tiles of small problems keep NS - 1
 // K-tiles in flight (a 1k x 1k x 1024 GEMM is latency-bound: with 2 stages every one of its 16 K-tiles
 // exposed a full L2 / Infinity-Cache round trip, ~1.2 us each against ~0.1 us of MFMAs).  4 stages
 // (64 KiB of LDS) rather than 8: a G64 block is bound by its 2 waves ISSUING the LDS-DMA pieces
 // (8 per wave per K-tile, ~2.7 us for the first 7 K-tiles of an 8-deep ring in the stamps), so a deeper
 // ring gains nothing alone, while 64 KiB lets two evaluations' rank GEMMs share a CU (two HIP streams:
 // 31.0 -> 26.6 us per evaluation, tools/eval_pipe.py)
-// The K14 batches' rings (cmve_eval_batch_*): 128 x 128 with 8 waves, 2 stages of 32 KiB -- two blocks per CU
-// (<= 128 VGPRs: CMVE_BATCH_WPE), so one block's level-2 re-score round trips run under the other's main loop
-// (round 4: rank GEMM 52 -> 38 us per batch of 8, headline 9.9e10 -> 1.11e11 against 3 stages of one block per
-// CU) -- and 128 x 64 (split-bf16), 3 stages of 24 KiB
-template <int MODE, int BM, int BN, bool PHASED, int NW = 4>
-constexpr int ring_stages() {
+// The K14 batches' rings (cmve_eval_batch_*): 128 x 128 on 4 waves, 2 stages of 32 KiB -- two blocks per CU, so one
+// block's level-2 re-score round trips run under the other's main loop -- and 128 x 64 (split-bf16, whose stage
+// holds both planes: 2 x 48 KiB; shapes that do not tile by 128).  Other tile shapes and depths: profiles/STUDIES.md
 #ifndef CMVE_G64_STAGES
 #define CMVE_G64_STAGES 4
 #endif
 #ifndef CMVE_G128R_STAGES
 #define CMVE_G128R_STAGES 2
 #endif
-  // (64 x 64, 128 x 64 and the 8-wave 128 x 128; the 4-wave G128 of mid-size problems keeps its 2-stage loop)
-#ifndef CMVE_G256R_STAGES
-#define CMVE_G256R_STAGES 3
-#endif
-  if (!PHASED && is_big_ring<BM, BN>() && NW == 8) return CMVE_G256R_STAGES;  // (3 x 48 KiB: one block per CU)
-  // the batches' 128 x 128: CMVE_G128R_STAGES x 64-deep K-tiles of LDS, as twice as many 32-deep stages with
-  // CMVE_BATCH_KB = 32 (ring_kb)
-  return (PHASED || (BN != 64 && !(BM == 128 && BN == 128 && NW == 8)) || (BM != 64 && BM != 128))
-             ? 2
-             : (BM == 64 ? CMVE_G64_STAGES : CMVE_G128R_STAGES * (BK / ring_kb<BM, BN, PHASED, NW>()));
+template <int BM, int BN, bool PHASED>
+constexpr int ring_stages() {
+  return !is_ring<BM, BN, PHASED>() ? 2 : (BM == 64 ? CMVE_G64_STAGES : CMVE_G128R_STAGES);
 }
 
-// the K-tile depth a kernel instantiation stages: ring_kb, but the 4-wave 128 x 128 batch ring takes CMVE_BATCH4_KB
-// (32: a 32 KiB two-stage ring, three blocks per CU fit the LDS -- a study)
-#ifndef CMVE_BATCH4_KB
-#define CMVE_BATCH4_KB 64
-#endif
-template <int MODE, int BM, int BN, bool PHASED, int NW, bool BATCH>
-constexpr int kernel_kb() {
-  return (BATCH && !PHASED && BM == 128 && BN == 128 && NW == 4 && MODE != CMVE_SIM_BF16X3) ? CMVE_BATCH4_KB
-                                                                                            : ring_kb<BM, BN, PHASED, NW>();
-}
-
-// LDS of the staging buffers of a non-persistent geometry (the launchers' dynamic shared memory)
-template <int MODE, int BM, int BN, bool PHASED, int NW>
+// LDS of the staging buffers of a geometry (the launchers' dynamic shared memory)
+template <int MODE, int BM, int BN, bool PHASED>
 constexpr size_t ring_lds_bytes() {
-  return ring_stages<MODE, BM, BN, PHASED, NW>() * stage_bytes<MODE, BM, BN, PHASED, ring_kb<BM, BN, PHASED, NW>()>();
+  return ring_stages<BM, BN, PHASED>() * stage_bytes<MODE, BM, BN, PHASED>();
 }
 
 #ifdef CMVE_DBG_STAMPS  // diagnostic build only: per-block s_memtime stamps into the (unused) candidate list
@@ -531,26 +383,11 @@ struct EpiLds<BM, BN, false, INL> {
 #ifndef CMVE_G64_BLOCKS
 #define CMVE_G64_BLOCKS 2
 #endif
-#ifndef CMVE_BATCH_FIX1
-#define CMVE_BATCH_FIX1 1
-#endif
-#ifndef CMVE_L2_P
-#define CMVE_L2_P 1  // K14 level-2 re-score: pairs per wave in flight at once (2: 128+ VGPRs, spills at 4 waves per SIMD)
-#endif
-#ifndef CMVE_L2_P_BIG
-#define CMVE_L2_P_BIG 2  // the same for the batches' 256 x 128 tiles (one 8-wave block per CU: registers to spare)
-#endif
-#ifndef CMVE_L2_P_ONE
-#define CMVE_L2_P_ONE 2  // the same for one evaluation's G64 rank GEMM (4 waves, ~6 listed pairs per tile: one round)
-#endif
 // BATCH: one launch over a batch of same-shaped problems (cmve_eval_batch_*): the block picks the problem's
 // argument block in `tab` (see batch_item below); otherwise `tab` is unused
-#ifndef CMVE_BATCH_WPE
-#define CMVE_BATCH_WPE 4  // the batch ring kernels: waves per SIMD the register budget must allow (<= 128 VGPRs)
-#endif
 #ifndef CMVE_BATCH4_WPE
-// the default 4-wave 128 x 128 batch tile: 3 waves per SIMD (<= 168 VGPRs) -- two GEMM blocks per CU and a wave of
-// another stream's prep beside them on every SIMD (the product kernel needs 152)
+// the batch tiles (4 waves): 3 waves per SIMD (<= 168 VGPRs) -- two GEMM blocks per CU and a wave of another
+// stream's prep beside them on every SIMD (the 128 x 128 product kernel needs 152)
 #define CMVE_BATCH4_WPE 3
 #endif
 // KG = 2 (one K14 evaluation's G64 rank GEMM, sim_kernel_kg2): two groups of WM x WN waves, each streaming half of
@@ -560,10 +397,7 @@ struct EpiLds<BM, BN, false, INL> {
 template <int MODE, int EPI, int WM, int WN, int TM, bool PHASED, bool BATCH = false, int KG = 1>
 __global__ __launch_bounds__(WM * WN * 64 * KG,
                             KG > 1 ? 1
-                                   : (BATCH ? (is_big_ring<WM * TM * 16, WN * 64>()
-                                                   ? 2
-                                                   : (WM * WN == 4 ? (MODE == CMVE_SIM_BF16X3 ? 2 : CMVE_BATCH4_WPE)
-                                                                   : CMVE_BATCH_WPE))
+                                   : (BATCH ? (MODE == CMVE_SIM_BF16X3 ? 2 : CMVE_BATCH4_WPE)
                                             : ((WM * TM * 16 == 64 && WN == 1) ? CMVE_G64_BLOCKS : 2)))
 void sim_kernel(
     SimArgs a_arg, const SimArgs* __restrict__ tab) {
@@ -581,10 +415,9 @@ void sim_kernel(
   using G = Geo<WM, WN, TM>;
   constexpr int BM = G::BM, BN = G::BN, TN = G::TN, NT = G::NT, NW = G::NW;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int KB = kernel_kb<MODE, BM, BN, PHASED, NW, BATCH>();  // K-tile depth of the staging buffers
-  constexpr int STAGE_BYTES = (int)stage_bytes<MODE, BM, BN, PHASED, KB>();
-  constexpr int NS = ring_stages<MODE, BM, BN, PHASED, NW>();
-  constexpr int A_BYTES = BM * KB * 2, B_BYTES = BN * KB * 2;
+  constexpr int STAGE_BYTES = (int)stage_bytes<MODE, BM, BN, PHASED>();
+  constexpr int NS = ring_stages<BM, BN, PHASED>();
+  constexpr int A_BYTES = BM * BK * 2, B_BYTES = BN * BK * 2;
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // provably uniform: scalar M0 / soffset
@@ -615,7 +448,8 @@ void sim_kernel(
 
   // the G64 ring rank kernel re-scores its undecided pairs itself when the K14 host asks (SimArgs::fix_inline)
   // (the batches' default 128 x 128 tiles on 4 waves of 64 x 64 take the ring loop too)
-  constexpr bool RING = is_ring<BM, BN, PHASED, NW>() || (BATCH && BM == 128 && BN == 128 && NW == 4);
+  constexpr bool RING = is_ring<BM, BN, PHASED>() || (BATCH && BM == 128 && BN == 128);
+  static_assert(KG == 1 || (RING && !PHASED && !BATCH), "split-K is the single evaluation's G64 ring launch only");
   constexpr bool INL = EPI == EPI_RANK && RING;
   __shared__ EpiLds<BM, BN, epi_thr(EPI), INL> epi;
   double sgt_pub = 0.0;  // INL: this thread's row / column GT score (tid < BM + BN), published with the thresholds
@@ -697,18 +531,15 @@ void sim_kernel(
   const uint16_t* const st_qlo = MODE == CMVE_SIM_BF16X3 ? a.qlo : nullptr;
   const uint16_t* const st_glo = MODE == CMVE_SIM_BF16X3 ? a.glo : nullptr;
   const int64_t st_ldk = a.ldk;
-  const uint32_t st_loff = stage_lane_off<KB>(st_ldk, lane);
+  const uint32_t st_loff = stage_lane_off(st_ldk, lane);
   auto stage = [&](int t, int s) {
-#ifdef CMVE_DBG_NOLOAD
-    return;
-#endif
     char* base = smem + (group * NS + s) * STAGE_BYTES;  // (KG = 2: each group's ring of its own)
-    const int k0 = t * KB;
-    stage_plane<BM, NW, KB>(st_qhi, st_ldk, m0, k0, base, lw, st_loff);
-    stage_plane<BN, NW, KB>(st_ghi, st_ldk, n0, k0, base + A_BYTES, lw, st_loff);
+    const int k0 = t * BK;
+    stage_plane<BM, NW>(st_qhi, st_ldk, m0, k0, base, lw, st_loff);
+    stage_plane<BN, NW>(st_ghi, st_ldk, n0, k0, base + A_BYTES, lw, st_loff);
     if (MODE == CMVE_SIM_BF16X3) {
-      stage_plane<BM, NW, KB>(st_qlo, st_ldk, m0, k0, base + A_BYTES + B_BYTES, lw, st_loff);
-      stage_plane<BN, NW, KB>(st_glo, st_ldk, n0, k0, base + 2 * A_BYTES + B_BYTES, lw, st_loff);
+      stage_plane<BM, NW>(st_qlo, st_ldk, m0, k0, base + A_BYTES + B_BYTES, lw, st_loff);
+      stage_plane<BN, NW>(st_glo, st_ldk, n0, k0, base + 2 * A_BYTES + B_BYTES, lw, st_loff);
     }
   };
 
@@ -744,13 +575,6 @@ void sim_kernel(
   };
 
   auto epilogue = [&]() {
-  #ifdef CMVE_DBG_NOEPI  // diagnostic build only: main loop without any epilogue (results are garbage)
-  #pragma unroll
-    for (int i = 0; i < TM; ++i)
-  #pragma unroll
-      for (int j = 0; j < TN; ++j) asm volatile("" ::"v"(acc[i][j]));
-    return;
-  #endif
     // ---------------- epilogues ----------------
     // accumulator element (i, j, r): row = m0 + wr*TM*16 + i*16 + (lane>>4)*4 + r,
     //                                col = n0 + wc*TN*16 + j*16 + (lane&15)
@@ -926,8 +750,6 @@ void sim_kernel(
           // followed by recomputing the bits cost more than writing them directly (16,384 x 131,072 rank
           // pass 3.92 -> 3.83 ms, tools/ab4.sh)
           uint32_t u = 0u;
-#ifndef CMVE_EPI_C
-#if CMVE_EPI_BOTH_ASM
           if constexpr (DR && DC && TN == 4) {  // both directions (K14 evaluations): hand-scheduled per column block
             uint32_t ur = 0u, uc = 0u;
   #pragma unroll
@@ -941,17 +763,6 @@ void sim_kernel(
             und[i] = ur | (uc << 16);
             continue;
           }
-#endif
-#if CMVE_EPI_T2V_DBL
-          if constexpr (DR && !DC && TN == 4) {  // t2v (the gallery shape): hand-scheduled per column block
-  #pragma unroll
-            for (int j = TN - 1; j >= 0; --j)
-              col4_count_bits(acc[i][j][3], acc[i][j][2], acc[i][j][1], acc[i][j][0], rhi, rlo, c3, c2, c1, c0, u);
-            row_reduce(i, c0 | (c1 << 8) | (c2 << 16) | (c3 << 24));
-            und[i] = u;
-            continue;
-          }
-#endif
           if constexpr (DR && !DC && TN == 4) {  // t2v (the bench / gallery shape): hand-scheduled per row
             c0 = row4_count_bits<0>(acc[i][0][0], acc[i][1][0], acc[i][2][0], acc[i][3][0], rhi[0], rlo[0], u);
             c1 = row4_count_bits<1>(acc[i][0][1], acc[i][1][1], acc[i][2][1], acc[i][3][1], rhi[1], rlo[1], u);
@@ -961,7 +772,7 @@ void sim_kernel(
             und[i] = u;
             continue;
           }
-#endif
+          // (column counts only: the compiler's form)
   #pragma unroll
           for (int j = 0; j < TN; ++j) {
             const f32x4_t sc = acc[i][j];
@@ -1092,19 +903,14 @@ void sim_kernel(
               }
             }
           }
-#ifdef CMVE_DBG_NOINLFIX  // diagnostic build only: no re-score (counts incomplete, results garbage)
-          listed = true;
-          ntot = 0;
-#endif
           if (listed) {
             CMVE_BAR_LDS();
             if (a.q_lo16) {
-              // level 2: each wave scores CMVE_L2_P listed pairs at once from the fp16 + bf16 residual planes
-              // (l16_scores) and decides every direction whose GT score lies outside s2 +- E2; a pair with a
+              // level 2: each wave scores its listed pairs from the fp16 + bf16 residual planes (l16_load /
+              // l16_partial, cmve_internal.h) and decides every direction whose GT score lies outside s2 +- E2; a pair with a
               // direction left undecided goes to the level-3 list (fp64 in the finish launch, off this kernel's
               // critical path), or -- the list full -- keeps those flags for the fp64 pass below (the wave owns its
               // entries: no other wave touches them)
-#if CMVE_L2_PIPE
               // software-pipelined: each wave scores one listed pair per step while the rows of its next pair are
               // already in flight (two pairs' rows in registers, as two pairs per round trip were; the same
               // arithmetic per pair, so the same bits)
@@ -1172,58 +978,6 @@ void sim_kernel(
                   p = pn;
                 }
               }
-#else
-              constexpr int RP = BATCH ? ((is_big_ring<BM, BN>() || NW == 4) ? CMVE_L2_P_BIG : CMVE_L2_P) : CMVE_L2_P_ONE;
-              for (int p0 = wave * RP; p0 < ntot; p0 += NWT * RP) {
-                int64_t qr[RP], gc[RP];
-                uint32_t ent[RP];
-#pragma unroll
-                for (int u = 0; u < RP; ++u) {
-                  ent[u] = p0 + u < ntot ? epi.list[p0 + u] : epi.list[p0];  // (a repeat: scored, not used)
-                  qr[u] = m0 + (ent[u] & 0xff);
-                  gc[u] = n0 + ((ent[u] >> 8) & 0xff);
-                }
-                // the pairs' row bounds are loaded with their plane rows (as a dependent load after the score
-                // they cost the re-score a second round trip)
-                float elq[RP], elg[RP];
-#pragma unroll
-                for (int u = 0; u < RP; ++u) {
-                  elq[u] = gld(a.q_el + qr[u]);
-                  elg[u] = gld(a.g_el + gc[u]);
-                }
-                double s2[RP];
-                l16_scores<RP>(a, qr, gc, lane, s2);
-                if (lane == 0) {
-#pragma unroll
-                  for (int u = 0; u < RP; ++u) {
-                    if (p0 + u >= ntot) break;
-                    const double eq = (double)elq[u], eg = (double)elg[u];
-                    const double E2 = eq + (1.0 + eq) * eg + 2e-12;
-                    uint32_t fl = (ent[u] >> 16) & 3u;
-                    const int lr = (int)(ent[u] & 0xff), lc = (int)((ent[u] >> 8) & 0xff);
-                    if (fl & 1u) {
-                      const double t = epi.sgt[lr];
-                      if (s2[u] - E2 > t) { lds_add_u32_async(&lds_rc[lr], 1); fl &= ~1u; }
-                      else if (s2[u] + E2 < t) fl &= ~1u;
-                    }
-                    if (fl & 2u) {
-                      const double t = epi.sgt[BM + lc];
-                      if (s2[u] - E2 > t) { lds_add_u32_async(&lds_cc[lc], 1); fl &= ~2u; }
-                      else if (s2[u] + E2 < t) fl &= ~2u;
-                    }
-                    if (fl && a.l3_count) {  // level 3: counted (a returning atomic: only these few pairs pay it),
-                      const unsigned slot = gadd(a.l3_count, 1u);  // listed for the finish (batches) or, with no
-                      if (a.l3 && slot < (unsigned)a.l3_cap) {     // list (one evaluation), re-scored right here
-                        gst(a.l3 + slot, (unsigned long long)qr[u] | ((unsigned long long)gc[u] << 31) |
-                                             ((unsigned long long)fl << 62));
-                        fl = 0u;
-                      }
-                    }
-                    epi.list[p0 + u] = (ent[u] & 0xffffu) | (fl << 16);
-                  }
-                }
-              }
-#endif
               CMVE_BAR_LDS();  // the level-2 flags are in LDS for every wave
             }
             auto rescore2 = [&](uint32_t e1, uint32_t e2, bool two) {
@@ -1264,8 +1018,7 @@ void sim_kernel(
             };
             // batches: one pair per wave at a time (64 registers of rows in flight, not 128), so that the kernel's
             // register count leaves room on each SIMD for a wave of the other stream's prep
-            constexpr bool FIX1 = BATCH && CMVE_BATCH_FIX1;
-            if constexpr (FIX1) {
+            if constexpr (BATCH) {
               for (int p = wave; p < ntot; p += NWT) {
                 const uint32_t e = epi.list[p];
                 if (!(e >> 16)) continue;  // decided at level 2
@@ -1331,10 +1084,6 @@ void sim_kernel(
         }
       }
       CMVE_STAMP(6);
-#ifdef CMVE_DBG_NOFLUSH  // diagnostic build only: no global flush of candidates / counts (results garbage)
-      for (int t = tid; t < BM + BN; t += NTT) lds_rc[t] = 0;
-      return;
-#endif
       CMVE_BAR_LDS();  // every wave's row / column count adds have landed in LDS
       for (int t = tid; t < BM + BN; t += NTT) {
         const int c = lds_rc[t];
@@ -1350,11 +1099,6 @@ void sim_kernel(
       const bool emit = total != 0u && !inl;  // (inline: re-scored above; the bucket count is the pair total)
       if (emit) {
         const unsigned long long w0 = __shfl(wbase, 0, 64);  // this wave's first slot in the bucket
-        // K14 with a fix-up launch (SimArgs::ovf_inline): a wave whose pairs do not all fit its bucket re-scores
-        // them here in fp64 (into the global counts, after the flush) and leaves null entries in the slots it
-        // reserved -- an evaluation never overflows (tiles dense with undecided pairs: near-duplicate rows)
-        bool rescue = false;
-        if constexpr (INL) rescue = a.ovf_inline && w0 + total > (unsigned long long)a.cap_b;
         unsigned long long slot = w0 + excl;
         unsigned long long* dst = a.cand + (size_t)bucket * a.cap_b;
   #pragma unroll
@@ -1376,45 +1120,11 @@ void sim_kernel(
                        (unsigned long long)(cbase + (bit >> 2) * 16);
             } else {
               const unsigned long long flags = ((und[i] >> bit) & 1u) | (((und[i] >> (16 + bit)) & 1u) << 1);
-              packed = rescue ? 0ull
-                              : (unsigned long long)(rbase + i * 16 + (bit & 3)) |
-                                    ((unsigned long long)(cbase + (bit >> 2) * 16) << 31) | (flags << 62);
+              packed = (unsigned long long)(rbase + i * 16 + (bit & 3)) |
+                       ((unsigned long long)(cbase + (bit >> 2) * 16) << 31) | (flags << 62);
             }
             if ((long long)slot < a.cap_b) gst(dst + slot, packed);
             ++slot;
-          }
-        }
-        if constexpr (INL) {
-          if (rescue) {  // (wave-uniform) the wave's pairs one at a time: fixup_walk's arithmetic, global counts
-#pragma unroll
-            for (int i = 0; i < TM; ++i) {
-              uint32_t bits = (und[i] | (und[i] >> 16)) & 0xffffu;
-              unsigned long long mm;
-              while ((mm = __builtin_amdgcn_ballot_w64(bits != 0u))) {
-                const int src = (int)__builtin_ctzll(mm);
-                const uint32_t sb = (uint32_t)__builtin_amdgcn_readlane((int)bits, src);
-                const uint32_t su = (uint32_t)__builtin_amdgcn_readlane((int)und[i], src);
-                const int bit = __builtin_ctz(sb);
-                if (lane == src) bits &= bits - 1u;
-                const int64_t row = m0 + wr * (TM * 16) + (src >> 4) * 4 + i * 16 + (bit & 3);
-                const int64_t col = n0 + wc * (TN * 16) + (src & 15) + (bit >> 2) * 16;
-                const double inva = gld(a.q_inv + row), invb = gld(a.g_inv + col);
-                double sc;
-                if (a.q_f64) {
-                  const double* x = (const double*)a.q_raw + row * a.q_ld;
-                  sc = a.g_f64 ? wave_cos64(x, (const double*)a.g_raw + col * a.g_ld, inva, invb, a.d, lane)
-                               : wave_cos64(x, (const float*)a.g_raw + col * a.g_ld, inva, invb, a.d, lane);
-                } else {
-                  const float* x = (const float*)a.q_raw + row * a.q_ld;
-                  sc = a.g_f64 ? wave_cos64(x, (const double*)a.g_raw + col * a.g_ld, inva, invb, a.d, lane)
-                               : wave_cos64(x, (const float*)a.g_raw + col * a.g_ld, inva, invb, a.d, lane);
-                }
-                if (lane == 0) {
-                  if (((su >> bit) & 1u) && sc > gld(a.row_sgt + row)) gadd(a.row_cnt + row, 1);
-                  if (((su >> (16 + bit)) & 1u) && sc > gld(a.col_sgt + col)) gadd(a.col_cnt + col, 1);
-                }
-              }
-            }
           }
         }
       }
@@ -1456,9 +1166,6 @@ void sim_kernel(
     // global chunk (l&7) ^ (row&7)
     const int voff = (lane >> 3) * ldk_b + (((lane & 7) ^ (lane >> 3)) << 4);
     auto stage_op = [&](const __amdgpu_buffer_rsrc_t& rhi, int t, int plane_off) {
-#ifdef CMVE_DBG_NOLOAD  // diagnostic build only: MFMA + LDS-read ceiling (results are garbage)
-      return;
-#endif
       char* dst = smem + (t & 1) * STAGE_BYTES + plane_off;
       bool alo = false, blo = false;
       int kt = t;
@@ -1495,12 +1202,6 @@ void sim_kernel(
       }
     };
     auto quadrant = [&](int qm, int qn, const s16x8_t (&fb)[2][2]) {
-#ifdef CMVE_DBG_NOMFMA  // diagnostic build only: staging + LDS-read floor (results are garbage)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) asm volatile("" ::"v"(fa[i][0]), "v"(fa[i][1]));
-#pragma unroll
-      for (int j = 0; j < 2; ++j) asm volatile("" ::"v"(fb[j][0]), "v"(fb[j][1]));
-#else
       __builtin_amdgcn_s_setprio(1);
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks)
@@ -1510,7 +1211,6 @@ void sim_kernel(
           for (int j = 0; j < 2; ++j)
             acc[qm * 4 + i][qn * 2 + j] = mfma<MODE>(fa[i][ks], fb[j][ks], acc[qm * 4 + i][qn * 2 + j]);
       __builtin_amdgcn_s_setprio(0);
-#endif
     };
 #define CMVE_BAR()                                  \
   __builtin_amdgcn_sched_barrier(0);                \
@@ -1599,27 +1299,13 @@ void sim_kernel(
 #undef CMVE_BAR
   } else if constexpr (RING) {
   // ---- ring of NS stages (G64): K-tiles t+1 .. t+NS-2 stay in flight while K-tile t is consumed ----
-  constexpr int RPI = 64 / (KB / 8);  // rows per staging wave-instruction (1 KiB)
+  constexpr int RPI = 64 / (BK / 8);  // rows per staging wave-instruction (1 KiB)
   constexpr int LPS = (BM / RPI / NW + BN / RPI / NW) * (MODE == CMVE_SIM_BF16X3 ? 2 : 1);  // loads / stage / wave
-  constexpr int KS = KB / 32;  // 32-deep MFMA steps per K-tile
-#ifndef CMVE_RING_KSPLIT
-#define CMVE_RING_KSPLIT 0
-#endif
-  // the batch rings with CMVE_RING_KSPLIT: fragments and MFMAs one 32-deep step at a time
-  constexpr bool KSPLIT = CMVE_RING_KSPLIT && BATCH && MODE != CMVE_SIM_BF16X3 && KS > 1;
+  constexpr int KS = BK / 32;  // 32-deep MFMA steps per K-tile
   static_assert(LPS * (NS - 2) <= 63, "vmcnt immediate");
-  const int nk0 = a.nk0 * (BK / KB);  // (a.nk0: 64-deep K-tiles; d_pad % 64 == 0)
   // KG = 2: this wave's group streams K-tiles [kt0, kt0 + nkg) (the host launches it only for nk0 % 2 == 0)
-  const int nkg = nk0 / KG, kt0 = group * nkg;
-  // the K-tile streamed at step t: in order, or (CMVE_RING_KROT study) rotated per tile, so the tiles of an XCD that
-  // run in lockstep read different K-slices of their shared panels at any moment (each tile's own sum in another
-  // order: the scores move within the error bound, the ranks do not)
-#if CMVE_RING_KROT
-  const int krot = BATCH ? (int)(((unsigned)(m0 / BM) * 3u + (unsigned)(n0 / BN) * 5u) % (unsigned)max(nkg, 1)) : 0;
-  auto kt_of = [&](int t) { const int u = t + krot; return kt0 + (u >= nkg ? u - nkg : u); };
-#else
-  auto kt_of = [&](int t) { return kt0 + t; };
-#endif
+  const int nkg = a.nk0 / KG, kt0 = group * nkg;
+  auto kt_of = [&](int t) { return kt0 + t; };  // the K-tile streamed at step t
   // K14: the other set's err_max shards as VECTOR loads, one shard per lane, issued before the first
   // K-tiles (the oldest loads: retired by the first ring wait) and folded after the main loop -- as scalar
   // loads their round trip held the prologue (~2.5 us to the first K-tile in the stamps)
@@ -1631,38 +1317,7 @@ void sim_kernel(
       emg = gld(a.g_emax + lane);
     }
   }
-  // CMVE_RING_VGPR_STAGE (the batch ring): K-tiles staged through registers -- global_load_dwordx4 of the same 16 B per
-  // lane an LDS-DMA piece moves, ds_write_b128 into the same LDS image -- one K-tile ahead in registers, one in LDS
-  // (an LDS-DMA piece costs its wave ~100-185 issue cycles inside a phase of MFMAs and fragment reads,
-  // MI355X_MICROARCH.md: 8 per wave per K-tile, the main loop's largest single cost)
-  constexpr bool RSTG = CMVE_RING_VGPR_STAGE && BATCH && MODE != CMVE_SIM_BF16X3 && KG == 1 && NS == 2;
-  constexpr int PWA = RSTG ? BM / RPI / NW : 1, PWB = RSTG ? BN / RPI / NW : 1;
-  cmve_u32x4 stg_a[PWA], stg_b[PWB];
-  auto rload = [&](int t) {
-    const int k0 = t * KB;
-    const char* ba = (const char*)(st_qhi + ((int64_t)m0 + lw * PWA * RPI) * st_ldk + k0);
-    const char* bb = (const char*)(st_ghi + ((int64_t)n0 + lw * PWB * RPI) * st_ldk + k0);
-#pragma unroll
-    for (int it = 0; it < PWA; ++it) stg_a[it] = gld((const cmve_u32x4*)(ba + (int64_t)it * RPI * st_ldk * 2 + st_loff));
-#pragma unroll
-    for (int it = 0; it < PWB; ++it) stg_b[it] = gld((const cmve_u32x4*)(bb + (int64_t)it * RPI * st_ldk * 2 + st_loff));
-  };
-  auto rstore = [&](int s) {
-    char* base = smem + s * STAGE_BYTES;
-#pragma unroll
-    for (int it = 0; it < PWA; ++it) *(cmve_u32x4*)(base + (lw * PWA + it) * 1024 + lane * 16) = stg_a[it];
-#pragma unroll
-    for (int it = 0; it < PWB; ++it) *(cmve_u32x4*)(base + A_BYTES + (lw * PWB + it) * 1024 + lane * 16) = stg_b[it];
-  };
-  if constexpr (RSTG) {
-    if (nkg > 0) {
-      rload(kt0);
-      rstore(0);
-    }
-    if (nkg > 1) rload(kt0 + 1);
-  } else {
-    for (int t = 0; t < NS - 1 && t < nkg; ++t) stage(kt_of(t), t);
-  }
+  for (int t = 0; t < NS - 1 && t < nkg; ++t) stage(kt_of(t), t);
   // K14 thresholds: the GT score / bound loads are issued behind the first K-tiles' loads and the rule
   // applied after the main loop (using them at once would wait vmcnt(0), i.e. for every staged K-tile)
   double sgt_raw = 0.0;
@@ -1678,66 +1333,33 @@ void sim_kernel(
     }
   }
   CMVE_STAMP(1);
-#ifdef CMVE_STUDY_LOOP_PRIO  // study: the batch ring's main loop at a raised wave priority (the co-resident preps' waves
-  if constexpr (BATCH) __builtin_amdgcn_s_setprio(CMVE_STUDY_LOOP_PRIO);  // stay at 0)
-#endif
   for (int t = 0; t < nkg; ++t) {
     // K-tile t has landed once at most LPS * (newer stages in flight) loads of this wave are outstanding
-    const int newer = RSTG ? -1 : min(NS - 2, nkg - 1 - t);  // (RSTG: K-tile t is in LDS, its loads long waited for)
-    switch (newer) {
-      case -1: break;
-#define CMVE_RING_WAIT(k) \
+    switch (min(NS - 2, nkg - 1 - t)) {
+      case -1: break;  // (never taken, t < nkg; without it the compiler lays the loop's waits out differently)
+#define CMVE_VM_WAIT(k) \
   case k: asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LPS * (k)) : "memory"); break;
-      CMVE_RING_WAIT(0) CMVE_RING_WAIT(1) CMVE_RING_WAIT(2) CMVE_RING_WAIT(3) CMVE_RING_WAIT(4) CMVE_RING_WAIT(5)
-      CMVE_RING_WAIT(6)
-#undef CMVE_RING_WAIT
+      CMVE_VM_WAIT(0) CMVE_VM_WAIT(1) CMVE_VM_WAIT(2) CMVE_VM_WAIT(3) CMVE_VM_WAIT(4) CMVE_VM_WAIT(5)
+      CMVE_VM_WAIT(6)
+#undef CMVE_VM_WAIT
       default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
     // every wave's share of K-tile t is in LDS, every wave is done with K-tile t-1 (an LDS-only barrier:
     // __syncthreads would drain vmcnt, i.e. the ring)
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#if CMVE_RING_READS_FIRST
-    // the same drain as a builtin the compiler's wait-count pass sees: with a scalar load it believes outstanding
-    // (the asm above is opaque to it) every LDS-read wait below would be lgkmcnt(0) instead of counted
-    __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0); vmcnt / expcnt left at their maxima (gfx9 encoding)
-#endif
-    if constexpr (!RSTG)
-      if (t + NS - 1 < nkg) stage(kt_of(t + NS - 1), (t + NS - 1) % NS);  // refills K-tile t-1's buffer
+    if (t + NS - 1 < nkg) stage(kt_of(t + NS - 1), (t + NS - 1) % NS);  // refills K-tile t-1's buffer
     const char* base = smem + (group * NS + t % NS) * STAGE_BYTES;
     const char* pA = base;
     const char* pB = base + A_BYTES;
-    if constexpr (KSPLIT) {
-      // one 32-deep step at a time: its fragments, then its MFMAs (half the fragment registers live)
-#pragma unroll
-      for (int ks = 0; ks < KS; ++ks) {
-        const int chunk = ks * 4 + (lane >> 4);
-        s16x8_t fa1[TM], fb1[TN];
-#pragma unroll
-        for (int j = 0; j < TN; ++j) fb1[j] = read_frag<KB>(pB, wc * (TN * 16) + j * 16 + frow, chunk);
-#pragma unroll
-        for (int i = 0; i < TM; ++i) fa1[i] = read_frag<KB>(pA, wr * (TM * 16) + i * 16 + frow, chunk);
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-          for (int j = 0; j < TN; ++j) acc[i][j] = mfma<MODE>(fa1[i], fb1[j], acc[i][j]);
-      }
-      continue;
-    }
     s16x8_t fa[KS][TM], fb[KS][TN];
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
       const int chunk = ks * 4 + (lane >> 4);
 #pragma unroll
-      for (int j = 0; j < TN; ++j) fb[ks][j] = read_frag<KB>(pB, wc * (TN * 16) + j * 16 + frow, chunk);
+      for (int j = 0; j < TN; ++j) fb[ks][j] = read_frag(pB, wc * (TN * 16) + j * 16 + frow, chunk);
 #pragma unroll
-      for (int i = 0; i < TM; ++i) fa[ks][i] = read_frag<KB>(pA, wr * (TM * 16) + i * 16 + frow, chunk);
+      for (int i = 0; i < TM; ++i) fa[ks][i] = read_frag(pA, wr * (TM * 16) + i * 16 + frow, chunk);
     }
-#if CMVE_RING_READS_FIRST
-    // every fragment read of the K-tile issued before its first MFMA: each 32-deep step's MFMAs wait (counted
-    // lgkmcnt) only for their own reads, the later step's reads land under the earlier step's MFMAs (left to the
-    // scheduler, the reads went out in groups of 6 and 2, each drained by lgkmcnt(0) right before its MFMAs)
-    __builtin_amdgcn_sched_barrier(0);
-#endif
     if constexpr (MODE == CMVE_SIM_BF16X3) {  // pairs (lo, hi) then (hi, lo): plane_of's order
       const char* pAl = base + A_BYTES + B_BYTES;
       const char* pBl = base + 2 * A_BYTES + B_BYTES;
@@ -1746,7 +1368,7 @@ void sim_kernel(
       for (int ks = 0; ks < KS; ++ks) {
         const int chunk = ks * 4 + (lane >> 4);
 #pragma unroll
-        for (int i = 0; i < TM; ++i) lx[ks][i] = read_frag<KB>(pAl, wr * (TM * 16) + i * 16 + frow, chunk);
+        for (int i = 0; i < TM; ++i) lx[ks][i] = read_frag(pAl, wr * (TM * 16) + i * 16 + frow, chunk);
       }
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks)
@@ -1758,7 +1380,7 @@ void sim_kernel(
       for (int ks = 0; ks < KS; ++ks) {
         const int chunk = ks * 4 + (lane >> 4);
 #pragma unroll
-        for (int j = 0; j < TN; ++j) lx[ks][j] = read_frag<KB>(pBl, wc * (TN * 16) + j * 16 + frow, chunk);
+        for (int j = 0; j < TN; ++j) lx[ks][j] = read_frag(pBl, wc * (TN * 16) + j * 16 + frow, chunk);
       }
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks)
@@ -1767,32 +1389,13 @@ void sim_kernel(
 #pragma unroll
           for (int j = 0; j < TN; ++j) acc[i][j] = mfma<MODE>(fa[ks][i], lx[ks][j], acc[i][j]);
     }
-#ifdef CMVE_DBG_NOMFMA  // diagnostic build only: the fragments are read, no MFMA issued (results garbage)
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-#pragma unroll
-      for (int i = 0; i < TM; ++i) asm volatile("" ::"v"(fa[ks][i]));
-#pragma unroll
-      for (int j = 0; j < TN; ++j) asm volatile("" ::"v"(fb[ks][j]));
-    }
-#else
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks)
 #pragma unroll
       for (int i = 0; i < TM; ++i)
 #pragma unroll
         for (int j = 0; j < TN; ++j) acc[i][j] = mfma<MODE>(fa[ks][i], fb[ks][j], acc[i][j]);
-#endif
-    if constexpr (RSTG) {  // K-tile t+1 into the other buffer (read by every wave before the barrier above), t+2 loaded
-      if (t + 1 < nkg) {
-        rstore((t + 1) % NS);
-        if (t + 2 < nkg) rload(kt0 + t + 2);
-      }
-    }
   }
-#ifdef CMVE_STUDY_LOOP_PRIO
-  if constexpr (BATCH) __builtin_amdgcn_s_setprio(0);
-#endif
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (the threshold loads, if any are still out)
   if constexpr (epi_thr(EPI)) {
     if (a.thr_gt) {  // fold the shards: a wave max (every lane the same bits)
@@ -1862,15 +1465,6 @@ void sim_kernel(
       for (int i = 0; i < TM; ++i) fa[ks][i] = read_frag(pA, wr * (TM * 16) + i * 16 + frow, chunk);
     }
     __builtin_amdgcn_sched_barrier(0);
-#ifdef CMVE_DBG_NOMFMA
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-#pragma unroll
-      for (int i = 0; i < TM; ++i) asm volatile("" ::"v"(fa[ks][i]));
-#pragma unroll
-      for (int j = 0; j < TN; ++j) asm volatile("" ::"v"(fb[ks][j]));
-    }
-#else
     if constexpr (MODE == CMVE_SIM_BF16X3) {  // pairs (lo, hi) then (hi, lo): plane_of's order
       const char* pAl = base + A_BYTES + B_BYTES;
       const char* pBl = base + 2 * A_BYTES + B_BYTES;
@@ -1908,7 +1502,6 @@ void sim_kernel(
 #pragma unroll
         for (int j = 0; j < TN; ++j) acc[i][j] = mfma<MODE>(fa[ks][i], fb[ks][j], acc[i][j]);
     __builtin_amdgcn_s_setprio(0);
-#endif
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
   }
@@ -1928,7 +1521,7 @@ template <int MODE, int EPI, int WM, int WN, int TM, bool PHASED, int KG = 1>
 static int launch_geo(SimArgs a, int64_t nq_pad, int64_t ng_pad, hipStream_t stream) {
   using G = Geo<WM, WN, TM>;
   // + the static epilogue scratch (EpiLds); KG = 2: a ring per K group
-  const size_t lds = ring_lds_bytes<MODE, G::BM, G::BN, PHASED, G::NW>() * KG;
+  const size_t lds = ring_lds_bytes<MODE, G::BM, G::BN, PHASED>() * KG;
   // once per instantiation; function-local static init is thread-safe (one host thread per shard / GPU)
   static const hipError_t attr_err = hipFuncSetAttribute(
       (const void*)sim_kernel<MODE, EPI, WM, WN, TM, PHASED, false, KG>, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -1945,48 +1538,33 @@ static int launch_geo(SimArgs a, int64_t nq_pad, int64_t ng_pad, hipStream_t str
   return check_launch("sim_kernel");
 }
 
-// G256 (phased schedule) for bf16/fp16 when both sides tile by 256 and the grid has >= 512
-// tiles; G64 below 128 tiles of 128^2; else G128 (2-stage).  Study builds (make study DEFS=-DCMVE_SIM_GEO=128 / 2562)
-// force G128 / the 2-stage G256 loop; the product build reads no environment.
-static constexpr int sim_geo_force() { return CMVE_SIM_GEO; }
-
-// true when launch_sim takes the persistent phased G256 kernel (which reads explicit thresholds only)
-static bool sim_uses_phased(int mode, int64_t nq_pad, int64_t ng_pad) {
-  const int force = sim_geo_force();
-  if (force == 128 || nq_pad % 256 || ng_pad % 256 || (nq_pad / 256) * (ng_pad / 256) < 512) return false;
-  return !(force == 2562 && mode != CMVE_SIM_BF16X3);
+// G256 (phased schedule) when both sides tile by 256 and the grid has >= 512 tiles; G64 below 128 tiles of 128^2;
+// else G128 (2-stage)
+static bool sim_uses_phased(int64_t nq_pad, int64_t ng_pad) {  // (the persistent kernel reads explicit thresholds only)
+  return nq_pad % 256 == 0 && ng_pad % 256 == 0 && (nq_pad / 256) * (ng_pad / 256) >= 512;
 }
 
 // true when launch_sim takes the G64 ring kernel (64 x 64 tiles: problems of fewer than 128 tiles of 128^2)
 static bool sim_uses_g64(int64_t nq_pad, int64_t ng_pad) {
-  return sim_geo_force() != 128 && !(nq_pad % 256 == 0 && ng_pad % 256 == 0 && (nq_pad / 256) * (ng_pad / 256) >= 512) &&
-         (nq_pad / 128) * (ng_pad / 128) < 128 && nq_pad % 64 == 0 && ng_pad % 64 == 0;
+  return !sim_uses_phased(nq_pad, ng_pad) && (nq_pad / 128) * (ng_pad / 128) < 128 && nq_pad % 64 == 0 &&
+         ng_pad % 64 == 0;
 }
 
 template <int MODE, int EPI>
 static int launch_sim(const SimArgs& a, int64_t nq_pad, int64_t ng_pad, hipStream_t stream) {
-  const int force = sim_geo_force();
-  if (force != 128 && nq_pad % 256 == 0 && ng_pad % 256 == 0 && (nq_pad / 256) * (ng_pad / 256) >= 512) {
-    if constexpr (MODE != CMVE_SIM_BF16X3)  // (split-bf16 takes the phased loop only)
-      if (force == 2562) return launch_geo<MODE, EPI, 2, 4, 8, false>(a, nq_pad, ng_pad, stream);  // 2-stage BK64
-    return launch_geo<MODE, EPI, 2, 4, 8, true>(a, nq_pad, ng_pad, stream);
-  }
+  if (sim_uses_phased(nq_pad, ng_pad)) return launch_geo<MODE, EPI, 2, 4, 8, true>(a, nq_pad, ng_pad, stream);
   // G64 (4 waves of 16 x 64, 64 x 64 tiles) when the 128^2 grid would leave most CUs idle (a 1k x 1k
   // problem: 64 tiles of 128^2 vs 256 of 64^2); every output element sees the same MFMA sequence in every
   // geometry.  4 waves rather than 2 of 32 x 64: the rank epilogue's scoring runs on all 4 SIMDs (2.0 ->
   // 1.2 us per tile in the K14 stamps); the main loop stays at ~6.3 us (the CU's L2 -> LDS fill of 256 KiB)
-  if (force != 128 && (nq_pad / 128) * (ng_pad / 128) < 128 && nq_pad % 64 == 0 && ng_pad % 64 == 0) {
-#ifndef CMVE_G64_2W
+  if (sim_uses_g64(nq_pad, ng_pad)) {
     // the rank GEMM at this size (one K14 evaluation, cmve_rank_mfma of a 1k x 1k problem): its 256 tiles are one per
     // CU, each a latency chain of 16 K-tiles -- two K groups of 4 waves halve the chain (and share the K14 level-2
     // re-score): one evaluation 31.6 -> 29.2 us back to back (profiles/r06_ab_g64_kg2.txt).  Every G64 rank launch
-    // takes it, so the separate-launch path and cmve_eval_ranks still see the same scores (CMVE_G64_KG = 1: off)
-    if constexpr (EPI == EPI_RANK && MODE != CMVE_SIM_BF16X3 && CMVE_G64_KG == 2)
+    // takes it, so the separate-launch path and cmve_eval_ranks still see the same scores
+    if constexpr (EPI == EPI_RANK && MODE != CMVE_SIM_BF16X3)
       if (a.nk0 >= 2 && a.nk0 % 2 == 0) return launch_geo<MODE, EPI, 4, 1, 1, false, 2>(a, nq_pad, ng_pad, stream);
     return launch_geo<MODE, EPI, 4, 1, 1, false>(a, nq_pad, ng_pad, stream);
-#else
-    return launch_geo<MODE, EPI, 2, 1, 2, false>(a, nq_pad, ng_pad, stream);
-#endif
   }
   return launch_geo<MODE, EPI, 2, 2, 4, false>(a, nq_pad, ng_pad, stream);
 }
@@ -2431,7 +2009,6 @@ struct EvalPlan {
   SimArgs a;
   int qf, gf;
   bool paired, inline_fix;
-  bool fix_launch = false;  // (inline_fix sizes) the GEMM lists its undecided pairs for a fix-up launch (level 2 + fp64)
 };
 
 static int eval_prepare(cmve_rows_t* q, cmve_rows_t* g, int32_t mode_flags, const int64_t* row_off,
@@ -2491,14 +2068,13 @@ static int eval_prepare(cmve_rows_t* q, cmve_rows_t* g, int32_t mode_flags, cons
   c.cap_b = l.cap_b;
   c.cand = cand;
   c.stats = out;
-  constexpr int dbg = CMVE_EVAL_DBG;  // kernel studies only (a study build)
-  c.dbg = dbg;
+  constexpr bool stamps = (CMVE_EVAL_DBG & 128) != 0;  // kernel studies only (a study build)
   static unsigned long long* stamp_buf = nullptr;
-  if ((dbg & 128) && !stamp_buf) {
+  if (stamps && !stamp_buf) {
     CMVE_HIP(hipMalloc(&stamp_buf, sizeof(unsigned long long) * 4 * 1024 * 8));
     CMVE_HIP(hipMemset(stamp_buf, 0, sizeof(unsigned long long) * 4 * 1024 * 8));
   }
-  c.stamps = (dbg & 128) ? stamp_buf : nullptr;
+  c.stamps = stamps ? stamp_buf : nullptr;
   g_eval_stamps = c.stamps;
   P.qf = q->raw_dtype == CMVE_F64;
   P.gf = g->raw_dtype == CMVE_F64;
@@ -2511,7 +2087,7 @@ static int eval_prepare(cmve_rows_t* q, cmve_rows_t* g, int32_t mode_flags, cons
   a = make_args(q, g, mode);
   // thresholds derived in the GEMM from the prep's GT scores and per-row bounds (row_hi / col_hi only
   // mark the directions that are on)
-  a.thr_gt = !sim_uses_phased(mode, q->n_pad, g->n_pad);
+  a.thr_gt = !sim_uses_phased(q->n_pad, g->n_pad);
   a.q_err = mode_err(q, mode);
   a.g_err = mode_err(g, mode);
   a.q_emax = c.emax + (0 * 3 + mode_slot(mode)) * cmve::EMAX_SHARDS;
@@ -2541,22 +2117,13 @@ static int eval_prepare(cmve_rows_t* q, cmve_rows_t* g, int32_t mode_flags, cons
   // G64 (1k-A scale): the rank GEMM re-scores its own undecided pairs (no list, no fix-up launch)
   P.inline_fix = a.thr_gt && sim_uses_g64(q->n_pad, g->n_pad);
   // level-2 re-score from the fp16 + bf16 residual planes: the F16 mode whose prep runs the register path (the
-  // only one that writes lo16: 16-B row pieces, d_pad <= 1024, both sides).  Two forms: (a) inline (the default)
-  // -- level 2 inside the rank GEMM, level 3 deferred to the finish through the workspace's list; (b) the fix-up
-  // launch (CMVE_EVAL_INLINE_L2=0, kernel studies) -- the rank GEMM only lists its undecided pairs and eval_fix
-  // re-scores them, two pairs per wave.  Measured (round 4, tools/ab_env.sh, batches of 8): (b) takes the round
-  // trips out of the GEMM (38 -> 27 us) but its own launch costs 27 us -- its gathers miss the L2 the GEMM's
-  // tiles had just filled -- and a single evaluation pays a launch boundary (b2b 35.0 vs 35.9 us).
-  // Study builds: CMVE_EVAL_INLINE_L2=0 (form b), CMVE_EVAL_NO_L2=1 (every band pair in fp64 inside the GEMM)
-  constexpr bool no_l2 = CMVE_EVAL_NO_L2 != 0;
-  constexpr bool inline_l2 = CMVE_EVAL_INLINE_L2 != 0;
-  // level 3 of ONE evaluation (cmve_eval_ranks, its graphs): re-scored inside the rank GEMM (its ~4 pairs cost the
-  // GEMM ~0.7 us and spare the finish its fp64 round trip, 5.2 -> 4.4 us: 32.5 -> 31.4 us back to back); batches list
-  // them for the finish (in a chained run it rides in the next prep launch).  Both count them (out[12]).
-  // Study builds: CMVE_EVAL_L3_LIST=1, the single evaluation lists them too
-  const bool l3_inline = !batch && CMVE_EVAL_L3_LIST == 0;
-  const bool l2 = P.inline_fix && mode == CMVE_SIM_F16 && P.sq.vec && P.sg.vec && q->d_pad <= 1024 && !no_l2;
-  P.fix_launch = l2 && !inline_l2;
+  // only one that writes lo16: 16-B row pieces, d_pad <= 1024, both sides).  Level 2 runs inside the rank GEMM, which
+  // counts the pairs it leaves for level 3 (out[12]).  ONE evaluation (cmve_eval_ranks, its graphs) re-scores those
+  // in the GEMM too (its ~4 pairs cost the GEMM ~0.7 us and spare the finish its fp64 round trip: 32.5 -> 31.4 us
+  // back to back); batches list them for the finish (in a chained run it rides in the next prep launch).  The forms
+  // that were measured and dropped (a fix-up launch, fp64 only, a listed level 3 for one evaluation):
+  // profiles/STUDIES.md
+  const bool l2 = P.inline_fix && mode == CMVE_SIM_F16 && P.sq.vec && P.sg.vec && q->d_pad <= 1024;
   if (l2) {
     P.sq.lo16 = (uint16_t*)(base + w.q_l16);
     P.sg.lo16 = (uint16_t*)(base + w.g_l16);
@@ -2566,20 +2133,15 @@ static int eval_prepare(cmve_rows_t* q, cmve_rows_t* g, int32_t mode_flags, cons
     a.g_lo16 = P.sg.lo16;
     a.q_el = P.sq.err_lo16;
     a.g_el = P.sg.err_lo16;
-    if (!P.fix_launch) {
-      c.l3_count = (unsigned*)(base + w.l3);
-      c.l3 = (uint64_t*)(base + w.l3 + 8);
-      c.l3_cap = l3_inline ? 0 : EVAL_L3_CAP;  // (0: the finish re-scores nothing; its count still reaches out[12])
-      a.l3_count = c.l3_count;
-      a.l3 = l3_inline ? nullptr : (unsigned long long*)c.l3;
-      a.l3_cap = c.l3_cap;
-    }
+    c.l3_count = (unsigned*)(base + w.l3);
+    c.l3 = (uint64_t*)(base + w.l3 + 8);
+    c.l3_cap = batch ? EVAL_L3_CAP : 0;  // (0: the finish re-scores nothing; its count still reaches out[12])
+    a.l3_count = c.l3_count;
+    a.l3 = batch ? (unsigned long long*)c.l3 : nullptr;
+    a.l3_cap = c.l3_cap;
   }
-  if (P.inline_fix) {
-    // fix_inline 1: the GEMM re-scores its undecided pairs; with the fix-up launch (2) it lists them and re-scores
-    // only the pairs of a wave whose bucket is full (SimArgs::ovf_inline): never an overflow either way
-    a.fix_inline = P.fix_launch ? 0 : 1;
-    a.ovf_inline = P.fix_launch ? 1 : 0;
+  if (P.inline_fix) {  // the GEMM re-scores its undecided pairs: no list, never an overflow
+    a.fix_inline = 1;
     a.q_f64 = P.qf;
     a.g_f64 = P.gf;
     a.q_raw = q->raw;
@@ -2589,7 +2151,7 @@ static int eval_prepare(cmve_rows_t* q, cmve_rows_t* g, int32_t mode_flags, cons
     a.d = q->d;
     a.q_inv = q->inv_norm;
     a.g_inv = g->inv_norm;
-    c.fix_inline = P.fix_launch ? 2 : 1;
+    c.fix_inline = 1;
   }
   a.dbg_stamps = c.stamps ? c.stamps + 3 * 1024 * 8 : nullptr;
   return CMVE_OK;
@@ -2640,10 +2202,10 @@ extern "C" int cmve_eval_ranks(cmve_handle_t h, cmve_rows_t* q, cmve_rows_t* g, 
   if (st) return st;
   if (ev) CMVE_HIP(hipEventRecord(ev[2], s));
   if (timing_slot >= 0) {
-    h->eval_no_fix[timing_slot] = P.inline_fix && !P.fix_launch;
+    h->eval_no_fix[timing_slot] = P.inline_fix;
     h->eval_chained[timing_slot] = false;
   }
-  if (!P.inline_fix || P.fix_launch) {
+  if (!P.inline_fix) {
     arm(2);
     st = cmve::launch_eval(P.sq, P.sg, P.c, P.qf, P.gf, 1, s);
     if (st) return st;
@@ -2666,7 +2228,6 @@ struct cmve_eval_batch {
   int bm = 64, bn = 64;           // the rank tile (batch_geo_bm / _bn)
   cmve::EvalSide sq0, sg0;        // the shapes (the launch grids)
   cmve::EvalCommon c0;            // (the first evaluation's: which prep kernel applies)
-  bool fix_launch = false;        // the rank GEMM lists its undecided pairs for a fix-up launch
   cmve::EvalItem* d_items = nullptr;
   SimArgs* d_args = nullptr;
   std::vector<void*> ws;          // the evaluations' workspaces and outputs: a chained run refuses a previous batch
@@ -2678,31 +2239,19 @@ struct cmve_eval_batch {
 
 // the batch's rank geometry: 128 x 128 tiles on 4 waves of 64 x 64 (a 2-stage ring of 32 KiB stages, two blocks of
 // ~73 KiB per CU, up to 256 VGPRs).  A batch's launch runs beside the other streams' launches (three batches in flight):
-// a rank-GEMM block of 4 waves at 152 VGPRs leaves each SIMD room for two waves of another stream's prep, which the
-// 8-wave form (round 4: 8 waves of 32 x 64 at 114 VGPRs, four waves per SIMD, 456 of 512 VGPRs) left none -- alone
-// it is slower (42 vs 36 us per batch of 8), beside the preps the headline gains 4-5% (1.18 vs 1.13e11 pairs/s,
-// round 5).  Split-bf16 (whose ring holds both planes) takes 128 x 64; kernel studies: CMVE_BATCH_GEO = 1288 (the
-// 8-wave 128 x 128), 256128 (256 x 128, one block per CU), 64 / 12864 (64 x 64 / 128 x 64).
-static constexpr int batch_geo_force() { return CMVE_BATCH_GEO; }
-static bool batch_geo_big(int64_t nq_pad, int64_t ng_pad, int mode) {
-  return batch_geo_force() == 256128 && nq_pad % 256 == 0 && ng_pad % 128 == 0 && mode != CMVE_SIM_BF16X3;
-}
-static int batch_geo_bm(int64_t nq_pad, int64_t ng_pad, int mode) {
-  if (batch_geo_big(nq_pad, ng_pad, mode)) return 256;
-  return (batch_geo_force() != 64 && nq_pad % 128 == 0) ? 128 : 64;
-}
+// a rank-GEMM block of 4 waves at 152 VGPRs leaves each SIMD room for two waves of another stream's prep.  Split-bf16
+// (whose ring holds both planes) and shapes that do not tile by 128 take 128 x 64 or 64 x 64 (the other tile shapes
+// that were measured: profiles/STUDIES.md)
+static int batch_geo_bm(int64_t nq_pad) { return nq_pad % 128 == 0 ? 128 : 64; }
 static int batch_geo_bn(int64_t nq_pad, int64_t ng_pad, int mode) {
-  const int f = batch_geo_force();
-  if (batch_geo_big(nq_pad, ng_pad, mode)) return 128;
-  return (f != 64 && f != 12864 && nq_pad % 128 == 0 && ng_pad % 128 == 0 && mode != CMVE_SIM_BF16X3) ? 128 : 64;
+  return (nq_pad % 128 == 0 && ng_pad % 128 == 0 && mode != CMVE_SIM_BF16X3) ? 128 : 64;
 }
 
-template <int MODE, int WN, int TM, int WM = 4>
+template <int MODE, int WM, int WN, int TM>
 static int launch_rank_batch(const SimArgs* tab, int count, int64_t nq_pad, int64_t ng_pad,
                              hipStream_t stream) {
   using G = Geo<WM, WN, TM>;
-  const size_t lds = (size_t)ring_stages<MODE, G::BM, G::BN, false, G::NW>() *
-                     stage_bytes<MODE, G::BM, G::BN, false, kernel_kb<MODE, G::BM, G::BN, false, G::NW, true>()>();
+  const size_t lds = ring_lds_bytes<MODE, G::BM, G::BN, false>();
   static const hipError_t attr_err = hipFuncSetAttribute(
       (const void*)sim_kernel<MODE, EPI_RANK, WM, WN, TM, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
       (int)lds);
@@ -2715,14 +2264,10 @@ static int launch_rank_batch(const SimArgs* tab, int count, int64_t nq_pad, int6
 template <int MODE>
 static int launch_rank_batch(const SimArgs* tab, int count, int64_t nq_pad, int64_t ng_pad,
                              int bm, int bn, hipStream_t stream) {
-  if constexpr (MODE != CMVE_SIM_BF16X3) {
-    if (bm == 256 && bn == 128) return launch_rank_batch<MODE, 2, 4>(tab, count, nq_pad, ng_pad, stream);
-    if (bm == 128 && bn == 128 && batch_geo_force() == 1288)  // (8 waves of 32 x 64: round 4's geometry)
-      return launch_rank_batch<MODE, 2, 2>(tab, count, nq_pad, ng_pad, stream);
-    if (bm == 128 && bn == 128) return launch_rank_batch<MODE, 2, 4, 2>(tab, count, nq_pad, ng_pad, stream);
-  }
-  return bm == 128 ? launch_rank_batch<MODE, 1, 2>(tab, count, nq_pad, ng_pad, stream)
-                   : launch_rank_batch<MODE, 1, 1>(tab, count, nq_pad, ng_pad, stream);
+  if constexpr (MODE != CMVE_SIM_BF16X3)
+    if (bm == 128 && bn == 128) return launch_rank_batch<MODE, 2, 2, 4>(tab, count, nq_pad, ng_pad, stream);
+  return bm == 128 ? launch_rank_batch<MODE, 4, 1, 2>(tab, count, nq_pad, ng_pad, stream)
+                   : launch_rank_batch<MODE, 4, 1, 1>(tab, count, nq_pad, ng_pad, stream);
 }
 
 extern "C" int cmve_eval_batch_create(int32_t count, cmve_rows_t* const* q, cmve_rows_t* const* g,
@@ -2745,7 +2290,7 @@ extern "C" int cmve_eval_batch_create(int32_t count, cmve_rows_t* const* q, cmve
                                "128^2, e.g. 1,000 x 1,000) with the inline fix-up");
     if (P.c.stamps) {  // kernel studies (CMVE_EVAL_DBG & 128): the first evaluation's prep / finish blocks, and
                        // every evaluation's rank tiles while the stamp buffer's 1,024 tile slots last
-      const int64_t per = (q[i]->n_pad / batch_geo_bm(q[i]->n_pad, g[i]->n_pad, mode_flags & 0xff)) *
+      const int64_t per = (q[i]->n_pad / batch_geo_bm(q[i]->n_pad)) *
                           (g[i]->n_pad / batch_geo_bn(q[i]->n_pad, g[i]->n_pad, mode_flags & 0xff));
       P.a.dbg_stamps = (i + 1) * per <= 1024 ? P.c.stamps + 3 * 1024 * 8 + (size_t)i * per * 8 : nullptr;
       if (i > 0) P.c.stamps = nullptr;
@@ -2757,12 +2302,12 @@ extern "C" int cmve_eval_batch_create(int32_t count, cmve_rows_t* const* q, cmve
                        g[i]->n_pad == g[0]->n_pad && q[i]->d == q[0]->d && q[i]->d_pad == q[0]->d_pad &&
                        P.qf == P0.qf && P.gf == P0.gf && P.paired == P0.paired,
                    "cmve_eval_batch_create: evaluation %d differs in shape / dtype / pairing from the first", i);
-      // the batch's launches pick their kernels (the specialised paired prep, the level-2 re-score, a fix-up launch)
+      // the batch's launches pick their kernels (the specialised paired prep, the level-2 re-score)
       // from the first evaluation's plan: every evaluation must plan the same way -- e.g. a row-strided input whose
       // rows are not 16-B aligned takes no register prep and no residual plane, which the specialised prep would
       // still read and write through
       CMVE_REQUIRE(P.sq.vec == P0.sq.vec && P.sg.vec == P0.sg.vec && (P.sq.lo16 != nullptr) == (P0.sq.lo16 != nullptr) &&
-                       (P.sg.lo16 != nullptr) == (P0.sg.lo16 != nullptr) && P.fix_launch == P0.fix_launch &&
+                       (P.sg.lo16 != nullptr) == (P0.sg.lo16 != nullptr) &&
                        (P.c.l3_count != nullptr) == (P0.c.l3_count != nullptr),
                    "cmve_eval_batch_create: evaluation %d's inputs take another path than the first's (row alignment "
                    "or stride: every evaluation of a batch needs 16-B aligned rows if the first has them)", i);
@@ -2772,7 +2317,7 @@ extern "C" int cmve_eval_batch_create(int32_t count, cmve_rows_t* const* q, cmve
     }
     items[(size_t)i] = cmve::EvalItem{P.sq, P.sg, P.c};
     // (launch_geo fills these for a single launch)
-    geo_fill(P.a, q[i]->n_pad, g[i]->n_pad, batch_geo_bm(q[i]->n_pad, g[i]->n_pad, mode_flags & 0xff),
+    geo_fill(P.a, q[i]->n_pad, g[i]->n_pad, batch_geo_bm(q[i]->n_pad),
              batch_geo_bn(q[i]->n_pad, g[i]->n_pad, mode_flags & 0xff));
     args[(size_t)i] = P.a;
   }
@@ -2784,12 +2329,11 @@ extern "C" int cmve_eval_batch_create(int32_t count, cmve_rows_t* const* q, cmve
   b->paired = P0.paired;
   b->nq_pad = q[0]->n_pad;
   b->ng_pad = g[0]->n_pad;
-  b->bm = batch_geo_bm(b->nq_pad, b->ng_pad, b->mode);
+  b->bm = batch_geo_bm(b->nq_pad);
   b->bn = batch_geo_bn(b->nq_pad, b->ng_pad, b->mode);
   b->sq0 = P0.sq;
   b->sg0 = P0.sg;
   b->c0 = P0.c;
-  b->fix_launch = P0.fix_launch;
   b->ws.assign(ws, ws + count);
   b->outs.assign(out, out + count);
   // the fused chained launch runs the specialised PAIRED prep: a batch whose lists are no one-to-one pairing (run()
@@ -2824,9 +2368,7 @@ static int eval_batch_run(cmve_handle_t h, cmve_eval_batch_t b, int32_t timing_s
     kev = h->eval_kev[timing_slot];
     for (int k = 0; k < 8; ++k)
       if (!kev[k]) CMVE_HIP(hipEventCreate(&kev[k]));
-    // (the CMVE_EVAL_FIX_CHAINED study's batch has no fix-up launch of its own either)
-    h->eval_no_fix[timing_slot] = !b->fix_launch || (chained && b->chainable && CMVE_EVAL_FIX_CHAINED &&
-                                                     b->c0.nb <= cmve::EVAL_FIXC_MAXB);
+    h->eval_no_fix[timing_slot] = true;  // (a batch re-scores in its rank GEMM)
     h->eval_chained[timing_slot] = chained;
   }
   auto arm = [&](int k) {
@@ -2835,9 +2377,6 @@ static int eval_batch_run(cmve_handle_t h, cmve_eval_batch_t b, int32_t timing_s
   hipStream_t s = h->stream;
   int st = CMVE_OK;
   const bool fused = chained && b->chainable;  // the prep and the previous batch's finish in one launch
-  // CMVE_EVAL_FIX_CHAINED study (with the fix-up launch form, CMVE_EVAL_INLINE_L2=0): the previous batch's fix-up
-  // rides in this prep launch instead of following its rank GEMM; its finish then follows as a launch of its own
-  const bool fchain = fused && CMVE_EVAL_FIX_CHAINED && b->fix_launch && b->c0.nb <= cmve::EVAL_FIXC_MAXB;
   if (ev) CMVE_HIP(hipEventRecord(ev[0], s));
   if (chained && prev && !fused) {  // (not the specialised prep: the previous batch's finish as a launch of its own,
     // inside the prep's timing span; its own kernel events are not taken -- slot 0's kernel pair times the prep)
@@ -2845,12 +2384,7 @@ static int eval_batch_run(cmve_handle_t h, cmve_eval_batch_t b, int32_t timing_s
     if (st) return st;
   }
   arm(0);
-  if (fchain) {
-    st = cmve::launch_eval_batch_chained(b->sq0, b->sg0, b->c0, b->d_items, nullptr, b->count, b->qf, b->gf, s,
-                                         prev ? prev->d_items : nullptr);
-    if (!st && prev)
-      st = cmve::launch_eval_batch(prev->sq0, prev->sg0, prev->c0, prev->d_items, prev->count, prev->qf, prev->gf, 2, s);
-  } else if (fused)
+  if (fused)
     st = cmve::launch_eval_batch_chained(b->sq0, b->sg0, b->c0, b->d_items, prev ? prev->d_items : nullptr, b->count,
                                          b->qf, b->gf, s);
   else
@@ -2865,11 +2399,6 @@ static int eval_batch_run(cmve_handle_t h, cmve_eval_batch_t b, int32_t timing_s
   }
   if (st) return st;
   if (ev) CMVE_HIP(hipEventRecord(ev[2], s));
-  if (b->fix_launch && !fchain) {
-    arm(2);
-    st = cmve::launch_eval_batch(b->sq0, b->sg0, b->c0, b->d_items, b->count, b->qf, b->gf, 1, s);
-    if (st) return st;
-  }
   if (!chained) {
     arm(3);
     st = cmve::launch_eval_batch(b->sq0, b->sg0, b->c0, b->d_items, b->count, b->qf, b->gf, 2, s);
@@ -2925,10 +2454,6 @@ extern "C" int cmve_eval_batch_finish(cmve_handle_t h, cmve_eval_batch_t b) {
   CMVE_REQUIRE(h && b && b->d_items, "cmve_eval_batch_finish: NULL handle / batch");
   CMVE_REQUIRE(b->pending && b->pending_stream == h->stream,
                "cmve_eval_batch_finish: the batch has no chained run awaiting its finish on this stream");
-  if (CMVE_EVAL_FIX_CHAINED && b->chainable && b->fix_launch && b->c0.nb <= cmve::EVAL_FIXC_MAXB) {
-    const int sf = cmve::launch_eval_batch(b->sq0, b->sg0, b->c0, b->d_items, b->count, b->qf, b->gf, 1, h->stream);
-    if (sf) return sf;
-  }
   const int st = cmve::launch_eval_batch(b->sq0, b->sg0, b->c0, b->d_items, b->count, b->qf, b->gf, 2, h->stream);
   if (st) return st;
   b->pending = false;
@@ -3006,7 +2531,7 @@ extern "C" int cmve_eval_kernel_timing(cmve_handle_t h, int32_t slot, float* ms4
   CMVE_REQUIRE(h && ms4 && slot >= 0 && slot < CMVE_EVAL_TIMING_SLOTS, "cmve_eval_kernel_timing: bad argument");
   hipEvent_t* kev = h->eval_kev[slot];
   const bool chained = h->eval_chained[slot];  // (cmve_eval_batch_run_chained: the finish ran in the next run's prep)
-  const int last = chained ? (h->eval_no_fix[slot] ? 3 : 5) : 7;
+  const int last = chained ? 3 : 7;  // (a chained run is a batch's: prep and rank GEMM only)
   CMVE_REQUIRE(kev[0] && kev[last], "cmve_eval_kernel_timing: slot %d never recorded", slot);
   CMVE_HIP(hipEventSynchronize(kev[last]));
   for (int k = 0; k < 4; ++k) {
