@@ -465,10 +465,25 @@ __device__ __forceinline__ double wave_cos64(const TA* xa, const TB* xb, double 
 
 // ---- K14 level-2 re-score: one pair's score from the fp16 + bf16 residual planes (lo16_elem, cmve_internal.h) ----
 // lane L holds elements [16L, 16L + 16) of each 1024-element chunk: two 16-B fp16 loads and two 16-B bf16 loads
-// per row and chunk.  x2 = h + lo is formed in fp64 (exact unless lo lies 2^-42 below h: then within 2^-53 |x2|),
-// the products and sums in fp64, so the sum's error is a few ulps of 1:
+// per row and chunk.  x2 = h + lo is formed by ONE fp32 add, which is exact: with xf the fp32 value the prep packed
+// (lo16_elem: h = fp16(xf), d2 = xf - h exact, lo = bf16(d2)) and u = ulp32(xf),
+//   - h is a multiple of u (fp16(xf) keeps xf's top bits, normal or subnormal, or rounds up to the next power of two),
+//     and so is lo: d2 is a multiple of u, and rounding it to 8 bits either keeps it (fewer than 8 significant bits
+//     above u) or lands on a coarser multiple;
+//   - h + lo = xf + (lo - d2) with |lo - d2| <= 2^-9 |d2|, and both roundings are monotone with every power of two
+//     on their grids, so |h + lo| cannot pass the power of two above |xf|: it is a multiple of u no larger than
+//     2^24 u, an fp32 value.
+// (Checked on the CPU: 0 inexact sums in 44 million values, Gaussians at eleven scales from 1 to 2^-30 and every fp16
+// value in [0, 1] perturbed by k 2^-13 of its ulp and of itself, |k| <= 12.)  lo may be an fp32 subnormal (|d2| < 2^-126, xf itself below
+// 2^-102): the add is exact where the mode keeps fp32 denormals, as HIP's default does, and were they flushed x2 would
+// move by at most 2^-126 per element, which the 2e-12 term below covers a hundredfold over a row.  So one
+// v_cvt_f32_f16, one shift, one v_add_f32 and one v_cvt_f64_f32 per element and side replace two fp64 conversions and
+// an fp64 add.  The products and sums are fp64 (two FMA chains per lane, even and odd elements, added once; then
+// l16_wave_sum's fixed tree), so the sum's error is a few ulps of 1:
 //   |s2 - cos64| <= el_q + (1 + el_q) el_g + 2e-12
-// (the 2e-12 covers the fp64 sums here and in cos64, as score_error_bound's 1e-12 does for the MFMA bound)
+// (the 2e-12 covers the fp64 sums here and in cos64, as score_error_bound's 1e-12 does for the MFMA bound).  The
+// order of the sum is a function of the pair's elements alone (element e of lane L, then the lane tree), not of the
+// wave, the pipeline depth or the kernel geometry: one evaluation and a batch send the same pairs to level 3.
 typedef uint32_t cmve_u32x4 __attribute__((ext_vector_type(4)));
 struct L16Frag {
   cmve_u32x4 h0, h1, l0, l1;
@@ -483,17 +498,55 @@ __device__ __forceinline__ void l16_load(const uint16_t* __restrict__ hrow, cons
 __device__ __forceinline__ double l16_x(uint32_t hw, uint32_t lw, int half) {
   const uint16_t h = (uint16_t)(hw >> (16 * half));
   const uint32_t l = half ? (lw & 0xffff0000u) : (lw << 16);
-  return (double)(float)__builtin_bit_cast(_Float16, h) + (double)__uint_as_float(l);
+  return (double)((float)__builtin_bit_cast(_Float16, h) + __uint_as_float(l));  // (the fp32 add is exact: above)
 }
-__device__ __forceinline__ double l16_partial(const L16Frag& a, const L16Frag& b, double acc) {
+// this lane's 16 products: even elements into one FMA chain, odd elements into another, the two added once
+__device__ __forceinline__ double l16_partial(const L16Frag& a, const L16Frag& b) {
   const uint32_t ah[8] = {a.h0.x, a.h0.y, a.h0.z, a.h0.w, a.h1.x, a.h1.y, a.h1.z, a.h1.w};
   const uint32_t al[8] = {a.l0.x, a.l0.y, a.l0.z, a.l0.w, a.l1.x, a.l1.y, a.l1.z, a.l1.w};
   const uint32_t bh[8] = {b.h0.x, b.h0.y, b.h0.z, b.h0.w, b.h1.x, b.h1.y, b.h1.z, b.h1.w};
   const uint32_t bl[8] = {b.l0.x, b.l0.y, b.l0.z, b.l0.w, b.l1.x, b.l1.y, b.l1.z, b.l1.w};
+  double acc0 = 0.0, acc1 = 0.0;
 #pragma unroll
-  for (int e = 0; e < 16; ++e)
-    acc = fma(l16_x(ah[e >> 1], al[e >> 1], e & 1), l16_x(bh[e >> 1], bl[e >> 1], e & 1), acc);
-  return acc;
+  for (int w = 0; w < 8; ++w) {
+    acc0 = fma(l16_x(ah[w], al[w], 0), l16_x(bh[w], bl[w], 0), acc0);
+    acc1 = fma(l16_x(ah[w], al[w], 1), l16_x(bh[w], bl[w], 1), acc1);
+  }
+  return acc0 + acc1;
+}
+// the 64 lanes' sum in a fixed tree without an LDS round trip: four DPP row steps (quad xor 1, xor 2, half-row
+// mirror, row mirror), then v_permlane16_swap / v_permlane32_swap (gfx950) for the rows and the wave's halves.  At
+// every step both partners add the same two values, so every lane ends with the same bits.  (The builtins, not
+// inline asm: the compiler places the wait states between a VALU write and the v_permlane read.)
+template <int CTRL>
+__device__ __forceinline__ double l16_dpp(double v) {
+  const uint64_t b = __builtin_bit_cast(uint64_t, v);
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)b, CTRL, 0xF, 0xF, false);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(b >> 32), CTRL, 0xF, 0xF, false);
+  return __builtin_bit_cast(double, (uint64_t)lo | ((uint64_t)hi << 32));
+}
+__device__ __forceinline__ double l16_wave_sum(double v) {
+  v += l16_dpp<0xB1>(v);   // quad_perm [1,0,3,2]
+  v += l16_dpp<0x4E>(v);   // quad_perm [2,3,0,1]
+  v += l16_dpp<0x141>(v);  // row_half_mirror
+  v += l16_dpp<0x140>(v);  // row_mirror
+  {  // rows 0 + 1 and 2 + 3: the swap leaves rows (0, 0, 2, 2) in the first result and (1, 1, 3, 3) in the second
+    const uint64_t b = __builtin_bit_cast(uint64_t, v);
+    const uint32_t lo = (uint32_t)b, hi = (uint32_t)(b >> 32);
+    const auto sl = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
+    const auto sh = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
+    v = __builtin_bit_cast(double, (uint64_t)sl[0] | ((uint64_t)sh[0] << 32)) +
+        __builtin_bit_cast(double, (uint64_t)sl[1] | ((uint64_t)sh[1] << 32));
+  }
+  {  // the lower and the upper 32 lanes
+    const uint64_t b = __builtin_bit_cast(uint64_t, v);
+    const uint32_t lo = (uint32_t)b, hi = (uint32_t)(b >> 32);
+    const auto sl = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
+    const auto sh = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
+    v = __builtin_bit_cast(double, (uint64_t)sl[0] | ((uint64_t)sh[0] << 32)) +
+        __builtin_bit_cast(double, (uint64_t)sl[1] | ((uint64_t)sh[1] << 32));
+  }
+  return v;
 }
 // XCD-ordered re-score of the bucketed undecided pairs: XCD x (blockIdx & 7) owns buckets
 // x, x+8, ...; its waves stride through those buckets' pairs in order, so at any time an XCD works

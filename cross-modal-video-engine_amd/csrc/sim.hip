@@ -178,6 +178,13 @@ __device__ __forceinline__ void lds_add_u32_async(int* p, int v) {
   asm volatile("ds_add_u32 %0, %1" ::"v"(addr), "v"(v) : "memory");
 }
 
+// 16-B LDS write in inline asm, for the same reason (p is 16-B aligned): the level-2 re-score writes its scores while
+// its next pair's global loads are in flight.  Ordered by CMVE_BAR_LDS before anything reads them.
+__device__ __forceinline__ void lds_write_b128_async(void* p, cmve_u32x4 v) {
+  const uint32_t addr = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)p;
+  asm volatile("ds_write_b128 %0, %1" ::"v"(addr), "v"(v) : "memory");
+}
+
 // sum over the 16 lanes of each DPP row (quad xor 1, xor 2, half-row mirror, row mirror): 4 VALU
 __device__ __forceinline__ uint32_t row_sum16(uint32_t v) {
   v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, false);   // quad_perm [1,0,3,2]
@@ -907,77 +914,116 @@ void sim_kernel(
             CMVE_BAR_LDS();
             if (a.q_lo16) {
               // level 2: each wave scores its listed pairs from the fp16 + bf16 residual planes (l16_load /
-              // l16_partial, cmve_internal.h) and decides every direction whose GT score lies outside s2 +- E2; a pair with a
-              // direction left undecided goes to the level-3 list (fp64 in the finish launch, off this kernel's
-              // critical path), or -- the list full -- keeps those flags for the fp64 pass below (the wave owns its
-              // entries: no other wave touches them)
+              // l16_partial / l16_wave_sum, cmve_internal.h) and leaves each pair's score and row bounds in LDS
+              // beside its list entry; after the barrier one thread per entry decides every direction whose GT
+              // score lies outside s2 +- E2, all pairs at once.  A pair with a direction left undecided goes to the
+              // level-3 list (fp64 in the finish launch, off this kernel's critical path), or -- the list full --
+              // keeps those flags for the fp64 pass below.
               // software-pipelined: each wave scores one listed pair per step while the rows of its next pair are
-              // already in flight (two pairs' rows in registers, as two pairs per round trip were; the same
-              // arithmetic per pair, so the same bits)
+              // already in flight (two pairs' rows in registers); a step is loads -> conversions, 16 fp64 FMAs in
+              // two chains -> the register-only lane tree -> one LDS write: no LDS round trip, no atomic, no branch
+              // on the score
+              // Every path into a step's arithmetic has the same loads in flight: a step that fetches does so
+              // unconditionally (a lane past the row's end re-reads the row's start; its sum is dropped), and the
+              // wave's last pair, which has no next pair to fetch, is scored on a path of its own.  Only then can
+              // the compiler wait for the current pair's rows alone: with a fetch skipped on one path into shared
+              // code it merged the paths' counts and waited for vmcnt(0), the next pair's rows included, at the
+              // head of every step -- no load was ever in flight behind the arithmetic.
               struct L2Stage {
-                uint32_t ent;
-                int64_t qr, gc;
                 float elq, elg;
                 L16Frag fq, fg;
               };
+              // {s2, el_q, el_g} of list entry p at 16 p of the staging ring, which is idle from the main loop's
+              // last barrier to the block's end (this kernel's blocks take one tile each)
+              static_assert(!INL || ring_lds_bytes<MODE, BM, BN, PHASED>() >= (size_t)CMVE_INL_LIST * 16,
+                            "the level-2 scores alias the staging ring");
+              const int64_t l2_ldk = a.ldk;
+              const bool l2_inrow = 16 * (int64_t)lane < l2_ldk;  // (the level-2 planes need d_pad <= 1024: one chunk)
+              const int64_t l2_k = l2_inrow ? 16 * (int64_t)lane : 0;
               auto l2_fetch = [&](int p, L2Stage& st) {
-                st.ent = epi.list[p];
-                st.qr = m0 + (st.ent & 0xff);
-                st.gc = n0 + ((st.ent >> 8) & 0xff);
-                st.elq = gld(a.q_el + st.qr);  // (the row bounds travel with the plane rows)
-                st.elg = gld(a.g_el + st.gc);
-                const int64_t k = 16 * (int64_t)lane;  // (the level-2 planes need d_pad <= 1024: one chunk)
-                if (k < a.ldk) {
-                  l16_load(a.qhi + st.qr * a.ldk, a.q_lo16 + st.qr * a.ldk, k, st.fq);
-                  l16_load(a.ghi + st.gc * a.ldk, a.g_lo16 + st.gc * a.ldk, k, st.fg);
-                }
+                const uint32_t ent = epi.list[p];
+                const int64_t qr = m0 + (ent & 0xff), gc = n0 + ((ent >> 8) & 0xff);
+                st.elq = gld(a.q_el + qr);  // (the row bounds travel with the plane rows)
+                st.elg = gld(a.g_el + gc);
+                l16_load(a.qhi + qr * l2_ldk, a.q_lo16 + qr * l2_ldk, l2_k, st.fq);
+                l16_load(a.ghi + gc * l2_ldk, a.g_lo16 + gc * l2_ldk, l2_k, st.fg);
+                // (the scheduler otherwise lifts the current pair's first conversions, and with them the wait for
+                // its rows, above these loads)
+                __builtin_amdgcn_sched_barrier(0);
               };
               auto l2_finish = [&](int p, const L2Stage& st) {
-                double s2 = 16 * (int64_t)lane < a.ldk ? l16_partial(st.fq, st.fg, 0.0) : 0.0;
-#pragma unroll
-                for (int o = 32; o >= 1; o >>= 1) s2 += __shfl_xor(s2, o, 64);
+                const double part = l16_partial(st.fq, st.fg);
+                const double s2 = l16_wave_sum(l2_inrow ? part : 0.0);
                 if (lane == 0) {
-                  const double eq = (double)st.elq, eg = (double)st.elg;
-                  const double E2 = eq + (1.0 + eq) * eg + 2e-12;
-                  uint32_t fl = (st.ent >> 16) & 3u;
-                  const int lr = (int)(st.ent & 0xff), lc = (int)((st.ent >> 8) & 0xff);
-                  if (fl & 1u) {
-                    const double t = epi.sgt[lr];
-                    if (s2 - E2 > t) { lds_add_u32_async(&lds_rc[lr], 1); fl &= ~1u; }
-                    else if (s2 + E2 < t) fl &= ~1u;
-                  }
-                  if (fl & 2u) {
-                    const double t = epi.sgt[BM + lc];
-                    if (s2 - E2 > t) { lds_add_u32_async(&lds_cc[lc], 1); fl &= ~2u; }
-                    else if (s2 + E2 < t) fl &= ~2u;
-                  }
-                  if (fl && a.l3_count) {  // level 3: counted (a returning atomic: only these few pairs pay it),
-                    const unsigned slot = gadd(a.l3_count, 1u);  // listed for the finish (batches) or, with no
-                    if (a.l3 && slot < (unsigned)a.l3_cap) {     // list (one evaluation), re-scored right here
-                      gst(a.l3 + slot, (unsigned long long)st.qr | ((unsigned long long)st.gc << 31) |
-                                           ((unsigned long long)fl << 62));
-                      fl = 0u;
+                  const uint64_t sb = __builtin_bit_cast(uint64_t, s2);
+                  const cmve_u32x4 rec = {(uint32_t)sb, (uint32_t)(sb >> 32), __float_as_uint(st.elq),
+                                          __float_as_uint(st.elg)};
+                  lds_write_b128_async(smem + 16 * p, rec);
+                }
+              };
+              // the decision, one thread per list entry (the loop is uniform: every wave of the block takes every
+              // trip, so the ballot below sees whole waves)
+              auto l2_decide = [&]() {
+                for (int t0 = 0; t0 < ntot; t0 += NTT) {
+                  const int t = t0 + tid;
+                  uint32_t ent = 0u, fl = 0u;
+                  if (t < ntot) {
+                    ent = epi.list[t];
+                    const cmve_u32x4 rec = *(const cmve_u32x4*)(smem + 16 * t);
+                    const double s2 = __builtin_bit_cast(double, (uint64_t)rec.x | ((uint64_t)rec.y << 32));
+                    const double eq = (double)__uint_as_float(rec.z), eg = (double)__uint_as_float(rec.w);
+                    const double E2 = eq + (1.0 + eq) * eg + 2e-12;
+                    fl = (ent >> 16) & 3u;
+                    const int lr = (int)(ent & 0xff), lc = (int)((ent >> 8) & 0xff);
+                    if (fl & 1u) {
+                      const double sg = epi.sgt[lr];
+                      if (s2 - E2 > sg) { lds_add_u32_async(&lds_rc[lr], 1); fl &= ~1u; }
+                      else if (s2 + E2 < sg) fl &= ~1u;
+                    }
+                    if (fl & 2u) {
+                      const double sg = epi.sgt[BM + lc];
+                      if (s2 - E2 > sg) { lds_add_u32_async(&lds_cc[lc], 1); fl &= ~2u; }
+                      else if (s2 + E2 < sg) fl &= ~2u;
                     }
                   }
-                  epi.list[p] = (st.ent & 0xffffu) | (fl << 16);
+                  if (a.l3_count) {  // level 3: counted with one returning atomic per wave that has such pairs, and
+                    const unsigned long long um = __builtin_amdgcn_ballot_w64(fl != 0u);  // listed for the finish
+                    if (um) {  // (batches) or, with no list (one evaluation), re-scored right here
+                      unsigned base = 0u;
+                      if (lane == 0) base = gadd(a.l3_count, (unsigned)__builtin_popcountll(um));
+                      base = (unsigned)__builtin_amdgcn_readfirstlane((int)base);
+                      const unsigned slot = base + __builtin_amdgcn_mbcnt_hi((uint32_t)(um >> 32),
+                                                                             __builtin_amdgcn_mbcnt_lo((uint32_t)um, 0u));
+                      if (fl && a.l3 && slot < (unsigned)a.l3_cap) {
+                        gst(a.l3 + slot, (unsigned long long)(m0 + (ent & 0xff)) |
+                                             ((unsigned long long)(n0 + ((ent >> 8) & 0xff)) << 31) |
+                                             ((unsigned long long)fl << 62));
+                        fl = 0u;
+                      }
+                    }
+                  }
+                  if (t < ntot) epi.list[t] = (ent & 0xffffu) | (fl << 16);
                 }
               };
               {
                 L2Stage sa, sb;
                 int p = wave;
-                if (p < ntot) l2_fetch(p, sa);
-                while (p < ntot) {  // (two named stages, no register copies)
-                  int pn = p + NWT;
-                  if (pn < ntot) l2_fetch(pn, sb);
-                  l2_finish(p, sa);
-                  p = pn;
-                  if (p >= ntot) break;
-                  pn = p + NWT;
-                  if (pn < ntot) l2_fetch(pn, sa);
-                  l2_finish(p, sb);
-                  p = pn;
+                if (p < ntot) {
+                  l2_fetch(p, sa);
+                  for (;;) {  // (two named stages, no register copies; the wave's last pair is scored on a path of its
+                    if (p + NWT >= ntot) { l2_finish(p, sa); break; }  // own, with no fetch to skip: above)
+                    l2_fetch(p + NWT, sb);
+                    l2_finish(p, sa);
+                    p += NWT;
+                    if (p + NWT >= ntot) { l2_finish(p, sb); break; }
+                    l2_fetch(p + NWT, sa);
+                    l2_finish(p, sb);
+                    p += NWT;
+                  }
                 }
               }
+              CMVE_BAR_LDS();  // every listed pair's score is in LDS
+              l2_decide();
               CMVE_BAR_LDS();  // the level-2 flags are in LDS for every wave
             }
             auto rescore2 = [&](uint32_t e1, uint32_t e2, bool two) {
