@@ -472,17 +472,32 @@ def ap_from_positions(positions) -> float:
 # the shard
 # ---------------------------------------------------------------------------------------------
 
+_L2_MEASURES = ('euclidean', 'l2', 'l2_norm')  # CMVE_PW_L2 with fp64 score words: what K19 - K21 filter
+
+
 class ShardedGallery:
     """This rank's gallery shard [offset, offset + n) of an n_global-video gallery, packed in HBM.
 
     ``comm``: a communicator (default: TorchComm over torch.distributed's process group).
     ``measure``: 'cosine' (the default: packed rows, the fp16 MFMA rank GEMM) or one of evaluation.py's
     non-cosine measures: the rows stay resident unnormalised in the measure's input dtype, every method keeps its
-    return types, ``mode`` arguments are ignored and top-k returns errors (ascending)."""
+    return types, ``mode`` arguments are ignored and top-k returns errors (ascending).
+    ``filter`` (euclidean / l2 / l2_norm; ValueError when True under any other measure): the route of the evaluation's
+    count pass over this shard -- False: the fp64 chain (K18); True: the fp16 MFMA filter (K21,
+    ``engine.pairwise_count(filter=True)``: the same words, an overflowing band list resolved on the device, so
+    nothing synchronises and no flag rides a collective); None: the filter from ``engine.L2_FILTER_MIN_PAIRS``
+    (captions x this shard's videos).  ``band_cap``: the slots of the shard's first band list (default
+    ``engine.l2_band_cap`` of the first filtered pass); the methods that end on the host grow it, or switch this
+    shard's later passes to the fp64 route, from the counters (``filter_stats``)."""
 
     def __init__(self, local_embs, offset: int, n_global: int, with_lo: bool = False, eps: float = 0.0,
                  device: Optional[torch.device] = None, with_f16: bool = True, comm=None, cap: int = 1 << 22,
-                 measure: str = 'cosine'):
+                 measure: str = 'cosine', filter: Optional[bool] = None, band_cap: Optional[int] = None):
+        if filter and measure not in _L2_MEASURES:
+            raise ValueError(f"ShardedGallery: filter=True needs a Euclidean measure {_L2_MEASURES}, not {measure!r}")
+        self._pw_filter = filter
+        self._pw_band_cap = band_cap
+        self._pw_stats = None
         self.comm = _comm(comm)
         self.rank, self.world = self.comm.rank, self.comm.world
         self.offset = int(offset)
@@ -550,8 +565,11 @@ class ShardedGallery:
         self.shard = self._pw_rows(local_embs)  # resident, unnormalised, in the measure's input dtype
         self.device = self.shard.device
         self.n = int(self.shard.shape[0])
-        self._pw_packed = None  # the Euclidean measures: the shard's pack for K20, made by the first top-k
-        self._pw_filter_off = False  # latched by a top-k the filter handed back whole: this shard stays on fp64
+        self._pw_packed = None  # the Euclidean measures: the shard's pack for K20 / K21, made by the first call
+        self._pw_filter_off = False  # latched by a top-k the filter handed back whole, or a count whose band
+        #                              exceeds 1/8 of the pairs: this shard stays on fp64
+        self._pw_band = None  # K21's band list, persistent; _pw_plan grows it
+        self._pw_pairs = 0  # the pairs of the last filtered count
 
     def _pw_spec(self):
         from .linas.evaluation import measure_spec
@@ -568,9 +586,54 @@ class ShardedGallery:
         off, idx = csr
         return engine.pairwise_item_scores(q, self.shard, *self._pw_spec(), off, idx, n_items, col_dir, idx_base)
 
+    def _pw_pack(self):
+        """The shard's pack for the filters, made ONCE and shared by the top-k and the count; it keeps the rows it
+        is given, so there is no second copy of the shard."""
+        if self._pw_packed is None:
+            self._pw_packed = engine.RowSet(self.shard, eps=0.0, with_lo=False, device=self.device)
+        return self._pw_packed
+
     def _pw_count(self, q, row, col):
-        """ONE pass over (all captions) x (this shard): (row positions | None, column positions | None), int32."""
-        return engine.pairwise_count(q, self.shard, *self._pw_spec(), row=row, col=col)
+        """ONE pass over (all captions) x (this shard): (row positions | None, column positions | None), int32.
+        Under a Euclidean measure with the filter due (K21) the count is ``cmve_l2_count_resolved``'s: the same words
+        whatever the band list does, its counters kept on the device as this pass's ``filter_stats``."""
+        self._pw_stats = None
+        pairs = int(q.shape[0]) * self.n
+        due = (self.measure in _L2_MEASURES and self._pw_filter is not False and not self._pw_filter_off
+               and (self._pw_filter or pairs >= engine.L2_FILTER_MIN_PAIRS))
+        if not due:  # (filter=False: the shard decides the route, not the engine's own auto rule on plain rows)
+            return engine.pairwise_count(q, self.shard, *self._pw_spec(), row=row, col=col, filter=False)
+        if self._pw_band is None:
+            cap = engine.l2_band_cap(pairs) if self._pw_band_cap is None else int(self._pw_band_cap)
+            self._pw_band = torch.empty(cap, dtype=torch.int64, device=self.device)
+        rpos, cpos, self._pw_stats = engine.pairwise_count(q, self._pw_pack(), *self._pw_spec(), row=row, col=col,
+                                                           filter=True, band=self._pw_band, return_stats=True)
+        self._pw_pairs = pairs
+        return rpos, cpos
+
+    @property
+    def filter_stats(self):
+        """The counters of the last pass's filtered count over this shard -- {decided, band, rescored, overflow,
+        fallback}, fallback = the band list overflowed and the canonical count gave the words -- or None when that
+        pass did not try the filter.  Read from the device: this synchronises."""
+        if self._pw_stats is None:
+            return None
+        decided, band, rescored, overflow = (int(v) for v in self._pw_stats.cpu().numpy())
+        return {"decided": decided, "band": band, "rescored": rescored, "overflow": overflow,
+                "fallback": overflow == 1}
+
+    def _pw_plan(self):
+        """After a pass that ended on the host anyway: grow this shard's band list to the reported need, or latch
+        the fp64 route when the band exceeds 1/8 of the pairs (``engine.l2_band_plan``).  Shard-local: it changes the
+        route of later passes, never their words, so the ranks need not agree on it."""
+        st = self.filter_stats
+        if st is None:
+            return
+        cap = engine.l2_band_plan(self._pw_pairs, st["band"], st["overflow"], self._pw_band.numel())
+        if cap is None:
+            self._pw_filter_off = True
+        elif cap > self._pw_band.numel():
+            self._pw_band = torch.empty(cap, dtype=torch.int64, device=self.device)
 
     def _pw_ranks(self, off, sc, pos, n_m: int) -> torch.Tensor:
         return engine.pairwise_list_ranks(off, sc, pos, n_m)
@@ -581,11 +644,9 @@ class ShardedGallery:
         finished on the fp64 route here, on this shard alone: the words are the same and no flag rides a collective."""
         if self._pw_filter_off:
             return engine.pairwise_topk(q, self.shard, *self._pw_spec(), k, to_host=False, filter=False)
-        if (self._pw_packed is None and self.measure in ('euclidean', 'l2', 'l2_norm')
+        if (self._pw_packed is None and self.measure in _L2_MEASURES
                 and engine.l2_topk_auto(q.shape[0], self.n, packed=True)):
-            # packed ONCE, by the first call large enough for the filter; the pack keeps the rows it is given, so
-            # there is no second copy of the shard
-            self._pw_packed = engine.RowSet(self.shard, eps=0.0, with_lo=False, device=self.device)
+            self._pw_pack()  # ONCE, by the first call large enough for a filter
         g = self.shard if self._pw_packed is None else self._pw_packed
         idx, err, st = engine.pairwise_topk(q, g, *self._pw_spec(), k, to_host=False, return_stats=True)
         self._pw_filter_off = st is not None and st["fallback"]
@@ -655,6 +716,7 @@ class ShardedGallery:
             v2t_pos = v2t_pos.cpu().numpy().astype(np.int64)
         if t2v is not None:
             t2v, t2v_pos = t2v.cpu().numpy().astype(np.int64), t2v_pos.cpu().numpy().astype(np.int64)
+        self._pw_plan()  # (after the result copies: the stream has drained)
         return t2v, t2v_pos, v2t, v2t_pos
 
     def _pw_cal_perf(self, q_local, v2t_gt, t2v_gt):
@@ -732,7 +794,11 @@ class ShardedGallery:
         q_all = self.all_gather_rows(q_local)
         if self.measure != 'cosine':
             ranks, _ = self.rank_queries_device(q_all, gt_csr, n_q)
-            return ranks.cpu().numpy().astype(np.int64) if return_host else ranks
+            if not return_host:
+                return ranks
+            ranks = ranks.cpu().numpy().astype(np.int64)
+            self._pw_plan()
+            return ranks
         for _attempt in range(4):
             ranks, ovf = self.rank_queries_device(q_all, gt_csr, n_q, mode, events, chunks)
             if not bool(ovf.item()):

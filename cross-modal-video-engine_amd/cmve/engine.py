@@ -422,7 +422,7 @@ class _PairwisePositions:
             start += items
         rsc, csc, stats = buf[:ritems], buf[ritems:ritems + citems], buf[ritems + citems:]
         pairs = na * nb
-        cap = max(1, min(pairs // 8, max(1 << 16, pairs // 128)))
+        cap = l2_band_cap(pairs)
         for attempt in range(2):
             nbytes = l2_count_workspace(ra, rb, cap)
             ws = torch.empty(max(nbytes // 8, 1), dtype=torch.int64, device=dev)
@@ -530,15 +530,55 @@ def pairwise_item_scores(a, b, metric: int, alpha: float, beta: float, score_dty
     return out[:int(n_items)]
 
 
-def pairwise_count(a, b, metric: int, alpha: float, beta: float, score_dtype, row=None, col=None):
+def l2_band_cap(pairs: int) -> int:
+    """The band list a first filtered count over ``pairs`` pairs is given: 1/128 of the pairs, at least 65,536
+    slots, never more than the 1/8 above which the filter stops paying."""
+    return max(1, min(pairs // 8, max(1 << 16, pairs // 128)))
+
+
+def l2_band_plan(pairs: int, band: int, overflow, cap: int) -> Optional[int]:
+    """The band capacity for the NEXT filtered count over ``pairs`` pairs, from the counters of the last one (pure
+    host arithmetic): ``cap`` when its list held the band, the reported ``band`` when it overflowed and
+    ``band * 8 <= pairs`` (one list of that size suffices), None above that -- stop asking the filter: the fp64
+    route is the cheaper one for these rows."""
+    if not overflow:
+        return int(cap)
+    return int(band) if int(band) * 8 <= int(pairs) else None
+
+
+def _l2_set_ok(s) -> bool:
+    return s is None or (s.eps == 0.0 and s.has_f16 and not s.desc.flags & _lib.PACK_RAW)
+
+
+def pairwise_count(a, b, metric: int, alpha: float, beta: float, score_dtype, row=None, col=None,
+                   filter: Optional[bool] = None, band: Optional[torch.Tensor] = None, return_stats: bool = False):
     """(row_pos, col_pos): int32 device tensors of 0-based positions counted over THIS call's pairs against the
     caller's item scores (``cmve_pairwise_count``, K18's launch 2).  row = (off [na + 1], scores fp64 [items], n):
     a non-NaN item's word is #{ j : e(i, j) < score }; a NaN item's is n - (NaN items of its list) + (its place
     among them) when n > 0 and 0 when n == 0 (one shard passes the global n).  col: the mirror; a direction left
-    None gives None.  No host copy, no synchronisation."""
-    a, b = _pw_pair(a, b, "pairwise_count")
+    None gives None.  No host copy, no synchronisation.
+
+    a / b: plain rows, or a ``RowSet`` packed with eps = 0, ``with_lo=False`` and its fp16 plane (a resident side is
+    packed once; its ``.raw`` rows are the fp64 route's operand).  ``filter``: False -- ``cmve_pairwise_count``; True
+    -- ``cmve_l2_count_resolved`` (K21: the fp16 MFMA filter with the band re-scored on the canonical chain, and a
+    band list that overflows resolved ON THE DEVICE by the canonical count: the same words either way, nothing read
+    on the host), ValueError unless the metric is ``PW_L2`` with float64 score words, alpha finite and non-zero and
+    beta finite; None -- the filter when it applies and na * nb reaches ``L2_FILTER_MIN_PAIRS``.  Plain rows are
+    packed inside the call when the filter runs.  ``band``: a caller-owned int64 device tensor that holds the band
+    list, one slot per element (None: a fresh one of ``l2_band_cap(na * nb)`` slots).  ``return_stats``: also return
+    the int64 [4] DEVICE tensor {decided, band found, band re-scored, overflow} (``l2_band_plan`` reads it once the
+    caller has it on the host), or None when the filter did not run."""
+    applies = (metric == _lib.PW_L2 and score_dtype == torch.float64 and alpha != 0 and bool(np.isfinite(alpha))
+               and bool(np.isfinite(beta)))
+    if filter and not applies:
+        raise ValueError("pairwise_count: filter=True needs PW_L2 with float64 score words, alpha finite and "
+                         "non-zero, beta finite")
+    a_set = a if isinstance(a, RowSet) else None
+    b_set = b if isinstance(b, RowSet) else None
+    a, b = _pw_pair(a_set.raw if a_set is not None else a, b_set.raw if b_set is not None else b, "pairwise_count")
+    na, nb, dev = a.shape[0], b.shape[0], a.device
     sides = []
-    for side, n_lists in ((row, a.shape[0]), (col, b.shape[0])):
+    for side, n_lists in ((row, na), (col, nb)):
         if side is None:
             sides.append((None, None, 0, 0, None))
             continue
@@ -547,14 +587,33 @@ def pairwise_count(a, b, metric: int, alpha: float, beta: float, score_dtype, ro
             raise ValueError(f"pairwise_count: {off.numel() - 1} lists for {n_lists} rows")
         if sc.dtype != torch.float64 or not sc.is_contiguous():
             raise TypeError("pairwise_count: item scores are contiguous float64")
-        sides.append((off, sc, sc.numel(), int(n), torch.empty(max(sc.numel(), 1), dtype=torch.int32,
-                                                               device=a.device)))
+        sides.append((off, sc, sc.numel(), int(n), torch.empty(max(sc.numel(), 1), dtype=torch.int32, device=dev)))
     (roff, rsc, ritems, rn, rpos), (coff, csc, citems, cn, cpos) = sides
-    check(lib.cmve_pairwise_count(handle(a.device), _ptr(a), _dtype_code(a), _pw_ld(a), a.shape[0], _ptr(b),
-                                  _dtype_code(b), _pw_ld(b), b.shape[0], a.shape[1], metric, float(alpha),
-                                  float(beta), _pw_code(score_dtype), _ptr(roff), _ptr(rsc), ritems, rn, _ptr(rpos),
-                                  _ptr(coff), _ptr(csc), citems, cn, _ptr(cpos)), "cmve_pairwise_count")
-    return (None if rpos is None else rpos[:ritems]), (None if cpos is None else cpos[:citems])
+    if filter is None:  # auto never hands the entry what it refuses; filter=True does, and the entry says so
+        filter = applies and na * nb >= L2_FILTER_MIN_PAIRS and _l2_set_ok(a_set) and _l2_set_ok(b_set)
+    stats = None
+    if filter:
+        if band is not None and (band.dtype != torch.int64 or not band.is_contiguous() or band.device != dev):
+            raise TypeError("pairwise_count: band is a contiguous int64 tensor on the rows' device")
+        if a_set is None:
+            a_set = RowSet(a, with_lo=False, device=dev)
+        if b_set is None:
+            b_set = RowSet(b, with_lo=False, device=dev)
+        if band is None:
+            band = torch.empty(l2_band_cap(na * nb), dtype=torch.int64, device=dev)
+        stats = torch.empty(4, dtype=torch.int64, device=dev)
+        check(lib.cmve_l2_count_resolved(handle(dev), C.byref(a_set.desc), C.byref(b_set.desc), float(alpha),
+                                         float(beta), _ptr(roff), _ptr(rsc) if ritems else None, ritems, rn,
+                                         _ptr(rpos), _ptr(coff), _ptr(csc) if citems else None, citems, cn,
+                                         _ptr(cpos), _ptr(band) if band.numel() else None, 8 * band.numel(),
+                                         _ptr(stats)), "cmve_l2_count_resolved")
+    else:
+        check(lib.cmve_pairwise_count(handle(dev), _ptr(a), _dtype_code(a), _pw_ld(a), na, _ptr(b), _dtype_code(b),
+                                      _pw_ld(b), nb, a.shape[1], metric, float(alpha), float(beta),
+                                      _pw_code(score_dtype), _ptr(roff), _ptr(rsc), ritems, rn, _ptr(rpos), _ptr(coff),
+                                      _ptr(csc), citems, cn, _ptr(cpos)), "cmve_pairwise_count")
+    out = (None if rpos is None else rpos[:ritems]), (None if cpos is None else cpos[:citems])
+    return out + (stats,) if return_stats else out
 
 
 def pairwise_list_ranks(off: torch.Tensor, scores: torch.Tensor, pos: torch.Tensor, n_m: int) -> torch.Tensor:

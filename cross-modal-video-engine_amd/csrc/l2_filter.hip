@@ -15,6 +15,9 @@
 //   l2f_fixup_kernel  a wave takes 64 band pairs: the (a - b) chunks go through LDS transposed (coalesced loads), each
 //                     lane runs its own pair's chain
 //   l2f_nan_kernel    the NaN items' words (cmve_pairwise_count's rule with the caller's n)
+// K21 (cmve_l2_count_resolved): the same launches, then two that read the overflow word and do nothing when it is 0 --
+//   l2f_gated_zero_kernel zeroes the words, pairwise_rank.hip's gated pwr_count_kernel counts every pair on the
+//   canonical chain -- so the words are cmve_pairwise_count's whatever the band did, with no host read in between.
 #include "l2_filter_tile.h"
 
 namespace cmve {
@@ -303,6 +306,16 @@ __global__ __launch_bounds__(256) void l2f_nan_kernel(const int64_t* __restrict_
   }
 }
 
+// ---- K21: the band list overflowed -> drop the words counted so far (the canonical count that follows needs zeros) ----
+__global__ __launch_bounds__(256) void l2f_gated_zero_kernel(int32_t* __restrict__ row_pos, int64_t row_items,
+                                                             int32_t* __restrict__ col_pos, int64_t col_items,
+                                                             const l2f_u64* __restrict__ gate) {
+  if (gld(gate) == 0ull) return;
+  const int64_t step = (int64_t)gridDim.x * 256;
+  for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < row_items; p += step) row_pos[p] = 0;
+  for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < col_items; p += step) col_pos[p] = 0;
+}
+
 }  // namespace
 }  // namespace cmve
 
@@ -319,41 +332,44 @@ extern "C" int cmve_l2_count_workspace(const cmve_rows_t* a, const cmve_rows_t* 
   return CMVE_OK;
 }
 
-extern "C" int cmve_l2_count(cmve_handle_t h, const cmve_rows_t* a, const cmve_rows_t* b, double alpha, double beta,
-                             const int64_t* row_off, const double* row_sc, int64_t row_items, int64_t row_n,
-                             int32_t* row_pos, const int64_t* col_off, const double* col_sc, int64_t col_items,
-                             int64_t col_n, int32_t* col_pos, void* ws, int64_t ws_bytes, int64_t* stats) {
-  CMVE_REQUIRE(h && a && b && stats, "cmve_l2_count: NULL argument");
+// cmve_l2_count and cmve_l2_count_resolved: the checks (refusals name the entry) and K19's launches; `resolved` adds
+// the two launches gated on the overflow word
+static int l2_count_run(const char* name, bool resolved, cmve_handle_t h, const cmve_rows_t* a, const cmve_rows_t* b,
+                        double alpha, double beta, const int64_t* row_off, const double* row_sc, int64_t row_items,
+                        int64_t row_n, int32_t* row_pos, const int64_t* col_off, const double* col_sc,
+                        int64_t col_items, int64_t col_n, int32_t* col_pos, void* ws, int64_t ws_bytes,
+                        int64_t* stats) {
+  CMVE_REQUIRE(h && a && b && stats, "%s: NULL argument", name);
   CMVE_REQUIRE(alpha != 0.0 && std::isfinite(alpha) && std::isfinite(beta),
-               "cmve_l2_count: alpha must be finite and non-zero, beta finite (%g, %g)", alpha, beta);
-  CMVE_REQUIRE(a->d > 0 && a->d == b->d && a->d_pad == b->d_pad, "cmve_l2_count: dimensions differ (%lld, %lld)",
+               "%s: alpha must be finite and non-zero, beta finite (%g, %g)", name, alpha, beta);
+  CMVE_REQUIRE(a->d > 0 && a->d == b->d && a->d_pad == b->d_pad, "%s: dimensions differ (%lld, %lld)", name,
                (long long)a->d, (long long)b->d);
-  CMVE_REQUIRE(a->h16 && b->h16 && a->err_h16 && b->err_h16, "cmve_l2_count: a set was packed without its fp16 plane");
-  CMVE_REQUIRE(a->eps == 0.0 && b->eps == 0.0, "cmve_l2_count: the sets must be packed with eps = 0");
+  CMVE_REQUIRE(a->h16 && b->h16 && a->err_h16 && b->err_h16, "%s: a set was packed without its fp16 plane", name);
+  CMVE_REQUIRE(a->eps == 0.0 && b->eps == 0.0, "%s: the sets must be packed with eps = 0", name);
   CMVE_REQUIRE(!(a->flags & CMVE_PACK_RAW) && !(b->flags & CMVE_PACK_RAW),
-               "cmve_l2_count: CMVE_PACK_RAW sets hold no unit rows");
+               "%s: CMVE_PACK_RAW sets hold no unit rows", name);
   const int64_t na = a->n, nb = b->n, d = a->d;
   CMVE_REQUIRE(na >= 0 && nb >= 0 && na < (1ll << 31) && nb < (1ll << 31) && a->n_pad >= na && b->n_pad >= nb &&
                    a->n_pad % CMVE_ROW_ALIGN == 0 && b->n_pad % CMVE_ROW_ALIGN == 0 && a->d_pad >= d &&
                    a->d_pad % CMVE_DIM_ALIGN == 0,
-               "cmve_l2_count: bad shape");
+               "%s: bad shape", name);
   CMVE_REQUIRE((a->raw || !na) && (b->raw || !nb) && a->inv_norm && b->inv_norm && a->raw_ld >= d && b->raw_ld >= d,
-               "cmve_l2_count: the sets' raw rows are missing");
+               "%s: the sets' raw rows are missing", name);
   CMVE_REQUIRE((a->raw_dtype == CMVE_F32 || a->raw_dtype == CMVE_F64) &&
                    (b->raw_dtype == CMVE_F32 || b->raw_dtype == CMVE_F64),
-               "cmve_l2_count: raw rows must be CMVE_F32/CMVE_F64");
+               "%s: raw rows must be CMVE_F32/CMVE_F64", name);
   if (!row_pos) row_items = 0;
   if (!col_pos) col_items = 0;
   CMVE_REQUIRE(row_items >= 0 && col_items >= 0 && row_n >= 0 && col_n >= 0 && row_n < (1ll << 31) &&
                    col_n < (1ll << 31) && row_items < (1ll << 31) * 256 && col_items < (1ll << 31) * 256,
-               "cmve_l2_count: bad counts (%lld, %lld items; n %lld, %lld)", (long long)row_items,
+               "%s: bad counts (%lld, %lld items; n %lld, %lld)", name, (long long)row_items,
                (long long)col_items, (long long)row_n, (long long)col_n);
-  CMVE_REQUIRE(!row_pos || (row_off && (row_sc || !row_items)), "cmve_l2_count: row lists missing");
-  CMVE_REQUIRE(!col_pos || (col_off && (col_sc || !col_items)), "cmve_l2_count: column lists missing");
-  CMVE_REQUIRE(ws_bytes >= 0 && (ws || ws_bytes < 8), "cmve_l2_count: workspace missing");
-  CMVE_REQUIRE((((uintptr_t)ws) & 7) == 0, "cmve_l2_count: workspace must be 8-byte aligned");
+  CMVE_REQUIRE(!row_pos || (row_off && (row_sc || !row_items)), "%s: row lists missing", name);
+  CMVE_REQUIRE(!col_pos || (col_off && (col_sc || !col_items)), "%s: column lists missing", name);
+  CMVE_REQUIRE(ws_bytes >= 0 && (ws || ws_bytes < 8), "%s: workspace missing", name);
+  CMVE_REQUIRE((((uintptr_t)ws) & 7) == 0, "%s: workspace must be 8-byte aligned", name);
   const int64_t tiles_a = (na + L2F_BM - 1) / L2F_BM, tiles_b = (nb + L2F_BN - 1) / L2F_BN;
-  CMVE_REQUIRE(tiles_a * tiles_b < (1ll << 31), "cmve_l2_count: too many tiles (%lld x %lld)", (long long)tiles_a,
+  CMVE_REQUIRE(tiles_a * tiles_b < (1ll << 31), "%s: too many tiles (%lld x %lld)", name, (long long)tiles_a,
                (long long)tiles_b);
   const hipStream_t st = h->stream;
   CMVE_HIP(hipMemsetAsync(stats, 0, 4 * sizeof(int64_t), st));
@@ -405,5 +421,33 @@ extern "C" int cmve_l2_count(cmve_handle_t h, const cmve_rows_t* a, const cmve_r
     else L2F_FIX(float, float);
   }
 #undef L2F_FIX
-  return check_launch("l2_count");
+  if (resolved) {
+    // the list overflowed (decided on the device: both launches do nothing otherwise): the words so far are
+    // dropped and cmve_pairwise_count's kernel counts every pair on the canonical chain, NaN items included
+    const int64_t items = std::max(row_items, col_items);
+    const int zero_blocks = (int)std::max<int64_t>(1, std::min<int64_t>(8 * device_cus(), (items + 255) / 256));
+    hipLaunchKernelGGL(l2f_gated_zero_kernel, dim3((unsigned)zero_blocks), dim3(256), 0, st, g.row_pos, row_items,
+                       g.col_pos, col_items, (const l2f_u64*)g.stats + 3);
+    pwr_count_l2_gated_launch(st, a->raw, a->raw_dtype, a->raw_ld, na, b->raw, b->raw_dtype, b->raw_ld, nb, d, alpha,
+                              beta, row_off, row_sc, row_n, g.row_pos, col_off, col_sc, col_n, g.col_pos,
+                              (const l2f_u64*)g.stats + 3);
+  }
+  return check_launch(resolved ? "l2_count_resolved" : "l2_count");
+}
+
+extern "C" int cmve_l2_count(cmve_handle_t h, const cmve_rows_t* a, const cmve_rows_t* b, double alpha, double beta,
+                             const int64_t* row_off, const double* row_sc, int64_t row_items, int64_t row_n,
+                             int32_t* row_pos, const int64_t* col_off, const double* col_sc, int64_t col_items,
+                             int64_t col_n, int32_t* col_pos, void* ws, int64_t ws_bytes, int64_t* stats) {
+  return l2_count_run("cmve_l2_count", false, h, a, b, alpha, beta, row_off, row_sc, row_items, row_n, row_pos, col_off,
+                      col_sc, col_items, col_n, col_pos, ws, ws_bytes, stats);
+}
+
+extern "C" int cmve_l2_count_resolved(cmve_handle_t h, const cmve_rows_t* a, const cmve_rows_t* b, double alpha,
+                                      double beta, const int64_t* row_off, const double* row_sc, int64_t row_items,
+                                      int64_t row_n, int32_t* row_pos, const int64_t* col_off, const double* col_sc,
+                                      int64_t col_items, int64_t col_n, int32_t* col_pos, void* ws, int64_t ws_bytes,
+                                      int64_t* stats) {
+  return l2_count_run("cmve_l2_count_resolved", true, h, a, b, alpha, beta, row_off, row_sc, row_items, row_n, row_pos,
+                      col_off, col_sc, col_items, col_n, col_pos, ws, ws_bytes, stats);
 }

@@ -57,7 +57,11 @@ __global__ __launch_bounds__(256) void pwr_item_kernel(const TA* __restrict__ A,
 // cmve_gt_positions_from_matrix's value for it instead, row_n - (NaN items of the list) + (its place among them)
 // (row_n == 0: its word stays 0 -- another shard of the gallery stores it).  The grid has at least one block row and
 // column, so the rule also runs when na or nb is 0.  pos must be zero on entry.
-template <int METRIC, typename TA, typename TB>
+// GATED (K21, cmve_l2_count_resolved; gate / tiles_x / tiles are read by this instantiation alone): every thread reads
+// *gate first and the block returns at once when it is 0; otherwise the blocks of a BOUNDED 1-d grid loop over the
+// tiles_x x tiles_y tiles, block b taking b, b + gridDim.x, ... in the plain grid's own order -- a call whose gate stays
+// shut dispatches a few thousand blocks, not one per tile.
+template <int METRIC, typename TA, typename TB, bool GATED = false>
 __global__ __launch_bounds__(256) void pwr_count_kernel(const TA* __restrict__ A, int64_t lda, int64_t na,
                                                         const TB* __restrict__ B, int64_t ldb, int64_t nb, int64_t d,
                                                         double alpha, double beta, int f32,
@@ -66,8 +70,13 @@ __global__ __launch_bounds__(256) void pwr_count_kernel(const TA* __restrict__ A
                                                         int32_t* __restrict__ row_pos,
                                                         const int64_t* __restrict__ col_off,
                                                         const double* __restrict__ col_sc, int64_t col_n,
-                                                        int32_t* __restrict__ col_pos) {
+                                                        int32_t* __restrict__ col_pos,
+                                                        const unsigned long long* __restrict__ gate, unsigned tiles_x,
+                                                        int64_t tiles) {
   using G = PwWide;
+  if constexpr (GATED) {
+    if (gld(gate) == 0ull) return;  // block-uniform, before the first barrier and before any LDS write
+  }
   __shared__ __attribute__((aligned(16))) double sa[G::KS][G::PA];
   __shared__ __attribute__((aligned(16))) double sb[G::KS][G::PB];
   __shared__ int s_m[2];     // the longest row / column list of the tile: the rounds are block-uniform
@@ -75,114 +84,121 @@ __global__ __launch_bounds__(256) void pwr_count_kernel(const TA* __restrict__ A
   constexpr bool JAC = METRIC == CMVE_PW_JACCARD;
   const int tid = threadIdx.x;
   const int tx = tid % G::TX, ty = tid / G::TX;
-  const int64_t i0 = (int64_t)blockIdx.y * G::TA, j0 = (int64_t)blockIdx.x * G::TB;
-  if (tid < 2) s_m[tid] = 0;
-  if (tid < G::TB) lc[tid] = 0;
-  double e[G::NA][G::NB] = {}, s1[JAC ? G::NA : 1][JAC ? G::NB : 1] = {};
-  pw_tile_loop<G, METRIC>(A, lda, na, B, ldb, nb, d, i0, j0, sa, sb, e, s1);
+  int64_t t = blockIdx.x;  // GATED: this block's tile, then every gridDim.x-th after it
+  do {
+    const unsigned bx = GATED ? (unsigned)(t % tiles_x) : blockIdx.x;
+    const unsigned by = GATED ? (unsigned)(t / tiles_x) : blockIdx.y;
+    const int64_t i0 = (int64_t)by * G::TA, j0 = (int64_t)bx * G::TB;
+    if (tid < 2) s_m[tid] = 0;
+    if (tid < G::TB) lc[tid] = 0;
+    double e[G::NA][G::NB] = {}, s1[JAC ? G::NA : 1][JAC ? G::NB : 1] = {};
+    pw_tile_loop<G, METRIC>(A, lda, na, B, ldb, nb, d, i0, j0, sa, sb, e, s1);
 #pragma unroll
-  for (int u = 0; u < G::NA; ++u)
+    for (int u = 0; u < G::NA; ++u)
 #pragma unroll
-    for (int v = 0; v < G::NB; ++v)
-      e[u][v] = pw_round(pw_score<METRIC>(e[u][v], JAC ? s1[JAC ? u : 0][JAC ? v : 0] : 0.0, alpha, beta), f32);
-  // rows and columns of a partial tile beyond na / nb were staged as zeros: they never count and own no list
-  bool va[G::NA], vb[G::NB];
-  int64_t ro[G::NA], co[G::NB];
-  int mr[G::NA], mc[G::NB], mr_max = 0, mc_max = 0;
-#pragma unroll
-  for (int u = 0; u < G::NA; ++u) {
-    const int64_t i = i0 + G::arow(ty, u);
-    va[u] = i < na;
-    ro[u] = (va[u] && row_pos) ? row_off[i] : 0;
-    mr[u] = (va[u] && row_pos) ? (int)(row_off[i + 1] - ro[u]) : 0;
-    mr_max = max(mr_max, mr[u]);
-  }
-#pragma unroll
-  for (int v = 0; v < G::NB; ++v) {
-    const int64_t j = j0 + G::brow(tx, v);
-    vb[v] = j < nb;
-    co[v] = (vb[v] && col_pos) ? col_off[j] : 0;
-    mc[v] = (vb[v] && col_pos) ? (int)(col_off[j + 1] - co[v]) : 0;
-    mc_max = max(mc_max, mc[v]);
-  }
-  if (tx == 0 && mr_max) atomicMax(&s_m[0], mr_max);
-  if (ty == 0 && mc_max) atomicMax(&s_m[1], mc_max);
-  // NaN items: the last positions of the row / column, in list order (as gtpos_rows_kernel / gtpos_cols_kernel)
-  if (blockIdx.x == 0 && tx == 0 && row_n > 0) {
+      for (int v = 0; v < G::NB; ++v)
+        e[u][v] = pw_round(pw_score<METRIC>(e[u][v], JAC ? s1[JAC ? u : 0][JAC ? v : 0] : 0.0, alpha, beta), f32);
+    // rows and columns of a partial tile beyond na / nb were staged as zeros: they never count and own no list
+    bool va[G::NA], vb[G::NB];
+    int64_t ro[G::NA], co[G::NB];
+    int mr[G::NA], mc[G::NB], mr_max = 0, mc_max = 0;
 #pragma unroll
     for (int u = 0; u < G::NA; ++u) {
-      int n_nan = 0, run = 0;
-      for (int a = 0; a < mr[u]; ++a) {
-        const double t = row_sc[ro[u] + a];
-        n_nan += (t != t);
-      }
-      for (int a = 0; a < mr[u] && n_nan; ++a) {
-        const double t = row_sc[ro[u] + a];
-        if (t != t) row_pos[ro[u] + a] = (int32_t)(row_n - n_nan + run++);
-      }
+      const int64_t i = i0 + G::arow(ty, u);
+      va[u] = i < na;
+      ro[u] = (va[u] && row_pos) ? row_off[i] : 0;
+      mr[u] = (va[u] && row_pos) ? (int)(row_off[i + 1] - ro[u]) : 0;
+      mr_max = max(mr_max, mr[u]);
     }
-  }
-  if (blockIdx.y == 0 && ty == 0 && col_n > 0) {
 #pragma unroll
     for (int v = 0; v < G::NB; ++v) {
-      int n_nan = 0, run = 0;
-      for (int a = 0; a < mc[v]; ++a) {
-        const double t = col_sc[co[v] + a];
-        n_nan += (t != t);
-      }
-      for (int a = 0; a < mc[v] && n_nan; ++a) {
-        const double t = col_sc[co[v] + a];
-        if (t != t) col_pos[co[v] + a] = (int32_t)(col_n - n_nan + run++);
+      const int64_t j = j0 + G::brow(tx, v);
+      vb[v] = j < nb;
+      co[v] = (vb[v] && col_pos) ? col_off[j] : 0;
+      mc[v] = (vb[v] && col_pos) ? (int)(col_off[j + 1] - co[v]) : 0;
+      mc_max = max(mc_max, mc[v]);
+    }
+    if (tx == 0 && mr_max) atomicMax(&s_m[0], mr_max);
+    if (ty == 0 && mc_max) atomicMax(&s_m[1], mc_max);
+    // NaN items: the last positions of the row / column, in list order (as gtpos_rows_kernel / gtpos_cols_kernel)
+    if (bx == 0 && tx == 0 && row_n > 0) {
+#pragma unroll
+      for (int u = 0; u < G::NA; ++u) {
+        int n_nan = 0, run = 0;
+        for (int a = 0; a < mr[u]; ++a) {
+          const double t = row_sc[ro[u] + a];
+          n_nan += (t != t);
+        }
+        for (int a = 0; a < mr[u] && n_nan; ++a) {
+          const double t = row_sc[ro[u] + a];
+          if (t != t) row_pos[ro[u] + a] = (int32_t)(row_n - n_nan + run++);
+        }
       }
     }
-  }
-  __syncthreads();
-  const int rounds_r = s_m[0], rounds_c = s_m[1];
-  // rows: the 16 threads that share a row (tx = 0..15, consecutive lanes) sum by xor shuffles; every lane of the
-  // block runs every shuffle (the loop bounds are block-uniform, the list test is inside)
-  for (int a = 0; a < rounds_r; ++a) {
+    if (by == 0 && ty == 0 && col_n > 0) {
 #pragma unroll
-    for (int u = 0; u < G::NA; ++u) {
-      int c = 0;
-      if (a < mr[u]) {
-        const double t = row_sc[ro[u] + a];
-#pragma unroll
-        for (int v = 0; v < G::NB; ++v) c += (vb[v] && e[u][v] < t);
+      for (int v = 0; v < G::NB; ++v) {
+        int n_nan = 0, run = 0;
+        for (int a = 0; a < mc[v]; ++a) {
+          const double t = col_sc[co[v] + a];
+          n_nan += (t != t);
+        }
+        for (int a = 0; a < mc[v] && n_nan; ++a) {
+          const double t = col_sc[co[v] + a];
+          if (t != t) col_pos[co[v] + a] = (int32_t)(col_n - n_nan + run++);
+        }
       }
-      c += __shfl_xor(c, 8, 64);
-      c += __shfl_xor(c, 4, 64);
-      c += __shfl_xor(c, 2, 64);
-      c += __shfl_xor(c, 1, 64);
-      if (tx == 0 && c) gadd(row_pos + ro[u] + a, (int32_t)c);
-    }
-  }
-  // columns: the 16 threads that share a column are 4 lanes (ty & 3) of each of the 4 waves: shuffles within the
-  // wave, LDS across the waves, then one atomic per column
-  const int64_t jc = j0 + tid;
-  const bool cown = tid < G::TB && jc < nb && col_pos != nullptr;
-  const int64_t co_t = cown ? col_off[jc] : 0;
-  const int mc_t = cown ? (int)(col_off[jc + 1] - co_t) : 0;
-  for (int a = 0; a < rounds_c; ++a) {
-#pragma unroll
-    for (int v = 0; v < G::NB; ++v) {
-      int c = 0;
-      if (a < mc[v]) {
-        const double t = col_sc[co[v] + a];
-#pragma unroll
-        for (int u = 0; u < G::NA; ++u) c += (va[u] && e[u][v] < t);
-      }
-      c += __shfl_xor(c, 16, 64);
-      c += __shfl_xor(c, 32, 64);
-      if ((ty & 3) == 0 && c) atomicAdd(&lc[G::brow(tx, v)], c);
     }
     __syncthreads();
-    if (tid < G::TB) {
-      const int c = lc[tid];
-      if (a < mc_t && c) gadd(col_pos + co_t + a, (int32_t)c);
-      lc[tid] = 0;
+    const int rounds_r = s_m[0], rounds_c = s_m[1];
+    // rows: the 16 threads that share a row (tx = 0..15, consecutive lanes) sum by xor shuffles; every lane of the
+    // block runs every shuffle (the loop bounds are block-uniform, the list test is inside)
+    for (int a = 0; a < rounds_r; ++a) {
+#pragma unroll
+      for (int u = 0; u < G::NA; ++u) {
+        int c = 0;
+        if (a < mr[u]) {
+          const double t = row_sc[ro[u] + a];
+#pragma unroll
+          for (int v = 0; v < G::NB; ++v) c += (vb[v] && e[u][v] < t);
+        }
+        c += __shfl_xor(c, 8, 64);
+        c += __shfl_xor(c, 4, 64);
+        c += __shfl_xor(c, 2, 64);
+        c += __shfl_xor(c, 1, 64);
+        if (tx == 0 && c) gadd(row_pos + ro[u] + a, (int32_t)c);
+      }
     }
-    __syncthreads();
-  }
+    // columns: the 16 threads that share a column are 4 lanes (ty & 3) of each of the 4 waves: shuffles within the
+    // wave, LDS across the waves, then one atomic per column
+    const int64_t jc = j0 + tid;
+    const bool cown = tid < G::TB && jc < nb && col_pos != nullptr;
+    const int64_t co_t = cown ? col_off[jc] : 0;
+    const int mc_t = cown ? (int)(col_off[jc + 1] - co_t) : 0;
+    for (int a = 0; a < rounds_c; ++a) {
+#pragma unroll
+      for (int v = 0; v < G::NB; ++v) {
+        int c = 0;
+        if (a < mc[v]) {
+          const double t = col_sc[co[v] + a];
+#pragma unroll
+          for (int u = 0; u < G::NA; ++u) c += (va[u] && e[u][v] < t);
+        }
+        c += __shfl_xor(c, 16, 64);
+        c += __shfl_xor(c, 32, 64);
+        if ((ty & 3) == 0 && c) atomicAdd(&lc[G::brow(tx, v)], c);
+      }
+      __syncthreads();
+      if (tid < G::TB) {
+        const int c = lc[tid];
+        if (a < mc_t && c) gadd(col_pos + co_t + a, (int32_t)c);
+        lc[tid] = 0;
+      }
+      __syncthreads();
+    }
+    if constexpr (GATED) __syncthreads();  // the tile's last LDS reads before the next tile's first writes
+    t += gridDim.x;
+  } while (GATED && t < tiles);
 }
 
 // ---- top-k: one gallery chunk's scores into the workspace (fp64, already rounded to the score dtype) ----------
@@ -311,8 +327,27 @@ static void pwr_count_launch(hipStream_t st, const void* A, int32_t a_dtype, int
                   (unsigned)std::max<int64_t>(1, (na + PW_TA - 1) / PW_TA));
   PW_DISPATCH_METRIC(metric, M, PWR_TYPES(a_dtype, b_dtype, TA, TB, {
     hipLaunchKernelGGL((pwr_count_kernel<M, TA, TB>), grid, dim3(256), 0, st, (const TA*)A, lda, na, (const TB*)B, ldb,
-                       nb, d, alpha, beta, f32, row_off, row_sc, row_n, row_pos, col_off, col_sc, col_n, col_pos);
+                       nb, d, alpha, beta, f32, row_off, row_sc, row_n, row_pos, col_off, col_sc, col_n, col_pos,
+                       (const unsigned long long*)nullptr, 0u, (int64_t)0);
   }))
+}
+
+void pwr_count_l2_gated_launch(hipStream_t st, const void* A, int32_t a_dtype, int64_t lda, int64_t na, const void* B,
+                               int32_t b_dtype, int64_t ldb, int64_t nb, int64_t d, double alpha, double beta,
+                               const int64_t* row_off, const double* row_sc, int64_t row_n, int32_t* row_pos,
+                               const int64_t* col_off, const double* col_sc, int64_t col_n, int32_t* col_pos,
+                               const unsigned long long* gate) {
+  // pwr_count_launch's tiles (at least one block row and column: the NaN-item rule) over at most 64 blocks per compute
+  // unit: few enough that a shut gate costs microseconds, many enough that an open one keeps the plain grid's balance
+  // (8 per compute unit left whole rounds of resident blocks half empty: +1.3 ms on a 13 ms count, DESIGN s4 K21)
+  const int64_t tiles_x = std::max<int64_t>(1, (nb + PW_TB - 1) / PW_TB);
+  const int64_t tiles = tiles_x * std::max<int64_t>(1, (na + PW_TA - 1) / PW_TA);
+  const unsigned blocks = (unsigned)std::min<int64_t>(tiles, 64 * (int64_t)device_cus());
+  PWR_TYPES(a_dtype, b_dtype, TA, TB, {
+    hipLaunchKernelGGL((pwr_count_kernel<CMVE_PW_L2, TA, TB, true>), dim3(blocks), dim3(256), 0, st, (const TA*)A,
+                       lda, na, (const TB*)B, ldb, nb, d, alpha, beta, 0, row_off, row_sc, row_n, row_pos, col_off,
+                       col_sc, col_n, col_pos, gate, (unsigned)tiles_x, tiles);
+  })
 }
 
 }  // namespace cmve

@@ -747,6 +747,23 @@ int cmve_l2_count(cmve_handle_t h, const cmve_rows_t* a, const cmve_rows_t* b, d
                   const int64_t* row_off, const double* row_sc, int64_t row_items, int64_t row_n, int32_t* row_pos,
                   const int64_t* col_off, const double* col_sc, int64_t col_items, int64_t col_n, int32_t* col_pos,
                   void* ws, int64_t ws_bytes, int64_t* stats);
+/* K21: cmve_l2_count that is exact whatever the band does, decided on the device (csrc/l2_filter.hip) -- the count
+ * entry of a sharded gallery, whose pass may neither read a flag on the host nor redo a call alone.
+ *   Arguments, workspace (cmve_l2_count_workspace) and refusals: cmve_l2_count's.  On return row_pos / col_pos hold,
+ *   word for word, what
+ *   cmve_pairwise_count(metric = CMVE_PW_L2, score_dtype = CMVE_F64) writes for the same arguments, WHETHER OR NOT
+ *   the band list overflowed: no host read in between, no second call.
+ *   Launches: cmve_l2_count's own (memsets, NaN items, MFMA pass, band re-score -- which returns at once when the
+ *   list overflowed), then two launches of a few thousand blocks gated on the overflow word stats[3], each block of
+ *   which returns at once when it is 0: one zeroes row_pos / col_pos, the other runs cmve_pairwise_count's counting
+ *   tiles over the sets' raw rows (they apply the NaN-item rule themselves).  ws_bytes < 8 is capacity 0: every band
+ *   pair overflows.
+ *   stats: the same four words; overflow == 1 now also says that the words came from the canonical count;
+ *   stats[1] keeps counting past the capacity (the capacity the call would have needed), stats[2] is then 0. */
+int cmve_l2_count_resolved(cmve_handle_t h, const cmve_rows_t* a, const cmve_rows_t* b, double alpha, double beta,
+                           const int64_t* row_off, const double* row_sc, int64_t row_items, int64_t row_n,
+                           int32_t* row_pos, const int64_t* col_off, const double* col_sc, int64_t col_items,
+                           int64_t col_n, int32_t* col_pos, void* ws, int64_t ws_bytes, int64_t* stats);
 
 /* K20: cmve_pairwise_topk for CMVE_PW_L2 with fp64 score words at the MFMA rate (csrc/l2_topk.hip).
  * Replaces, as its K18 twin does: LINAS-engine/inference.py:78-80 (cal_error(video_embs, cap_emb, measure) then
