@@ -618,9 +618,8 @@ class ShardedGallery:
         pass did not try the filter.  Read from the device: this synchronises."""
         if self._pw_stats is None:
             return None
-        decided, band, rescored, overflow = (int(v) for v in self._pw_stats.cpu().numpy())
-        return {"decided": decided, "band": band, "rescored": rescored, "overflow": overflow,
-                "fallback": overflow == 1}
+        st = engine._l2_count_stats(self._pw_stats.cpu().numpy())
+        return dict(st, fallback=st["overflow"] == 1)
 
     def _pw_plan(self):
         """After a pass that ended on the host anyway: grow this shard's band list to the reported need, or latch

@@ -332,6 +332,66 @@ def _pw_ld(t: torch.Tensor) -> int:
     return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
 
 
+def _pw_pair(a, b, name: str):
+    a, b = _pw_rows(a, name), _pw_rows(b, name)
+    if a.shape[1] != b.shape[1]:
+        raise ValueError(f"{name}: shapes {tuple(a.shape)} and {tuple(b.shape)} do not match")
+    return a, b
+
+
+def _pw_code(score_dtype) -> int:
+    return _lib.CMVE_F64 if score_dtype == torch.float64 else _lib.CMVE_F32
+
+
+def _nbytes(t: torch.Tensor) -> int:
+    return t.numel() * t.element_size()
+
+
+# ---- the Euclidean filter (K19 / K20 / K21): the rules every entry composes, each in ONE place ----
+def _l2_applies(metric: int, score_dtype) -> bool:
+    """The filter speaks for ``PW_L2`` with float64 score words and for nothing else."""
+    return metric == _lib.PW_L2 and score_dtype == torch.float64
+
+
+def _l2_scaling_ok(alpha: float, beta: float) -> bool:
+    """What the filter's C entries ask of the scaling: alpha finite and non-zero, beta finite."""
+    return alpha != 0 and bool(np.isfinite(alpha)) and bool(np.isfinite(beta))
+
+
+def _l2_set_ok(s) -> bool:
+    """Plain rows (None: packed inside the call), or a ``RowSet`` the filter's C entries take."""
+    return s is None or (s.eps == 0.0 and s.has_f16 and not s.desc.flags & _lib.PACK_RAW)
+
+
+def _stats4(names, host) -> dict:
+    """The int64 [4] counters of a filter entry, on the host, under their names."""
+    return dict(zip(names, (int(v) for v in host)))
+
+
+def _l2_count_stats(host) -> dict:
+    """{decided, band, rescored, overflow} of ``cmve_l2_count`` / ``cmve_l2_count_resolved``."""
+    return _stats4(("decided", "band", "rescored", "overflow"), host)
+
+
+def _l2_count_call(entry: str, h, a_set: "RowSet", b_set: "RowSet", alpha, beta, row, col, ws, ws_bytes: int, stats):
+    """``cmve_l2_count`` or ``cmve_l2_count_resolved`` (``entry``: one argument list).  row / col: (offsets, item
+    scores, items, n, positions) of the direction; ws: the band list's tensor, ws_bytes of it handed over."""
+    (roff, rsc, ritems, rn, rpos), (coff, csc, citems, cn, cpos) = row, col
+    check(getattr(lib, entry)(h, C.byref(a_set.desc), C.byref(b_set.desc), float(alpha), float(beta),
+                              _ptr(roff), _ptr(rsc) if ritems else None, ritems, rn, _ptr(rpos),
+                              _ptr(coff), _ptr(csc) if citems else None, citems, cn, _ptr(cpos),
+                              _ptr(ws) if ws_bytes else None, ws_bytes, _ptr(stats)), entry)
+
+
+def _item_scores_into(out, a, b, metric, alpha, beta, score_dtype, off, idx, n_items, col_dir, idx_base):
+    """``cmve_pairwise_item_scores`` of one CSR side into the caller's fp64 slice ``out``."""
+    check(lib.cmve_pairwise_item_scores(handle(a.device), _ptr(a), _dtype_code(a), _pw_ld(a), a.shape[0], _ptr(b),
+                                        _dtype_code(b), _pw_ld(b), b.shape[0], a.shape[1], metric, float(alpha),
+                                        float(beta), _pw_code(score_dtype), _ptr(off), _ptr(idx), off.numel() - 1,
+                                        int(n_items), 1 if col_dir else 0, int(idx_base), _ptr(out)),
+          "cmve_pairwise_item_scores")
+
+
 def l2_count_workspace(a: "RowSet", b: "RowSet", band_cap: int) -> int:
     """Bytes of workspace ``cmve_l2_count`` needs for a band list of ``band_cap`` pairs (host only: no launch)."""
     n = C.c_int64()
@@ -360,12 +420,10 @@ class _PairwisePositions:
 
     def __init__(self, a, b, metric, alpha, beta, score_dtype, row_lists=None, col_lists=None, filter=None):
         self.filter_stats = None
-        applies = metric == _lib.PW_L2 and score_dtype == torch.float64
+        applies = _l2_applies(metric, score_dtype)
         if filter and not applies:
             raise ValueError("pairwise_gt_positions: filter=True needs PW_L2 with float64 score words")
-        a, b = _pw_rows(a, "pairwise_gt_positions"), _pw_rows(b, "pairwise_gt_positions")
-        if a.shape[1] != b.shape[1]:
-            raise ValueError(f"pairwise_gt_positions: shapes {tuple(a.shape)} and {tuple(b.shape)} do not match")
+        a, b = _pw_pair(a, b, "pairwise_gt_positions")
         na, nb, dev = a.shape[0], b.shape[0], a.device
         if row_lists is not None and len(row_lists) != na:
             raise ValueError(f"pairwise_gt_positions: {len(row_lists)} row lists for {na} rows")
@@ -383,19 +441,17 @@ class _PairwisePositions:
             sides.append((off, idx, items, torch.empty(max(items, 1), dtype=torch.int32, device=dev)))
         (roff, ridx, ritems, rpos), (coff, cidx, citems, cpos) = sides
         if filter is None:
-            filter = (applies and na * nb >= L2_FILTER_MIN_PAIRS and alpha != 0 and np.isfinite(alpha)
-                      and np.isfinite(beta))
+            filter = applies and na * nb >= L2_FILTER_MIN_PAIRS and _l2_scaling_ok(alpha, beta)
         sc = None
         if filter and na and nb and ritems + citems:
             sc = self._filtered(a, b, alpha, beta, sides)
         if sc is None:
             nbytes = pairwise_positions_workspace(na, nb, ritems, citems, metric)
             ws = torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=dev)
-            code = _lib.CMVE_F64 if score_dtype == torch.float64 else _lib.CMVE_F32
             check(lib.cmve_pairwise_positions(handle(dev), _ptr(a), _dtype_code(a), _pw_ld(a), na, _ptr(b),
                                               _dtype_code(b), _pw_ld(b), nb, a.shape[1], metric, float(alpha),
-                                              float(beta), code, _ptr(roff), _ptr(ridx), ritems, _ptr(rpos), _ptr(coff),
-                                              _ptr(cidx), citems, _ptr(cpos), _ptr(ws), nbytes),
+                                              float(beta), _pw_code(score_dtype), _ptr(roff), _ptr(ridx), ritems,
+                                              _ptr(rpos), _ptr(coff), _ptr(cidx), citems, _ptr(cpos), _ptr(ws), nbytes),
                   "cmve_pairwise_positions")
             sc = ws.cpu().numpy()
         self._collect(sides, sc)
@@ -413,10 +469,7 @@ class _PairwisePositions:
         for off, idx, items, col_dir, n_other in ((roff, ridx, ritems, 0, nb), (coff, cidx, citems, 1, na)):
             if items:
                 out = buf[start:start + items]
-                check(lib.cmve_pairwise_item_scores(h, _ptr(a), _dtype_code(a), _pw_ld(a), na, _ptr(b), _dtype_code(b),
-                                                    _pw_ld(b), nb, a.shape[1], _lib.PW_L2, float(alpha), float(beta),
-                                                    _lib.CMVE_F64, _ptr(off), _ptr(idx), off.numel() - 1, items, col_dir,
-                                                    0, _ptr(out)), "cmve_pairwise_item_scores")
+                _item_scores_into(out, a, b, _lib.PW_L2, alpha, beta, torch.float64, off, idx, items, col_dir, 0)
                 # an index outside the other side scores NaN here (the sharded entry gives it the all-zero word)
                 out.masked_fill_((idx[:items] < 0) | (idx[:items] >= n_other), float("nan"))
             start += items
@@ -426,19 +479,16 @@ class _PairwisePositions:
         for attempt in range(2):
             nbytes = l2_count_workspace(ra, rb, cap)
             ws = torch.empty(max(nbytes // 8, 1), dtype=torch.int64, device=dev)
-            check(lib.cmve_l2_count(h, C.byref(ra.desc), C.byref(rb.desc), float(alpha), float(beta),
-                                    _ptr(roff), _ptr(rsc) if ritems else None, ritems, nb, _ptr(rpos),
-                                    _ptr(coff), _ptr(csc) if citems else None, citems, na, _ptr(cpos),
-                                    _ptr(ws), nbytes, _ptr(stats)), "cmve_l2_count")
+            _l2_count_call("cmve_l2_count", h, ra, rb, alpha, beta, (roff, rsc, ritems, nb, rpos),
+                           (coff, csc, citems, na, cpos), ws, nbytes, stats)
             host = buf.cpu().numpy()
-            decided, band, rescored, overflow = (int(v) for v in host[ritems + citems:].view(np.int64))
-            self.filter_stats = {"decided": decided, "band": band, "rescored": rescored, "overflow": overflow,
-                                 "redone": attempt > 0, "fallback": False}
-            if not overflow:
+            st = _l2_count_stats(host[ritems + citems:].view(np.int64))
+            self.filter_stats = dict(st, redone=attempt > 0, fallback=False)
+            if not st["overflow"]:
                 return host[:ritems + citems]
-            if attempt or band * 8 > pairs:
+            cap = l2_band_plan(pairs, st["band"], st["overflow"], cap)  # (the call zeroes the positions again)
+            if attempt or cap is None:
                 break
-            cap = band  # the positions are zeroed again by the call itself
         self.filter_stats["fallback"] = True
         return None
 
@@ -500,17 +550,6 @@ def pairwise_gt_eval(a, b, metric: int, alpha: float, beta: float, score_dtype, 
     return (r.positions(0), r.ranks(0)), (r.positions(1), r.ranks(1))
 
 
-def _pw_pair(a, b, name: str):
-    a, b = _pw_rows(a, name), _pw_rows(b, name)
-    if a.shape[1] != b.shape[1]:
-        raise ValueError(f"{name}: shapes {tuple(a.shape)} and {tuple(b.shape)} do not match")
-    return a, b
-
-
-def _pw_code(score_dtype) -> int:
-    return _lib.CMVE_F64 if score_dtype == torch.float64 else _lib.CMVE_F32
-
-
 def pairwise_item_scores(a, b, metric: int, alpha: float, beta: float, score_dtype, off: torch.Tensor,
                          idx: torch.Tensor, n_items: int, col_dir: bool = False, idx_base: int = 0) -> torch.Tensor:
     """fp64 [n_items] on the device: the score of every listed item this call owns (``cmve_pairwise_item_scores``,
@@ -522,11 +561,7 @@ def pairwise_item_scores(a, b, metric: int, alpha: float, beta: float, score_dty
     if idx.numel() < int(n_items) or idx.dtype != torch.int32 or off.dtype != torch.int64:
         raise ValueError(f"pairwise_item_scores: {n_items} items need int64 offsets and as many int32 indices")
     out = torch.empty(max(int(n_items), 1), dtype=torch.float64, device=a.device)
-    check(lib.cmve_pairwise_item_scores(handle(a.device), _ptr(a), _dtype_code(a), _pw_ld(a), a.shape[0], _ptr(b),
-                                        _dtype_code(b), _pw_ld(b), b.shape[0], a.shape[1], metric, float(alpha),
-                                        float(beta), _pw_code(score_dtype), _ptr(off), _ptr(idx),
-                                        off.numel() - 1, int(n_items), 1 if col_dir else 0, int(idx_base), _ptr(out)),
-          "cmve_pairwise_item_scores")
+    _item_scores_into(out, a, b, metric, alpha, beta, score_dtype, off, idx, n_items, col_dir, idx_base)
     return out[:int(n_items)]
 
 
@@ -544,10 +579,6 @@ def l2_band_plan(pairs: int, band: int, overflow, cap: int) -> Optional[int]:
     if not overflow:
         return int(cap)
     return int(band) if int(band) * 8 <= int(pairs) else None
-
-
-def _l2_set_ok(s) -> bool:
-    return s is None or (s.eps == 0.0 and s.has_f16 and not s.desc.flags & _lib.PACK_RAW)
 
 
 def pairwise_count(a, b, metric: int, alpha: float, beta: float, score_dtype, row=None, col=None,
@@ -568,8 +599,7 @@ def pairwise_count(a, b, metric: int, alpha: float, beta: float, score_dtype, ro
     list, one slot per element (None: a fresh one of ``l2_band_cap(na * nb)`` slots).  ``return_stats``: also return
     the int64 [4] DEVICE tensor {decided, band found, band re-scored, overflow} (``l2_band_plan`` reads it once the
     caller has it on the host), or None when the filter did not run."""
-    applies = (metric == _lib.PW_L2 and score_dtype == torch.float64 and alpha != 0 and bool(np.isfinite(alpha))
-               and bool(np.isfinite(beta)))
+    applies = _l2_applies(metric, score_dtype) and _l2_scaling_ok(alpha, beta)
     if filter and not applies:
         raise ValueError("pairwise_count: filter=True needs PW_L2 with float64 score words, alpha finite and "
                          "non-zero, beta finite")
@@ -602,11 +632,8 @@ def pairwise_count(a, b, metric: int, alpha: float, beta: float, score_dtype, ro
         if band is None:
             band = torch.empty(l2_band_cap(na * nb), dtype=torch.int64, device=dev)
         stats = torch.empty(4, dtype=torch.int64, device=dev)
-        check(lib.cmve_l2_count_resolved(handle(dev), C.byref(a_set.desc), C.byref(b_set.desc), float(alpha),
-                                         float(beta), _ptr(roff), _ptr(rsc) if ritems else None, ritems, rn,
-                                         _ptr(rpos), _ptr(coff), _ptr(csc) if citems else None, citems, cn,
-                                         _ptr(cpos), _ptr(band) if band.numel() else None, 8 * band.numel(),
-                                         _ptr(stats)), "cmve_l2_count_resolved")
+        _l2_count_call("cmve_l2_count_resolved", handle(dev), a_set, b_set, alpha, beta, sides[0], sides[1], band,
+                       _nbytes(band), stats)
     else:
         check(lib.cmve_pairwise_count(handle(dev), _ptr(a), _dtype_code(a), _pw_ld(a), na, _ptr(b), _dtype_code(b),
                                       _pw_ld(b), nb, a.shape[1], metric, float(alpha), float(beta),
@@ -678,16 +705,14 @@ def l2_topk(q: "RowSet", g: "RowSet", alpha: float, beta: float, k: int, cand_ca
     cap = L2_TOPK_CAND_MAX if cand_cap is None else int(cand_cap)
     nbytes = l2_topk_workspace(q, g, k, cap, sample_rows)
     dev = g.device
-    if ws is None or ws.numel() * ws.element_size() < nbytes or ws.data_ptr() % 8:
+    if ws is None or _nbytes(ws) < nbytes or ws.data_ptr() % 8:
         ws = torch.empty(max(nbytes // 8, 1), dtype=torch.int64, device=dev)
     idx = torch.empty((q.n, int(k)), dtype=torch.int64, device=dev)
     err = torch.empty((q.n, int(k)), dtype=torch.float64, device=dev)
     st = torch.empty(4, dtype=torch.int64, device=dev)
     check(lib.cmve_l2_topk(handle(dev), C.byref(q.desc), C.byref(g.desc), float(alpha), float(beta), int(k), cap,
                            int(sample_rows or 0), _ptr(ws), nbytes, _ptr(idx), _ptr(err), _ptr(st)), "cmve_l2_topk")
-    excluded, found, rescored, unresolved = (int(v) for v in st.cpu().numpy())
-    stats = {"excluded": excluded, "candidates": found, "rescored": rescored, "unresolved": unresolved}
-    return idx, err, stats
+    return idx, err, _stats4(("excluded", "candidates", "rescored", "unresolved"), st.cpu().numpy())
 
 
 def _topk_filtered(q, g, alpha, beta, k, cand_cap, sample_rows, ws=None):
@@ -731,12 +756,9 @@ def pairwise_topk(q, g, metric: int, alpha: float, beta: float, score_dtype, k: 
     rescored, unresolved, fallback_rows, fallback}, or None when the filter was not tried."""
     g_set = g if isinstance(g, RowSet) else None
     q_set = q if isinstance(q, RowSet) else None
-    q = q_set.raw if q_set is not None else _pw_rows(q, "pairwise_topk")
-    g = g_set.raw if g_set is not None else _pw_rows(g, "pairwise_topk")
-    if q.shape[1] != g.shape[1]:
-        raise ValueError(f"pairwise_topk: shapes {tuple(q.shape)} and {tuple(g.shape)} do not match")
+    q, g = _pw_pair(q_set.raw if q_set is not None else q, g_set.raw if g_set is not None else g, "pairwise_topk")
     n_q, n_g = q.shape[0], g.shape[0]
-    applies = metric == _lib.PW_L2 and score_dtype == torch.float64
+    applies = _l2_applies(metric, score_dtype)
     if filter and not applies:
         raise ValueError("pairwise_topk: filter=True needs PW_L2 with float64 score words")
 
@@ -750,10 +772,8 @@ def pairwise_topk(q, g, metric: int, alpha: float, beta: float, score_dtype, k: 
     if k > _lib.TOPK_MAX:
         raise ValueError(f"pairwise_topk: k <= {_lib.TOPK_MAX}")
     if filter is None:  # auto never hands the entry what it refuses; filter=True does, and the entry says so
-        filter = (applies and l2_topk_auto(n_q, n_g, g_set is not None) and alpha != 0 and np.isfinite(alpha)
-                  and np.isfinite(beta)
-                  and all(s is None or (s.eps == 0.0 and s.has_f16 and not s.desc.flags & _lib.PACK_RAW)
-                          for s in (q_set, g_set)))
+        filter = (applies and l2_topk_auto(n_q, n_g, g_set is not None) and _l2_scaling_ok(alpha, beta)
+                  and _l2_set_ok(q_set) and _l2_set_ok(g_set))
     topk_stats = None
     if filter and n_q > 0 and k <= L2_TOPK_CAND_MAX:
         if g_set is None:
@@ -763,16 +783,15 @@ def pairwise_topk(q, g, metric: int, alpha: float, beta: float, score_dtype, k: 
         if idx is not None:
             return result(idx, err, topk_stats)
     lo, rec = pairwise_topk_workspace(n_q, n_g, k, metric)
-    if ws is None or (topk_stats is not None and ws.numel() * ws.element_size() < lo):
+    if ws is None or (topk_stats is not None and _nbytes(ws) < lo):
         ws = torch.empty(max(rec if ws_bytes is None else int(ws_bytes), 8), dtype=torch.uint8, device=q.device)
-    if ws.numel() * ws.element_size() < lo:
-        raise ValueError(f"pairwise_topk: workspace of {ws.numel() * ws.element_size()} bytes < minimum {lo}")
+    if _nbytes(ws) < lo:
+        raise ValueError(f"pairwise_topk: workspace of {_nbytes(ws)} bytes < minimum {lo}")
     idx = torch.empty((n_q, k), dtype=torch.int64, device=q.device)
     err = torch.empty((n_q, k), dtype=torch.float64, device=q.device)
-    code = _lib.CMVE_F64 if score_dtype == torch.float64 else _lib.CMVE_F32
     check(lib.cmve_pairwise_topk(handle(q.device), _ptr(q), _dtype_code(q), _pw_ld(q), n_q, _ptr(g), _dtype_code(g),
-                                 _pw_ld(g), n_g, q.shape[1], metric, float(alpha), float(beta), code, k,
-                                 int(geometry), _ptr(ws), ws.numel() * ws.element_size(), _ptr(idx), _ptr(err)),
+                                 _pw_ld(g), n_g, q.shape[1], metric, float(alpha), float(beta),
+                                 _pw_code(score_dtype), k, int(geometry), _ptr(ws), _nbytes(ws), _ptr(idx), _ptr(err)),
           "cmve_pairwise_topk")
     return result(idx, err, topk_stats)
 

@@ -79,8 +79,8 @@ __global__ __launch_bounds__(256, 2) void l2f_main_kernel(L2fArgs a) {
   if (tid < L2F_BM) {
     const int64_t i = i0 + tid;
     const bool v = i < a.na;
-    E.an[tid] = v ? 1.0 / a.a_inv[i] : (double)NAN;
-    E.ae[tid] = v ? (double)a.a_err[i] + a.c.theta : (double)NAN;
+    E.an[tid] = l2f_side_norm(i, v, a.a_inv);
+    E.ae[tid] = l2f_side_err(i, v, a.a_err, a.c.theta);
     const int64_t o = (v && a.row_pos) ? a.row_off[i] : 0;
     const int m = (v && a.row_pos) ? (int)(a.row_off[i + 1] - o) : 0;
     E.ro[tid] = o;
@@ -91,8 +91,8 @@ __global__ __launch_bounds__(256, 2) void l2f_main_kernel(L2fArgs a) {
     const int t = tid - L2F_BM;
     const int64_t j = j0 + t;
     const bool v = j < a.nb;
-    E.bn[t] = v ? 1.0 / a.b_inv[j] : (double)NAN;
-    E.be[t] = v ? (double)a.b_err[j] + a.c.theta : (double)NAN;
+    E.bn[t] = l2f_side_norm(j, v, a.b_inv);
+    E.be[t] = l2f_side_err(j, v, a.b_err, a.c.theta);
     const int64_t o = (v && a.col_pos) ? a.col_off[j] : 0;
     const int m = (v && a.col_pos) ? (int)(a.col_off[j + 1] - o) : 0;
     E.co[t] = o;
@@ -342,22 +342,8 @@ static int l2_count_run(const char* name, bool resolved, cmve_handle_t h, const 
   CMVE_REQUIRE(h && a && b && stats, "%s: NULL argument", name);
   CMVE_REQUIRE(alpha != 0.0 && std::isfinite(alpha) && std::isfinite(beta),
                "%s: alpha must be finite and non-zero, beta finite (%g, %g)", name, alpha, beta);
-  CMVE_REQUIRE(a->d > 0 && a->d == b->d && a->d_pad == b->d_pad, "%s: dimensions differ (%lld, %lld)", name,
-               (long long)a->d, (long long)b->d);
-  CMVE_REQUIRE(a->h16 && b->h16 && a->err_h16 && b->err_h16, "%s: a set was packed without its fp16 plane", name);
-  CMVE_REQUIRE(a->eps == 0.0 && b->eps == 0.0, "%s: the sets must be packed with eps = 0", name);
-  CMVE_REQUIRE(!(a->flags & CMVE_PACK_RAW) && !(b->flags & CMVE_PACK_RAW),
-               "%s: CMVE_PACK_RAW sets hold no unit rows", name);
+  if (int rc = l2f_check_sets(name, a, b)) return rc;
   const int64_t na = a->n, nb = b->n, d = a->d;
-  CMVE_REQUIRE(na >= 0 && nb >= 0 && na < (1ll << 31) && nb < (1ll << 31) && a->n_pad >= na && b->n_pad >= nb &&
-                   a->n_pad % CMVE_ROW_ALIGN == 0 && b->n_pad % CMVE_ROW_ALIGN == 0 && a->d_pad >= d &&
-                   a->d_pad % CMVE_DIM_ALIGN == 0,
-               "%s: bad shape", name);
-  CMVE_REQUIRE((a->raw || !na) && (b->raw || !nb) && a->inv_norm && b->inv_norm && a->raw_ld >= d && b->raw_ld >= d,
-               "%s: the sets' raw rows are missing", name);
-  CMVE_REQUIRE((a->raw_dtype == CMVE_F32 || a->raw_dtype == CMVE_F64) &&
-                   (b->raw_dtype == CMVE_F32 || b->raw_dtype == CMVE_F64),
-               "%s: raw rows must be CMVE_F32/CMVE_F64", name);
   if (!row_pos) row_items = 0;
   if (!col_pos) col_items = 0;
   CMVE_REQUIRE(row_items >= 0 && col_items >= 0 && row_n >= 0 && col_n >= 0 && row_n < (1ll << 31) &&
@@ -410,17 +396,13 @@ static int l2_count_run(const char* name, bool resolved, cmve_handle_t h, const 
   g.tiles_b = (int)tiles_b;
   hipLaunchKernelGGL(l2f_main_kernel, dim3((unsigned)(tiles_a * tiles_b)), dim3(256), 0, st, g);
   const int fix_blocks = (int)std::max<int64_t>(1, std::min<int64_t>(8 * device_cus(), (g.cap + 255) / 256));
-#define L2F_FIX(TA, TB)                                                                                              \
-  hipLaunchKernelGGL((l2f_fixup_kernel<TA, TB>), dim3((unsigned)fix_blocks), dim3(256), 0, st, (const TA*)a->raw,    \
-                     a->raw_ld, (const TB*)b->raw, b->raw_ld, d, alpha, beta, row_off, row_sc, g.row_pos, col_off,   \
-                     col_sc, g.col_pos, (const int2*)g.band, g.cap, g.stats)
   if (g.cap > 0) {
-    if (a->raw_dtype == CMVE_F64 && b->raw_dtype == CMVE_F64) L2F_FIX(double, double);
-    else if (a->raw_dtype == CMVE_F64) L2F_FIX(double, float);
-    else if (b->raw_dtype == CMVE_F64) L2F_FIX(float, double);
-    else L2F_FIX(float, float);
+    PWR_TYPES(a->raw_dtype, b->raw_dtype, TA, TB, {
+      hipLaunchKernelGGL((l2f_fixup_kernel<TA, TB>), dim3((unsigned)fix_blocks), dim3(256), 0, st, (const TA*)a->raw,
+                         a->raw_ld, (const TB*)b->raw, b->raw_ld, d, alpha, beta, row_off, row_sc, g.row_pos, col_off,
+                         col_sc, g.col_pos, (const int2*)g.band, g.cap, g.stats);
+    })
   }
-#undef L2F_FIX
   if (resolved) {
     // the list overflowed (decided on the device: both launches do nothing otherwise): the words so far are
     // dropped and cmve_pairwise_count's kernel counts every pair on the canonical chain, NaN items included

@@ -40,6 +40,36 @@ static inline L2fConsts l2f_consts(int64_t d, int64_t d_pad) {
   return c;
 }
 
+// What every filter entry asks of its two packed sets (host): the refusals name the entry.
+static inline int l2f_check_sets(const char* name, const cmve_rows_t* a, const cmve_rows_t* b) {
+  CMVE_REQUIRE(a->d > 0 && a->d == b->d && a->d_pad == b->d_pad, "%s: dimensions differ (%lld, %lld)", name,
+               (long long)a->d, (long long)b->d);
+  CMVE_REQUIRE(a->h16 && b->h16 && a->err_h16 && b->err_h16, "%s: a set was packed without its fp16 plane", name);
+  CMVE_REQUIRE(a->eps == 0.0 && b->eps == 0.0, "%s: the sets must be packed with eps = 0", name);
+  CMVE_REQUIRE(!(a->flags & CMVE_PACK_RAW) && !(b->flags & CMVE_PACK_RAW),
+               "%s: CMVE_PACK_RAW sets hold no unit rows", name);
+  const int64_t na = a->n, nb = b->n, d = a->d;
+  CMVE_REQUIRE(na >= 0 && nb >= 0 && na < (1ll << 31) && nb < (1ll << 31) && a->n_pad >= na && b->n_pad >= nb &&
+                   a->n_pad % CMVE_ROW_ALIGN == 0 && b->n_pad % CMVE_ROW_ALIGN == 0 && a->d_pad >= d &&
+                   a->d_pad % CMVE_DIM_ALIGN == 0,
+               "%s: bad shape", name);
+  CMVE_REQUIRE((a->raw || !na) && (b->raw || !nb) && a->inv_norm && b->inv_norm && a->raw_ld >= d && b->raw_ld >= d,
+               "%s: the sets' raw rows are missing", name);
+  CMVE_REQUIRE((a->raw_dtype == CMVE_F32 || a->raw_dtype == CMVE_F64) &&
+                   (b->raw_dtype == CMVE_F32 || b->raw_dtype == CMVE_F64),
+               "%s: raw rows must be CMVE_F32/CMVE_F64", name);
+  return CMVE_OK;
+}
+
+// The epilogues' side load of one tile row as l2f_interval takes it: the row's norm (from 1 / inv_norm) and its error
+// (err_h16 + theta); NaN for a row beyond the set (no interval: its pairs are never decided)
+__device__ __forceinline__ double l2f_side_norm(int64_t row, bool valid, const double* inv_norm) {
+  return valid ? 1.0 / inv_norm[row] : (double)NAN;
+}
+__device__ __forceinline__ double l2f_side_err(int64_t row, bool valid, const float* err_h16, double theta) {
+  return valid ? (double)err_h16[row] + theta : (double)NAN;
+}
+
 // The item word t mapped back to squared-distance space (DESIGN s4, K19).  A pair of true squared distance D has
 // e(i, j) < t whenever   alpha > 0: D < tb,   alpha < 0: D > tb   and  e(i, j) >= t  whenever  alpha > 0: D > tn,
 // alpha < 0: D < tn.  x = (t - beta) / alpha is the distance at which the real-number score equals t; sig covers the

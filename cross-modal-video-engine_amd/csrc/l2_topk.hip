@@ -86,8 +86,8 @@ __global__ __launch_bounds__(256, 2) void l2t_pass_kernel(L2tArgs a) {
   if (tid < L2F_BM) {
     const int64_t i = i0 + tid;
     const bool v = i < a.q_end;
-    E.qn[tid] = v ? 1.0 / a.q_inv[i] : (double)NAN;
-    E.qe[tid] = v ? (double)a.q_err[i] + a.c.theta : (double)NAN;
+    E.qn[tid] = l2f_side_norm(i, v, a.q_inv);
+    E.qe[tid] = l2f_side_err(i, v, a.q_err, a.c.theta);
     if (MODE == 1) {
       E.thr[tid] = v ? a.thr[i - a.q0] : (double)NAN;
       // An overflowed list is lost (launch C asks only whether the counter exceeds cap), so its row stops appending:
@@ -100,8 +100,8 @@ __global__ __launch_bounds__(256, 2) void l2t_pass_kernel(L2tArgs a) {
     const int t = tid - L2F_BM;
     const int64_t j = j0 + t;
     const bool v = j < a.ng;
-    E.gn[t] = v ? 1.0 / a.g_inv[j] : (double)NAN;
-    E.ge[t] = v ? (double)a.g_err[j] + a.c.theta : (double)NAN;
+    E.gn[t] = l2f_side_norm(j, v, a.g_inv);
+    E.ge[t] = l2f_side_err(j, v, a.g_err, a.c.theta);
   }
   if (tid == 0) E.n_cand = E.n_excl = 0;
   __syncthreads();
@@ -328,6 +328,16 @@ L2tLayout l2t_layout(int64_t n_q, int64_t n_g, int32_t k, int64_t cand_cap, int6
   return l;
 }
 
+// what both top-k entries ask of k / cand_cap / sample_rows (the refusals name the entry)
+int l2t_check_params(const char* name, int32_t k, int64_t cand_cap, int64_t sample_rows) {
+  CMVE_REQUIRE(k >= 1, "%s: k must be at least 1 (%d)", name, k);
+  CMVE_REQUIRE(cand_cap >= k && cand_cap <= L2T_CAND_MAX, "%s: cand_cap must be in [k, %d] (%lld, k %d)", name,
+               L2T_CAND_MAX, (long long)cand_cap, k);
+  CMVE_REQUIRE(sample_rows >= 0 && sample_rows < (1ll << 31), "%s: bad sample_rows (%lld)", name,
+               (long long)sample_rows);
+  return CMVE_OK;
+}
+
 }  // namespace
 }  // namespace cmve
 
@@ -336,12 +346,7 @@ using namespace cmve;
 extern "C" int cmve_l2_topk_workspace(const cmve_rows_t* q, const cmve_rows_t* g, int32_t k, int64_t cand_cap,
                                       int64_t sample_rows, int64_t* bytes) {
   CMVE_REQUIRE(q && g && bytes, "cmve_l2_topk_workspace: NULL argument");
-  CMVE_REQUIRE(k >= 1, "cmve_l2_topk_workspace: k must be at least 1 (%d)", k);
-  CMVE_REQUIRE(cand_cap >= k && cand_cap <= L2T_CAND_MAX,
-               "cmve_l2_topk_workspace: cand_cap must be in [k, %d] (%lld, k %d)", L2T_CAND_MAX, (long long)cand_cap,
-               k);
-  CMVE_REQUIRE(sample_rows >= 0 && sample_rows < (1ll << 31), "cmve_l2_topk_workspace: bad sample_rows (%lld)",
-               (long long)sample_rows);
+  if (int rc = l2t_check_params("cmve_l2_topk_workspace", k, cand_cap, sample_rows)) return rc;
   CMVE_REQUIRE(q->n >= 0 && g->n >= 0 && q->n < (1ll << 31) && g->n < (1ll << 31) && q->d > 0 && q->d == g->d,
                "cmve_l2_topk_workspace: bad shape (%lld x %lld, %lld x %lld)", (long long)q->n, (long long)q->d,
                (long long)g->n, (long long)g->d);
@@ -355,28 +360,10 @@ extern "C" int cmve_l2_topk(cmve_handle_t h, const cmve_rows_t* q, const cmve_ro
   CMVE_REQUIRE(h && q && g && stats, "cmve_l2_topk: NULL argument");
   CMVE_REQUIRE(alpha != 0.0 && std::isfinite(alpha) && std::isfinite(beta),
                "cmve_l2_topk: alpha must be finite and non-zero, beta finite (%g, %g)", alpha, beta);
-  CMVE_REQUIRE(k >= 1, "cmve_l2_topk: k must be at least 1 (%d)", k);
-  CMVE_REQUIRE(cand_cap >= k && cand_cap <= L2T_CAND_MAX, "cmve_l2_topk: cand_cap must be in [k, %d] (%lld, k %d)",
-               L2T_CAND_MAX, (long long)cand_cap, k);
-  CMVE_REQUIRE(sample_rows >= 0 && sample_rows < (1ll << 31), "cmve_l2_topk: bad sample_rows (%lld)",
-               (long long)sample_rows);
-  CMVE_REQUIRE(q->d > 0 && q->d == g->d && q->d_pad == g->d_pad, "cmve_l2_topk: dimensions differ (%lld, %lld)",
-               (long long)q->d, (long long)g->d);
-  CMVE_REQUIRE(q->h16 && g->h16 && q->err_h16 && g->err_h16, "cmve_l2_topk: a set was packed without its fp16 plane");
-  CMVE_REQUIRE(q->eps == 0.0 && g->eps == 0.0, "cmve_l2_topk: the sets must be packed with eps = 0");
-  CMVE_REQUIRE(!(q->flags & CMVE_PACK_RAW) && !(g->flags & CMVE_PACK_RAW),
-               "cmve_l2_topk: CMVE_PACK_RAW sets hold no unit rows");
+  if (int rc = l2t_check_params("cmve_l2_topk", k, cand_cap, sample_rows)) return rc;
+  if (int rc = l2f_check_sets("cmve_l2_topk", q, g)) return rc;
   const int64_t n_q = q->n, n_g = g->n, d = q->d;
-  CMVE_REQUIRE(n_q >= 0 && n_g >= 0 && n_q < (1ll << 31) && n_g < (1ll << 31) && q->n_pad >= n_q && g->n_pad >= n_g &&
-                   q->n_pad % CMVE_ROW_ALIGN == 0 && g->n_pad % CMVE_ROW_ALIGN == 0 && q->d_pad >= d &&
-                   q->d_pad % CMVE_DIM_ALIGN == 0,
-               "cmve_l2_topk: bad shape");
   CMVE_REQUIRE(k <= n_g || n_q == 0, "cmve_l2_topk: k exceeds the gallery (%d > %lld): clamp it", k, (long long)n_g);
-  CMVE_REQUIRE((q->raw || !n_q) && (g->raw || !n_g) && q->inv_norm && g->inv_norm && q->raw_ld >= d && g->raw_ld >= d,
-               "cmve_l2_topk: the sets' raw rows are missing");
-  CMVE_REQUIRE((q->raw_dtype == CMVE_F32 || q->raw_dtype == CMVE_F64) &&
-                   (g->raw_dtype == CMVE_F32 || g->raw_dtype == CMVE_F64),
-               "cmve_l2_topk: raw rows must be CMVE_F32/CMVE_F64");
   CMVE_REQUIRE((out_idx && out_err) || !n_q, "cmve_l2_topk: NULL output");
   const L2tLayout l = l2t_layout(n_q, n_g, k, cand_cap, sample_rows);
   CMVE_REQUIRE(n_q == 0 || (ws && ws_bytes >= l.bytes), "cmve_l2_topk: workspace too small (%lld < %lld bytes)",
@@ -417,15 +404,11 @@ extern "C" int cmve_l2_topk(cmve_handle_t h, const cmve_rows_t* q, const cmve_ro
     a.ng = n_g;
     a.tiles_b = (int)tiles_g;
     hipLaunchKernelGGL(l2t_pass_kernel<1>, dim3((unsigned)(a.tiles_a * tiles_g)), dim3(256), 0, st, a);
-#define L2T_FIN(TA, TB)                                                                                              \
-  hipLaunchKernelGGL((l2t_finish_kernel<TA, TB>), dim3((unsigned)nq), dim3(256), 0, st, (const TA*)q->raw,           \
-                     q->raw_ld, (const TB*)g->raw, g->raw_ld, d, alpha, beta, q0, (const double*)thr,                \
-                     (const int32_t*)a.cnt, (const int32_t*)a.list, cand_cap, (int)k, out_idx, out_err, a.stats)
-    if (q->raw_dtype == CMVE_F64 && g->raw_dtype == CMVE_F64) L2T_FIN(double, double);
-    else if (q->raw_dtype == CMVE_F64) L2T_FIN(double, float);
-    else if (g->raw_dtype == CMVE_F64) L2T_FIN(float, double);
-    else L2T_FIN(float, float);
-#undef L2T_FIN
+    PWR_TYPES(q->raw_dtype, g->raw_dtype, TA, TB, {
+      hipLaunchKernelGGL((l2t_finish_kernel<TA, TB>), dim3((unsigned)nq), dim3(256), 0, st, (const TA*)q->raw,
+                         q->raw_ld, (const TB*)g->raw, g->raw_ld, d, alpha, beta, q0, (const double*)thr,
+                         (const int32_t*)a.cnt, (const int32_t*)a.list, cand_cap, (int)k, out_idx, out_err, a.stats);
+    })
     if (int rc = check_launch("l2_topk")) return rc;
   }
   return CMVE_OK;

@@ -64,35 +64,13 @@ extern "C" int cmve_pairwise(cmve_handle_t h, const void* A, int32_t a_dtype, in
   if (na == 0 || nb == 0) return CMVE_OK;
   CMVE_REQUIRE((na + PW_TA - 1) / PW_TA < 65536, "cmve_pairwise: too many rows in A (%lld)", (long long)na);
   const dim3 grid((unsigned)((nb + PW_TB - 1) / PW_TB), (unsigned)((na + PW_TA - 1) / PW_TA));
-#define PW_LAUNCH(TA, TB, TO, M)                                                                            \
+#define PW_LAUNCH(TO)                                                                                       \
   hipLaunchKernelGGL((pairwise_kernel<TA, TB, TO, M>), grid, dim3(256), 0, h->stream, (const TA*)A, lda, na, \
                      (const TB*)B, ldb, nb, d, alpha, beta, (TO*)out, ldo)
-#define PW_METRIC(TA, TB, TO)                                          \
-  switch (metric) {                                                    \
-    case CMVE_PW_SQ_L2: PW_LAUNCH(TA, TB, TO, CMVE_PW_SQ_L2); break;   \
-    case CMVE_PW_L2: PW_LAUNCH(TA, TB, TO, CMVE_PW_L2); break;         \
-    case CMVE_PW_L1: PW_LAUNCH(TA, TB, TO, CMVE_PW_L1); break;         \
-    case CMVE_PW_ORDER: PW_LAUNCH(TA, TB, TO, CMVE_PW_ORDER); break;   \
-    case CMVE_PW_DOT: PW_LAUNCH(TA, TB, TO, CMVE_PW_DOT); break;       \
-    default: PW_LAUNCH(TA, TB, TO, CMVE_PW_JACCARD); break;            \
-  }
-#define PW_OUT(TA, TB)              \
-  if (out_dtype == CMVE_F64) {      \
-    PW_METRIC(TA, TB, double)       \
-  } else {                          \
-    PW_METRIC(TA, TB, float)        \
-  }
-  if (a_dtype == CMVE_F64 && b_dtype == CMVE_F64) {
-    PW_OUT(double, double)
-  } else if (a_dtype == CMVE_F64) {
-    PW_OUT(double, float)
-  } else if (b_dtype == CMVE_F64) {
-    PW_OUT(float, double)
-  } else {
-    PW_OUT(float, float)
-  }
-#undef PW_OUT
-#undef PW_METRIC
+  PW_DISPATCH_METRIC(metric, M, PWR_TYPES(a_dtype, b_dtype, TA, TB, {
+    if (out_dtype == CMVE_F64) PW_LAUNCH(double);
+    else PW_LAUNCH(float);
+  }))
 #undef PW_LAUNCH
   return check_launch("pairwise");
 }

@@ -275,13 +275,6 @@ static int64_t pwr_segments(int64_t n_q, int64_t n_g, int64_t k) {
 static int64_t pwr_seg_lists_bytes(int64_t nk, int64_t S) { return (2 * S + 4) * nk * 8; }
 constexpr int PWR_KMAX = 2048;  // K12f's limit (TD_KMAX, topk.hip): TOPK_MAX of the Python binding
 
-// PWR_TYPES(a, b, TA, TB, stmt): stmt with the element types of the two sides
-#define PWR_TYPES(a_dtype, b_dtype, TA, TB, ...)                                    \
-  if (a_dtype == CMVE_F64 && b_dtype == CMVE_F64) { using TA = double; using TB = double; __VA_ARGS__; } \
-  else if (a_dtype == CMVE_F64) { using TA = double; using TB = float; __VA_ARGS__; }                    \
-  else if (b_dtype == CMVE_F64) { using TA = float; using TB = double; __VA_ARGS__; }                    \
-  else { using TA = float; using TB = float; __VA_ARGS__; }
-
 // ---- the best-GT rank of every list from its items' scores and positions (one thread per list) ------------------
 // 1 + the least position over the non-NaN items; an empty list ranks n_m + 1, a list whose items all score NaN n_m
 // (cmve_rank_from_matrix's rules, metrics.py:137-147)

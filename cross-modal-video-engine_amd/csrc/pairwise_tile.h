@@ -134,6 +134,12 @@ __device__ __forceinline__ void pw_tile_loop(const TA* __restrict__ A, int64_t l
     case CMVE_PW_DOT: { constexpr int M = CMVE_PW_DOT; __VA_ARGS__; } break;      \
     default: { constexpr int M = CMVE_PW_JACCARD; __VA_ARGS__; } break;           \
   }
+// PWR_TYPES(a, b, TA, TB, stmt): stmt with the element types of the two sides (CMVE_F32 / CMVE_F64 each)
+#define PWR_TYPES(a_dtype, b_dtype, TA, TB, ...)                                    \
+  if (a_dtype == CMVE_F64 && b_dtype == CMVE_F64) { using TA = double; using TB = double; __VA_ARGS__; } \
+  else if (a_dtype == CMVE_F64) { using TA = double; using TB = float; __VA_ARGS__; }                    \
+  else if (b_dtype == CMVE_F64) { using TA = float; using TB = double; __VA_ARGS__; }                    \
+  else { using TA = float; using TB = float; __VA_ARGS__; }
 
 }  // namespace cmve
 #endif

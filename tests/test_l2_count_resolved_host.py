@@ -97,3 +97,10 @@ def test_sharded_filter_true_needs_a_euclidean_measure(m):
 
     with pytest.raises(ValueError, match="Euclidean"):
         ShardedGallery(np.zeros((4, 8), np.float32), offset=0, n_global=4, comm=NoComm(), measure=m, filter=True)
+
+
+def test_one_decoder_names_the_four_counters():
+    from cmve import engine
+    st = engine._l2_count_stats(np.array([7, 5, 3, 1], np.int64))
+    assert st == {"decided": 7, "band": 5, "rescored": 3, "overflow": 1}
+    assert list(st) == ["decided", "band", "rescored", "overflow"] and all(type(v) is int for v in st.values())

@@ -69,3 +69,20 @@ def test_engine_wrapper_and_filter_argument_need_no_gpu():
     for f in (engine.pairwise_gt_positions, engine.pairwise_gt_ranks, engine.pairwise_gt_eval,
               engine._PairwisePositions.__init__):
         assert inspect.signature(f).parameters["filter"].default is None
+
+
+def test_each_entry_refuses_a_set_without_its_fp16_plane_under_its_own_name():
+    """The checks on the two sets are shared by the three entries (l2f_check_sets); the refusal still begins with
+    the name of the entry that was called.  Every check runs before the handle is used, so a host buffer stands in
+    for it and nothing is launched."""
+    from cmve import _lib
+    a, b = _rows(300, 67), _rows(520, 67)  # h16 / err_h16 are NULL: packed without the fp16 plane
+    h = C.create_string_buffer(256)
+    stats = (C.c_int64 * 4)()
+    lib = _lib.lib
+    for name in ("cmve_l2_count", "cmve_l2_count_resolved"):
+        rc = getattr(lib, name)(h, C.byref(a), C.byref(b), 1.0, 0.0, None, None, 0, 0, None, None, None, 0, 0, None,
+                                None, 0, stats)
+        assert rc < 0 and _err().startswith(name.encode() + b": a set was packed without its fp16 plane"), _err()
+    rc = lib.cmve_l2_topk(h, C.byref(a), C.byref(b), 1.0, 0.0, 10, 2048, 0, None, 0, None, None, stats)
+    assert rc < 0 and _err().startswith(b"cmve_l2_topk: a set was packed without its fp16 plane"), _err()
