@@ -408,6 +408,119 @@ def l2_count_workspace(a: "RowSet", b: "RowSet", band_cap: int) -> int:
 L2_FILTER_MIN_PAIRS = 4096 * 4096
 
 
+# ---- the SAD filter of the L1 measures (K22): the rules every entry composes, each in ONE place ----
+L1_D_MAX = 65536  # cmve_l1_count's limit on d: the u32 SAD of uint16 codes is exact up to there
+# Auto dispatch of the K22 filter (``filter=None``): the smallest na * nb at which it beats the fp64 route by more
+# than the two routes' combined spread (None would mean: never taken automatically, ``filter="l1"`` alone runs it).
+# tools/l1_filter_bench.py measures both routes at na = nb in {256 .. 16384}, D = 1024 (profiles/l1_filter.json,
+# "crossover"): up to 4096 x 4096 the filter's extra launches (grid, two packs, the gated pair) cost it 0.1-0.9 ms
+# (4.86 ms against 4.75 ms at 4096 x 4096, inside the spread), at 8192 x 8192 it takes 8.18 ms against 11.72 ms with
+# 0.70 ms of combined spread, at 16384 x 16384 17.1 ms against 33.8 ms.
+L1_FILTER_MIN_PAIRS = 8192 * 8192
+
+
+def _l1_applies(metric: int, score_dtype) -> bool:
+    """The SAD filter speaks for ``PW_L1`` with float64 score words and for nothing else."""
+    return metric == _lib.PW_L1 and score_dtype == torch.float64
+
+
+def _l1_forced(name: str, filter, metric: int, alpha: float, beta: float, score_dtype) -> bool:
+    """Whether ``filter`` is the forced value ``"l1"``; ValueError when the SAD filter cannot speak for the call."""
+    if not (isinstance(filter, str) and filter == "l1"):
+        return False
+    if not (_l1_applies(metric, score_dtype) and _l2_scaling_ok(alpha, beta)):
+        raise ValueError(f'{name}: filter="l1" needs PW_L1 with float64 score words, alpha finite and non-zero, '
+                         "beta finite")
+    return True
+
+
+def _l1_auto(filter, metric: int, alpha: float, beta: float, score_dtype, pairs: int, d: int) -> bool:
+    """Whether ``filter=None`` takes the SAD filter at this size (never hands the entry what it refuses)."""
+    return (filter is None and L1_FILTER_MIN_PAIRS is not None and _l1_applies(metric, score_dtype)
+            and _l2_scaling_ok(alpha, beta) and pairs >= L1_FILTER_MIN_PAIRS and d <= L1_D_MAX)
+
+
+def _l1_count_stats(host) -> dict:
+    """{decided, band, rescored, overflow} of ``cmve_l1_count``: ``cmve_l2_count_resolved``'s four words."""
+    return _l2_count_stats(host)
+
+
+def l1_pack_size(n: int, d: int) -> Tuple[int, int]:
+    """(n_pad, d_pad) of a set's uint16 codes (``cmve_l1_pack_size``; host only: no launch)."""
+    n_pad, d_pad = C.c_int64(), C.c_int64()
+    check(lib.cmve_l1_pack_size(int(n), int(d), C.byref(n_pad), C.byref(d_pad)), "cmve_l1_pack_size")
+    return n_pad.value, d_pad.value
+
+
+def l1_count_workspace(band_cap: int) -> int:
+    """Bytes of workspace ``cmve_l1_count`` needs for a band list of ``band_cap`` pairs (host only: no launch)."""
+    n = C.c_int64()
+    check(lib.cmve_l1_count_workspace(int(band_cap), C.byref(n)), "cmve_l1_count_workspace")
+    return n.value
+
+
+def l1_grid(x: torch.Tensor, grid: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The device float64 [2] grid words {lo, hi} of the rows ``x`` (``cmve_l1_grid``); with ``grid`` the words
+    already there are extended in place, so that two sets share one grid.  No host copy, no synchronisation."""
+    accumulate = grid is not None
+    if grid is None:
+        grid = torch.empty(2, dtype=torch.float64, device=x.device)
+    check(lib.cmve_l1_grid(handle(x.device), _ptr(x), _dtype_code(x), _pw_ld(x), x.shape[0], x.shape[1], _ptr(grid),
+                           1 if accumulate else 0), "cmve_l1_grid")
+    return grid
+
+
+class L1Set:
+    """Rows packed for the SAD filter of the L1 measures (K22): the raw rows (``.raw``, the fp64 route's operand and
+    the source of every canonical score), their uint16 codes in ``cmve_l1_pack``'s tiled order, the rows' errors, the
+    grid tensor and the pads.  A resident side is packed once: ``L1Set(gallery)`` derives the grid from its own
+    rows, ``L1Set(x, grid=other.grid)`` packs a second set on an existing grid (elements outside it clamp: only the
+    band grows)."""
+
+    def __init__(self, x, grid: Optional[torch.Tensor] = None, device: Optional[torch.device] = None):
+        raw = _pw_rows(x if isinstance(x, torch.Tensor) else to_device(x, device), "L1Set")
+        n, d = raw.shape
+        if d == 0 or d > L1_D_MAX:
+            raise ValueError(f"L1Set: d must be in [1, {L1_D_MAX}], got {d}")
+        if grid is not None and (grid.dtype != torch.float64 or grid.numel() != 2 or grid.device != raw.device):
+            raise TypeError("L1Set: grid is a float64 [2] tensor on the rows' device")
+        self.device, self.raw = raw.device, raw
+        self.n, self.d = n, d
+        self.n_pad, self.d_pad = l1_pack_size(n, d)
+        self.grid = l1_grid(raw) if grid is None else grid
+        self.codes = torch.empty(max(self.n_pad * self.d_pad, 8), dtype=torch.int16, device=raw.device)
+        self.err = torch.empty(max(n, 1), dtype=torch.float64, device=raw.device)
+        check(lib.cmve_l1_pack(handle(raw.device), _ptr(raw), _dtype_code(raw), _pw_ld(raw), n, d, _ptr(self.grid),
+                               _ptr(self.codes), self.n_pad, self.d_pad, _ptr(self.err)), "cmve_l1_pack")
+
+
+def _l1_sets(a, b, a_set: Optional["L1Set"], b_set: Optional["L1Set"]):
+    """Both sides as ``L1Set`` on ONE grid: a resident side's when there is one, else both sets' elements."""
+    if a_set is not None and b_set is not None:
+        if a_set.grid.data_ptr() != b_set.grid.data_ptr():
+            raise ValueError("the two L1Set sides were packed on different grids: pack one with grid=other.grid")
+        return a_set, b_set
+    if a_set is not None:
+        return a_set, L1Set(b, grid=a_set.grid)
+    if b_set is not None:
+        return L1Set(a, grid=b_set.grid), b_set
+    grid = l1_grid(b, l1_grid(a))
+    return L1Set(a, grid=grid), L1Set(b, grid=grid)
+
+
+def _l1_count_call(h, a_set: "L1Set", b_set: "L1Set", alpha, beta, row, col, ws, ws_bytes: int, stats):
+    """``cmve_l1_count``.  row / col: (offsets, item scores, items, n, positions) of the direction; ws: the band
+    list's tensor, ws_bytes of it handed over."""
+    (roff, rsc, ritems, rn, rpos), (coff, csc, citems, cn, cpos) = row, col
+    a, b = a_set.raw, b_set.raw
+    check(lib.cmve_l1_count(h, _ptr(a), _dtype_code(a), _pw_ld(a), a_set.n, _ptr(a_set.codes), _ptr(a_set.err),
+                            _ptr(b), _dtype_code(b), _pw_ld(b), b_set.n, _ptr(b_set.codes), _ptr(b_set.err), a_set.d,
+                            _ptr(a_set.grid), float(alpha), float(beta),
+                            _ptr(roff), _ptr(rsc) if ritems else None, ritems, rn, _ptr(rpos),
+                            _ptr(coff), _ptr(csc) if citems else None, citems, cn, _ptr(cpos),
+                            _ptr(ws) if ws_bytes else None, ws_bytes, _ptr(stats)), "cmve_l1_count")
+
+
 class _PairwisePositions:
     """One ``cmve_pairwise_positions`` call: per direction the 0-based positions, the item scores and the offsets.
 
@@ -416,12 +529,19 @@ class _PairwisePositions:
     canonical re-score of the band: the same words); None -- the filter when it applies and na * nb reaches
     ``L2_FILTER_MIN_PAIRS``.  The filter is an accelerator: a band list that overflows is redone once with the
     reported need, and a band above 1/8 of the pairs runs the fp64 route.  ``filter_stats``: the four counters of
-    the last ``cmve_l2_count`` plus ``redone`` / ``fallback``, or None when the filter was not tried."""
+    the last ``cmve_l2_count`` plus ``redone`` / ``fallback``, or None when the filter was not tried.
+
+    ``filter="l1"`` -- the K22 route for ``PW_L1`` with fp64 score words: both sides packed to uint16 codes on one
+    grid, the item scores from ``cmve_pairwise_item_scores``, the count from ONE ``cmve_l1_count`` (integer SAD filter
+    + canonical re-score of the band, an overflowing list resolved on the device: the same words, no redo);
+    None takes it too when it applies and na * nb reaches ``L1_FILTER_MIN_PAIRS``.  ``filter_stats`` then carries
+    the four counters, ``redone=False`` and ``fallback`` (the overflow word: the canonical count ran)."""
 
     def __init__(self, a, b, metric, alpha, beta, score_dtype, row_lists=None, col_lists=None, filter=None):
         self.filter_stats = None
         applies = _l2_applies(metric, score_dtype)
-        if filter and not applies:
+        l1 = _l1_forced("pairwise_gt_positions", filter, metric, alpha, beta, score_dtype)
+        if filter and not l1 and not applies:
             raise ValueError("pairwise_gt_positions: filter=True needs PW_L2 with float64 score words")
         a, b = _pw_pair(a, b, "pairwise_gt_positions")
         na, nb, dev = a.shape[0], b.shape[0], a.device
@@ -440,10 +560,13 @@ class _PairwisePositions:
             items = sum(len(l) for l in lists)
             sides.append((off, idx, items, torch.empty(max(items, 1), dtype=torch.int32, device=dev)))
         (roff, ridx, ritems, rpos), (coff, cidx, citems, cpos) = sides
+        l1 = l1 or _l1_auto(filter, metric, alpha, beta, score_dtype, na * nb, a.shape[1])
         if filter is None:
             filter = applies and na * nb >= L2_FILTER_MIN_PAIRS and _l2_scaling_ok(alpha, beta)
         sc = None
-        if filter and na and nb and ritems + citems:
+        if l1 and na and nb and ritems + citems:
+            sc = self._filtered_l1(a, b, alpha, beta, sides)
+        elif filter and not l1 and na and nb and ritems + citems:
             sc = self._filtered(a, b, alpha, beta, sides)
         if sc is None:
             nbytes = pairwise_positions_workspace(na, nb, ritems, citems, metric)
@@ -463,16 +586,7 @@ class _PairwisePositions:
         na, nb, dev, h = a.shape[0], b.shape[0], a.device, handle(a.device)
         ra, rb = RowSet(a, with_lo=False, device=dev), RowSet(b, with_lo=False, device=dev)
         a, b = ra.raw, rb.raw
-        # the items' scores, then the four counters, in ONE buffer: one copy to the host brings both
-        buf = torch.empty(ritems + citems + 4, dtype=torch.float64, device=dev)
-        start = 0
-        for off, idx, items, col_dir, n_other in ((roff, ridx, ritems, 0, nb), (coff, cidx, citems, 1, na)):
-            if items:
-                out = buf[start:start + items]
-                _item_scores_into(out, a, b, _lib.PW_L2, alpha, beta, torch.float64, off, idx, items, col_dir, 0)
-                # an index outside the other side scores NaN here (the sharded entry gives it the all-zero word)
-                out.masked_fill_((idx[:items] < 0) | (idx[:items] >= n_other), float("nan"))
-            start += items
+        buf = self._item_scores(a, b, _lib.PW_L2, alpha, beta, sides)
         rsc, csc, stats = buf[:ritems], buf[ritems:ritems + citems], buf[ritems + citems:]
         pairs = na * nb
         cap = l2_band_cap(pairs)
@@ -491,6 +605,40 @@ class _PairwisePositions:
                 break
         self.filter_stats["fallback"] = True
         return None
+
+    @staticmethod
+    def _item_scores(a, b, metric, alpha, beta, sides):
+        """The items' fp64 scores, then room for a filter's four counters, in ONE device buffer: one copy to the host
+        brings both."""
+        (roff, ridx, ritems, _), (coff, cidx, citems, _) = sides
+        na, nb = a.shape[0], b.shape[0]
+        buf = torch.empty(ritems + citems + 4, dtype=torch.float64, device=a.device)
+        start = 0
+        for off, idx, items, col_dir, n_other in ((roff, ridx, ritems, 0, nb), (coff, cidx, citems, 1, na)):
+            if items:
+                out = buf[start:start + items]
+                _item_scores_into(out, a, b, metric, alpha, beta, torch.float64, off, idx, items, col_dir, 0)
+                # an index outside the other side scores NaN here (the sharded entry gives it the all-zero word)
+                out.masked_fill_((idx[:items] < 0) | (idx[:items] >= n_other), float("nan"))
+            start += items
+        return buf
+
+    def _filtered_l1(self, a, b, alpha, beta, sides):
+        """The K22 route into the sides' position buffers; the items' scores (host).  ONE ``cmve_l1_count`` call:
+        a band list that overflows is resolved on the device (``fallback``: the canonical count ran), never redone."""
+        (roff, ridx, ritems, rpos), (coff, cidx, citems, cpos) = sides
+        na, nb, dev = a.shape[0], b.shape[0], a.device
+        sa, sb = _l1_sets(a, b, None, None)
+        buf = self._item_scores(a, b, _lib.PW_L1, alpha, beta, sides)
+        rsc, csc, stats = buf[:ritems], buf[ritems:ritems + citems], buf[ritems + citems:]
+        nbytes = l1_count_workspace(l2_band_cap(na * nb))
+        ws = torch.empty(max(nbytes // 8, 1), dtype=torch.int64, device=dev)
+        _l1_count_call(handle(dev), sa, sb, alpha, beta, (roff, rsc, ritems, nb, rpos), (coff, csc, citems, na, cpos),
+                       ws, nbytes, stats)
+        host = buf.cpu().numpy()
+        st = _l1_count_stats(host[ritems + citems:].view(np.int64))
+        self.filter_stats = dict(st, redone=False, fallback=bool(st["overflow"]))
+        return host[:ritems + citems]
 
     def _collect(self, sides, sc):
         self.pos, self.nan = [], []
@@ -598,14 +746,24 @@ def pairwise_count(a, b, metric: int, alpha: float, beta: float, score_dtype, ro
     packed inside the call when the filter runs.  ``band``: a caller-owned int64 device tensor that holds the band
     list, one slot per element (None: a fresh one of ``l2_band_cap(na * nb)`` slots).  ``return_stats``: also return
     the int64 [4] DEVICE tensor {decided, band found, band re-scored, overflow} (``l2_band_plan`` reads it once the
-    caller has it on the host), or None when the filter did not run."""
+    caller has it on the host), or None when the filter did not run.
+
+    ``filter="l1"`` -- ``cmve_l1_count`` (K22: the integer SAD filter of ``PW_L1``, the band re-scored on the canonical
+    chain and an overflowing list resolved on the device: the same words), ValueError unless the metric is ``PW_L1``
+    with float64 score words, alpha finite and non-zero and beta finite; None also takes it when it applies and
+    na * nb reaches ``L1_FILTER_MIN_PAIRS`` (never while that is None).  a / b may then be an ``L1Set`` (a resident
+    side packed once; the other side is packed on its grid inside the call) -- plain rows on both sides share a
+    grid made from both.  ``band`` / ``return_stats`` as above."""
     applies = _l2_applies(metric, score_dtype) and _l2_scaling_ok(alpha, beta)
-    if filter and not applies:
+    l1 = _l1_forced("pairwise_count", filter, metric, alpha, beta, score_dtype)
+    if filter and not l1 and not applies:
         raise ValueError("pairwise_count: filter=True needs PW_L2 with float64 score words, alpha finite and "
                          "non-zero, beta finite")
+    a_l1, b_l1 = (a if isinstance(a, L1Set) else None), (b if isinstance(b, L1Set) else None)
     a_set = a if isinstance(a, RowSet) else None
     b_set = b if isinstance(b, RowSet) else None
-    a, b = _pw_pair(a_set.raw if a_set is not None else a, b_set.raw if b_set is not None else b, "pairwise_count")
+    a, b = _pw_pair(a.raw if isinstance(a, (RowSet, L1Set)) else a, b.raw if isinstance(b, (RowSet, L1Set)) else b,
+                    "pairwise_count")
     na, nb, dev = a.shape[0], b.shape[0], a.device
     sides = []
     for side, n_lists in ((row, na), (col, nb)):
@@ -619,12 +777,22 @@ def pairwise_count(a, b, metric: int, alpha: float, beta: float, score_dtype, ro
             raise TypeError("pairwise_count: item scores are contiguous float64")
         sides.append((off, sc, sc.numel(), int(n), torch.empty(max(sc.numel(), 1), dtype=torch.int32, device=dev)))
     (roff, rsc, ritems, rn, rpos), (coff, csc, citems, cn, cpos) = sides
+    l1 = l1 or _l1_auto(filter, metric, alpha, beta, score_dtype, na * nb, a.shape[1])
     if filter is None:  # auto never hands the entry what it refuses; filter=True does, and the entry says so
         filter = applies and na * nb >= L2_FILTER_MIN_PAIRS and _l2_set_ok(a_set) and _l2_set_ok(b_set)
     stats = None
-    if filter:
-        if band is not None and (band.dtype != torch.int64 or not band.is_contiguous() or band.device != dev):
-            raise TypeError("pairwise_count: band is a contiguous int64 tensor on the rows' device")
+    if (l1 or filter) and band is not None and (band.dtype != torch.int64 or not band.is_contiguous()
+                                                or band.device != dev):
+        raise TypeError("pairwise_count: band is a contiguous int64 tensor on the rows' device")
+    if l1:
+        a_l1, b_l1 = _l1_sets(a, b, a_l1, b_l1)
+        if band is None:
+            band = torch.empty(l2_band_cap(na * nb), dtype=torch.int64, device=dev)
+        stats = torch.empty(4, dtype=torch.int64, device=dev)
+        _l1_count_call(handle(dev), a_l1, b_l1, alpha, beta, sides[0], sides[1], band, _nbytes(band), stats)
+    elif filter:
+        if a_l1 is not None or b_l1 is not None:
+            raise TypeError("pairwise_count: an L1Set is packed for filter=\"l1\"; the Euclidean filter takes a RowSet")
         if a_set is None:
             a_set = RowSet(a, with_lo=False, device=dev)
         if b_set is None:

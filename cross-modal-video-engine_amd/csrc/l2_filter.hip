@@ -18,7 +18,7 @@
 // K21 (cmve_l2_count_resolved): the same launches, then two that read the overflow word and do nothing when it is 0 --
 //   l2f_gated_zero_kernel zeroes the words, pairwise_rank.hip's gated pwr_count_kernel counts every pair on the
 //   canonical chain -- so the words are cmve_pairwise_count's whatever the band did, with no host read in between.
-#include "l2_filter_tile.h"
+#include "l1_filter_tile.h"  // (l2_filter_tile.h, and the launches this file defines for both filters)
 
 namespace cmve {
 namespace {
@@ -253,7 +253,9 @@ __global__ __launch_bounds__(256, 2) void l2f_main_kernel(L2fArgs a) {
 }
 
 // ---- the band pairs on the canonical chain -----------------------------------------------------------------------------
-template <typename TA, typename TB>
+// (METRIC: CMVE_PW_L2, or CMVE_PW_L1 for the SAD filter of l1_filter.hip -- the list, the lists' words and the
+// counters are the same, the chain is the metric's)
+template <int METRIC, typename TA, typename TB>
 __global__ __launch_bounds__(256) void l2f_fixup_kernel(const TA* __restrict__ A, int64_t lda,
                                                         const TB* __restrict__ B, int64_t ldb, int64_t d, double alpha,
                                                         double beta, const int64_t* __restrict__ row_off,
@@ -270,8 +272,8 @@ __global__ __launch_bounds__(256) void l2f_fixup_kernel(const TA* __restrict__ A
     const int64_t p = b0 + w * 64 + lane;
     const bool live = p < n;
     const int2 ij = band[live ? p : b0];  // an idle lane repeats a pair of the list: its loads stay in bounds
-    const double s = l2f_chain64(A, lda, B, ldb, d, ij.x, ij.y, sd[w], lane);
-    const double e = pw_score<CMVE_PW_L2>(s, 0.0, alpha, beta);
+    const double s = l2f_chain64<METRIC>(A, lda, B, ldb, d, ij.x, ij.y, sd[w], lane);
+    const double e = pw_score<METRIC>(s, 0.0, alpha, beta);
     if (live) {
       if (row_pos) {
         const int64_t o = row_off[ij.x], m = row_off[ij.x + 1];
@@ -317,6 +319,43 @@ __global__ __launch_bounds__(256) void l2f_gated_zero_kernel(int32_t* __restrict
 }
 
 }  // namespace
+
+// ---- the launches K22's SAD filter shares (l1_filter_tile.h) -------------------------------------------------------------
+void l2f_nan_launch(hipStream_t st, const int64_t* off, const double* sc, int64_t n_lists, int64_t n, int32_t* pos) {
+  hipLaunchKernelGGL(l2f_nan_kernel, dim3((unsigned)((n_lists + 255) / 256)), dim3(256), 0, st, off, sc, n_lists, n,
+                     pos);
+}
+
+void l2f_fixup_launch(hipStream_t st, int32_t metric, const void* A, int32_t a_dtype, int64_t lda, const void* B,
+                      int32_t b_dtype, int64_t ldb, int64_t d, double alpha, double beta, const int64_t* row_off,
+                      const double* row_sc, int32_t* row_pos, const int64_t* col_off, const double* col_sc,
+                      int32_t* col_pos, const void* band, int64_t cap, int64_t* stats) {
+  const int fix_blocks = (int)std::max<int64_t>(1, std::min<int64_t>(8 * device_cus(), (cap + 255) / 256));
+#define L2F_FIXUP(M)                                                                                                  \
+  PWR_TYPES(a_dtype, b_dtype, TA, TB, {                                                                               \
+    hipLaunchKernelGGL((l2f_fixup_kernel<M, TA, TB>), dim3((unsigned)fix_blocks), dim3(256), 0, st, (const TA*)A, lda, \
+                       (const TB*)B, ldb, d, alpha, beta, row_off, row_sc, row_pos, col_off, col_sc, col_pos,         \
+                       (const int2*)band, cap, (l2f_u64*)stats);                                                      \
+  })
+  if (metric == CMVE_PW_L1) { L2F_FIXUP(CMVE_PW_L1) } else { L2F_FIXUP(CMVE_PW_L2) }
+#undef L2F_FIXUP
+}
+
+void l2f_resolve_launch(hipStream_t st, int32_t metric, const void* A, int32_t a_dtype, int64_t lda, int64_t na,
+                        const void* B, int32_t b_dtype, int64_t ldb, int64_t nb, int64_t d, double alpha, double beta,
+                        const int64_t* row_off, const double* row_sc, int64_t row_items, int64_t row_n,
+                        int32_t* row_pos, const int64_t* col_off, const double* col_sc, int64_t col_items,
+                        int64_t col_n, int32_t* col_pos, const int64_t* stats) {
+  // the list overflowed (decided on the device: both launches do nothing otherwise): the words so far are
+  // dropped and cmve_pairwise_count's kernel counts every pair on the canonical chain, NaN items included
+  const int64_t items = std::max(row_items, col_items);
+  const int zero_blocks = (int)std::max<int64_t>(1, std::min<int64_t>(8 * device_cus(), (items + 255) / 256));
+  hipLaunchKernelGGL(l2f_gated_zero_kernel, dim3((unsigned)zero_blocks), dim3(256), 0, st, row_pos, row_items, col_pos,
+                     col_items, (const l2f_u64*)stats + 3);
+  pwr_count_gated_launch(st, A, a_dtype, lda, na, B, b_dtype, ldb, nb, d, metric, alpha, beta, row_off, row_sc, row_n,
+                         row_pos, col_off, col_sc, col_n, col_pos, (const l2f_u64*)stats + 3);
+}
+
 }  // namespace cmve
 
 using namespace cmve;
@@ -363,12 +402,8 @@ static int l2_count_run(const char* name, bool resolved, cmve_handle_t h, const 
   if (row_items) CMVE_HIP(hipMemsetAsync(row_pos, 0, sizeof(int32_t) * row_items, st));
   if (col_items) CMVE_HIP(hipMemsetAsync(col_pos, 0, sizeof(int32_t) * col_items, st));
   // the NaN items' words are the caller's n, whatever this call's own na / nb
-  if (row_items && row_n && na)
-    hipLaunchKernelGGL(l2f_nan_kernel, dim3((unsigned)((na + 255) / 256)), dim3(256), 0, st, row_off, row_sc, na, row_n,
-                       row_pos);
-  if (col_items && col_n && nb)
-    hipLaunchKernelGGL(l2f_nan_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, col_off, col_sc, nb, col_n,
-                       col_pos);
+  if (row_items && row_n && na) l2f_nan_launch(st, row_off, row_sc, na, row_n, row_pos);
+  if (col_items && col_n && nb) l2f_nan_launch(st, col_off, col_sc, nb, col_n, col_pos);
   if (na == 0 || nb == 0) return check_launch("l2_count");
   L2fArgs g;
   g.a16 = a->h16;
@@ -395,25 +430,13 @@ static int l2_count_run(const char* name, bool resolved, cmve_handle_t h, const 
   g.tiles_a = (int)tiles_a;
   g.tiles_b = (int)tiles_b;
   hipLaunchKernelGGL(l2f_main_kernel, dim3((unsigned)(tiles_a * tiles_b)), dim3(256), 0, st, g);
-  const int fix_blocks = (int)std::max<int64_t>(1, std::min<int64_t>(8 * device_cus(), (g.cap + 255) / 256));
-  if (g.cap > 0) {
-    PWR_TYPES(a->raw_dtype, b->raw_dtype, TA, TB, {
-      hipLaunchKernelGGL((l2f_fixup_kernel<TA, TB>), dim3((unsigned)fix_blocks), dim3(256), 0, st, (const TA*)a->raw,
-                         a->raw_ld, (const TB*)b->raw, b->raw_ld, d, alpha, beta, row_off, row_sc, g.row_pos, col_off,
-                         col_sc, g.col_pos, (const int2*)g.band, g.cap, g.stats);
-    })
-  }
-  if (resolved) {
-    // the list overflowed (decided on the device: both launches do nothing otherwise): the words so far are
-    // dropped and cmve_pairwise_count's kernel counts every pair on the canonical chain, NaN items included
-    const int64_t items = std::max(row_items, col_items);
-    const int zero_blocks = (int)std::max<int64_t>(1, std::min<int64_t>(8 * device_cus(), (items + 255) / 256));
-    hipLaunchKernelGGL(l2f_gated_zero_kernel, dim3((unsigned)zero_blocks), dim3(256), 0, st, g.row_pos, row_items,
-                       g.col_pos, col_items, (const l2f_u64*)g.stats + 3);
-    pwr_count_l2_gated_launch(st, a->raw, a->raw_dtype, a->raw_ld, na, b->raw, b->raw_dtype, b->raw_ld, nb, d, alpha,
-                              beta, row_off, row_sc, row_n, g.row_pos, col_off, col_sc, col_n, g.col_pos,
-                              (const l2f_u64*)g.stats + 3);
-  }
+  if (g.cap > 0)
+    l2f_fixup_launch(st, CMVE_PW_L2, a->raw, a->raw_dtype, a->raw_ld, b->raw, b->raw_dtype, b->raw_ld, d, alpha, beta,
+                     row_off, row_sc, g.row_pos, col_off, col_sc, g.col_pos, g.band, g.cap, stats);
+  if (resolved)
+    l2f_resolve_launch(st, CMVE_PW_L2, a->raw, a->raw_dtype, a->raw_ld, na, b->raw, b->raw_dtype, b->raw_ld, nb, d, alpha,
+                       beta, row_off, row_sc, row_items, row_n, g.row_pos, col_off, col_sc, col_items, col_n, g.col_pos,
+                       stats);
   return check_launch(resolved ? "l2_count_resolved" : "l2_count");
 }
 

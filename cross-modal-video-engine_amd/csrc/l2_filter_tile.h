@@ -75,6 +75,9 @@ __device__ __forceinline__ double l2f_side_err(int64_t row, bool valid, const fl
 // alpha < 0: D < tn.  x = (t - beta) / alpha is the distance at which the real-number score equals t; sig covers the
 // roundings of x itself and of the chain's alpha * x + beta (contracted or not); rho those of the sum, the
 // subtractions and the square root.  A NaN item is never counted: every pair with a finite interval is not-below.
+// SQUARED = false (K22, CMVE_PW_L1): D is the L1 distance itself -- no square -- and sig also carries the underflow of
+// the chain's product alpha * S, 2^-1074 / |alpha| in distance space.
+template <bool SQUARED = true>
 __device__ __forceinline__ void l2f_thresholds(double t, double alpha, double beta, double rho, double& tb,
                                                double& tn) {
   const bool pos = alpha > 0.0;
@@ -86,11 +89,12 @@ __device__ __forceinline__ void l2f_thresholds(double t, double alpha, double be
     return;
   }
   const double x = (t - beta) / alpha;
-  const double sig = 16.0 * L2F_U * ((fabs(t) + fabs(beta)) / fabs(alpha)) + 1e-290;
+  double sig = 16.0 * L2F_U * ((fabs(t) + fabs(beta)) / fabs(alpha)) + 1e-290;
+  if constexpr (!SQUARED) sig += 4.9406564584124654e-324 / fabs(alpha);
   const double xlo = x - sig, xhi = x + sig;
   const double l = xlo * (1.0 - rho), h = xhi * (1.0 + 2.0 * rho);
-  const double lo_t = xlo > 0.0 ? (l * l) * (1.0 - 4.0 * L2F_U) : -inf;  // D below it: the distance is below x
-  const double hi_t = xhi > 0.0 ? (h * h) * (1.0 + 4.0 * L2F_U) : 0.0;   // D above it: the distance is above x
+  const double lo_t = xlo > 0.0 ? (SQUARED ? l * l : l) * (1.0 - 4.0 * L2F_U) : -inf;  // D below it: the distance is below x
+  const double hi_t = xhi > 0.0 ? (SQUARED ? h * h : h) * (1.0 + 4.0 * L2F_U) : 0.0;   // D above it: the distance is above x
   tb = pos ? lo_t : hi_t;
   tn = pos ? hi_t : lo_t;
 }
@@ -180,12 +184,12 @@ __device__ __forceinline__ void l2f_gemm_tile(const uint16_t* __restrict__ a16, 
 #undef L2F_WRITE
 }
 
-// The canonical sum of squares of 64 listed pairs, one per lane of a wave: lane l's pair is (A row i, B row j) of ITS
+// The canonical sum (of squares: CMVE_PW_L2; of magnitudes: CMVE_PW_L1) of 64 listed pairs, one per lane of a wave: lane l's pair is (A row i, B row j) of ITS
 // arguments.  The (a - b) chunks go through sd (this wave's [64][L2F_KC + 1] doubles of LDS) transposed, so the loads
 // are coalesced (16 lanes read 128 contiguous bytes of a row); each lane then runs its own pair's chain, pw_acc with
 // k ascending into one accumulator from zero.  Every lane must name rows that exist (an idle lane repeats a listed
 // pair).  The barriers are the block's: every wave of the block calls this the same number of times with the same d.
-template <typename TA, typename TB>
+template <int METRIC = CMVE_PW_L2, typename TA, typename TB>
 __device__ __forceinline__ double l2f_chain64(const TA* __restrict__ A, int64_t lda, const TB* __restrict__ B,
                                               int64_t ldb, int64_t d, int i, int j, double (&sd)[64][L2F_KC + 1],
                                               int lane) {
@@ -202,7 +206,7 @@ __device__ __forceinline__ double l2f_chain64(const TA* __restrict__ A, int64_t 
     __syncthreads();
     const int kn = (int)min<int64_t>(L2F_KC, d - k0);
     // the subtraction was done above (exact fp64 either way): pw_acc's own  t - 0  leaves it as it is
-    for (int k = 0; k < kn; ++k) pw_acc<CMVE_PW_L2>(sd[lane][k], 0.0, s, unused);
+    for (int k = 0; k < kn; ++k) pw_acc<METRIC>(sd[lane][k], 0.0, s, unused);
     __syncthreads();
   }
   return s;

@@ -57,7 +57,7 @@ __global__ __launch_bounds__(256) void pwr_item_kernel(const TA* __restrict__ A,
 // cmve_gt_positions_from_matrix's value for it instead, row_n - (NaN items of the list) + (its place among them)
 // (row_n == 0: its word stays 0 -- another shard of the gallery stores it).  The grid has at least one block row and
 // column, so the rule also runs when na or nb is 0.  pos must be zero on entry.
-// GATED (K21, cmve_l2_count_resolved; gate / tiles_x / tiles are read by this instantiation alone): every thread reads
+// GATED (K21 / K22, cmve_l2_count_resolved and cmve_l1_count; gate / tiles_x / tiles are read by this instantiation alone): every thread reads
 // *gate first and the block returns at once when it is 0; otherwise the blocks of a BOUNDED 1-d grid loop over the
 // tiles_x x tiles_y tiles, block b taking b, b + gridDim.x, ... in the plain grid's own order -- a call whose gate stays
 // shut dispatches a few thousand blocks, not one per tile.
@@ -325,22 +325,25 @@ static void pwr_count_launch(hipStream_t st, const void* A, int32_t a_dtype, int
   }))
 }
 
-void pwr_count_l2_gated_launch(hipStream_t st, const void* A, int32_t a_dtype, int64_t lda, int64_t na, const void* B,
-                               int32_t b_dtype, int64_t ldb, int64_t nb, int64_t d, double alpha, double beta,
-                               const int64_t* row_off, const double* row_sc, int64_t row_n, int32_t* row_pos,
-                               const int64_t* col_off, const double* col_sc, int64_t col_n, int32_t* col_pos,
-                               const unsigned long long* gate) {
+void pwr_count_gated_launch(hipStream_t st, const void* A, int32_t a_dtype, int64_t lda, int64_t na, const void* B,
+                            int32_t b_dtype, int64_t ldb, int64_t nb, int64_t d, int32_t metric, double alpha,
+                            double beta, const int64_t* row_off, const double* row_sc, int64_t row_n, int32_t* row_pos,
+                            const int64_t* col_off, const double* col_sc, int64_t col_n, int32_t* col_pos,
+                            const unsigned long long* gate) {
   // pwr_count_launch's tiles (at least one block row and column: the NaN-item rule) over at most 64 blocks per compute
   // unit: few enough that a shut gate costs microseconds, many enough that an open one keeps the plain grid's balance
   // (8 per compute unit left whole rounds of resident blocks half empty: +1.3 ms on a 13 ms count, DESIGN s4 K21)
   const int64_t tiles_x = std::max<int64_t>(1, (nb + PW_TB - 1) / PW_TB);
   const int64_t tiles = tiles_x * std::max<int64_t>(1, (na + PW_TA - 1) / PW_TA);
   const unsigned blocks = (unsigned)std::min<int64_t>(tiles, 64 * (int64_t)device_cus());
-  PWR_TYPES(a_dtype, b_dtype, TA, TB, {
-    hipLaunchKernelGGL((pwr_count_kernel<CMVE_PW_L2, TA, TB, true>), dim3(blocks), dim3(256), 0, st, (const TA*)A,
-                       lda, na, (const TB*)B, ldb, nb, d, alpha, beta, 0, row_off, row_sc, row_n, row_pos, col_off,
-                       col_sc, col_n, col_pos, gate, (unsigned)tiles_x, tiles);
+#define PWR_GATED(M)                                                                                                  \
+  PWR_TYPES(a_dtype, b_dtype, TA, TB, {                                                                               \
+    hipLaunchKernelGGL((pwr_count_kernel<M, TA, TB, true>), dim3(blocks), dim3(256), 0, st, (const TA*)A, lda, na,    \
+                       (const TB*)B, ldb, nb, d, alpha, beta, 0, row_off, row_sc, row_n, row_pos, col_off, col_sc,    \
+                       col_n, col_pos, gate, (unsigned)tiles_x, tiles);                                               \
   })
+  if (metric == CMVE_PW_L1) { PWR_GATED(CMVE_PW_L1) } else { PWR_GATED(CMVE_PW_L2) }
+#undef PWR_GATED
 }
 
 }  // namespace cmve

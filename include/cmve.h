@@ -765,6 +765,53 @@ int cmve_l2_count_resolved(cmve_handle_t h, const cmve_rows_t* a, const cmve_row
                            int32_t* row_pos, const int64_t* col_off, const double* col_sc, int64_t col_items,
                            int64_t col_n, int32_t* col_pos, void* ws, int64_t ws_bytes, int64_t* stats);
 
+/* K22: cmve_pairwise_count for CMVE_PW_L1 with fp64 score words from an integer SAD filter (csrc/l1_filter.hip).
+ * Replaces, as its K18 twin does: LINAS-engine/evaluation.py:24-29 (cal_error under l1 / l1_norm) +
+ * util/metrics.py:61-157 (t2v_map, v2t_map, eval_q2m's argsort loop).
+ *   Both sets are quantised to uint16 codes on ONE grid; the L1 distance of the decoded rows is s * SAD(codes)
+ *   exactly (v_sad_u16, u32 accumulators: exact for d <= 65,536), and the true distance lies within the two rows'
+ *   quantisation errors of it.  Additive entries: the ABI version does not change.
+ *   cmve_l1_pack_size  host only (LINAS-engine/evaluation.py:24-29 + util/metrics.py:61-157: the packed form of
+ *                      cal_error's operands): n_pad = n rounded up to 128 rows, d_pad = d rounded up to 32
+ *                      elements.  codes take n_pad * d_pad * 2 bytes (16-byte aligned), err n doubles.
+ *   cmve_l1_grid       (evaluation.py:24-29 + metrics.py:61-157, as above) grid = device double[2] {lo, hi}: min and
+ *                      max over X's elements with |x| <= 1e30.  accumulate = 0 starts from the empty grid
+ *                      {+inf, -inf}; accumulate != 0 extends the grid already there, so that two sets share one.  Integer
+ *                      atomics on the words' bits: order-independent.  Every kernel derives s = (hi - lo) / 65535
+ *                      from the two words by one function; hi > lo false (empty, constant, NaN): lo = 0, s = 1.
+ *                      Correctness never depends on the grid -- a bad one only enlarges the band.
+ *   cmve_l1_pack       (evaluation.py:24-29 + metrics.py:61-157, as above) X [n, d] f32 / f64 rows -> codes
+ *                      q = clamp(rint((x - lo) / s), 0, 65535) in the tiled order the count kernel copies to LDS as it
+ *                      lies ([128-row tile][32-element K tile][16 code dwords][128 rows]; padding is code 0), and
+ *                      err[i] >= sum_k |x_k - (lo + s q_k)| (fp64, rounded up; +inf for a row with a non-finite
+ *                      element or one above 1e150: its pairs all go to the canonical chain).  Refused: a short pad
+ *                      (n_pad / d_pad are cmve_l1_pack_size's; a larger n_pad is fine).
+ *   cmve_l1_count_workspace  host only: 8 * band_cap bytes, the band list and nothing else.
+ *   cmve_l1_count      (evaluation.py:24-29 + metrics.py:61-157, as above) cmve_l2_count_resolved's contract with
+ *                      CMVE_PW_L1 in place of CMVE_PW_L2: A / B are the raw rows (the source of every canonical
+ *                      score), a_codes / a_err / b_codes / b_err their packs on `grid`.  On return row_pos / col_pos
+ *                      hold, word for word, what cmve_pairwise_count(metric = CMVE_PW_L1, score_dtype = CMVE_F64)
+ *                      writes for the same row_off / row_sc / row_n / col_off / col_sc / col_n (NaN items included,
+ *                      also when na or nb is 0; either direction may be NULL), WHETHER OR NOT the band list
+ *                      overflowed: the overflow is resolved on the device by cmve_l2_count_resolved's two gated
+ *                      launches.  ws: 8-byte aligned, need not be zeroed, the capacity is ws_bytes / 8.  stats: device
+ *                      int64[4] = {pairs decided by the filter, band pairs found, band pairs re-scored, overflow
+ *                      flag}, as cmve_l2_count_resolved's.  Enqueued on the handle's stream; allocates nothing, never
+ *                      synchronises; integer atomics only: two calls give the same words.  Refused: alpha 0 or
+ *                      non-finite, beta non-finite, d > 65,536, NULL codes / err / grid. */
+int cmve_l1_pack_size(int64_t n, int64_t d, int64_t* n_pad, int64_t* d_pad);
+int cmve_l1_grid(cmve_handle_t h, const void* X, int32_t dtype, int64_t ld, int64_t n, int64_t d, double* grid,
+                 int32_t accumulate);
+int cmve_l1_pack(cmve_handle_t h, const void* X, int32_t dtype, int64_t ld, int64_t n, int64_t d, const double* grid,
+                 void* codes, int64_t n_pad, int64_t d_pad, double* err);
+int cmve_l1_count_workspace(int64_t band_cap, int64_t* bytes);
+int cmve_l1_count(cmve_handle_t h, const void* A, int32_t a_dtype, int64_t lda, int64_t na, const void* a_codes,
+                  const double* a_err, const void* B, int32_t b_dtype, int64_t ldb, int64_t nb, const void* b_codes,
+                  const double* b_err, int64_t d, const double* grid, double alpha, double beta,
+                  const int64_t* row_off, const double* row_sc, int64_t row_items, int64_t row_n, int32_t* row_pos,
+                  const int64_t* col_off, const double* col_sc, int64_t col_items, int64_t col_n, int32_t* col_pos,
+                  void* ws, int64_t ws_bytes, int64_t* stats);
+
 /* K20: cmve_pairwise_topk for CMVE_PW_L2 with fp64 score words at the MFMA rate (csrc/l2_topk.hip).
  * Replaces, as its K18 twin does: LINAS-engine/inference.py:78-80 (cal_error(video_embs, cap_emb, measure) then
  * np.argsort(errors[0])[:topK]) under euclidean / l2 / l2_norm (LINAS-engine/evaluation.py:22-35).
