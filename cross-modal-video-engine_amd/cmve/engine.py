@@ -369,18 +369,23 @@ def _stats4(names, host) -> dict:
 
 
 def _l2_count_stats(host) -> dict:
-    """{decided, band, rescored, overflow} of ``cmve_l2_count`` / ``cmve_l2_count_resolved``."""
+    """{decided, band, rescored, overflow} of ``cmve_l2_count`` / ``cmve_l2_count_resolved`` / ``cmve_l1_count``."""
     return _stats4(("decided", "band", "rescored", "overflow"), host)
 
 
-def _l2_count_call(entry: str, h, a_set: "RowSet", b_set: "RowSet", alpha, beta, row, col, ws, ws_bytes: int, stats):
-    """``cmve_l2_count`` or ``cmve_l2_count_resolved`` (``entry``: one argument list).  row / col: (offsets, item
-    scores, items, n, positions) of the direction; ws: the band list's tensor, ws_bytes of it handed over."""
+def _count_tail(row, col, ws, ws_bytes: int, stats):
+    """The last thirteen arguments of every filtered count entry.  row / col: (offsets, item scores, items, n,
+    positions) of the direction; ws: the band list's tensor, ws_bytes of it handed over; stats: the int64 [4] words."""
     (roff, rsc, ritems, rn, rpos), (coff, csc, citems, cn, cpos) = row, col
+    return (_ptr(roff), _ptr(rsc) if ritems else None, ritems, rn, _ptr(rpos),
+            _ptr(coff), _ptr(csc) if citems else None, citems, cn, _ptr(cpos),
+            _ptr(ws) if ws_bytes else None, ws_bytes, _ptr(stats))
+
+
+def _l2_count_call(entry: str, h, a_set: "RowSet", b_set: "RowSet", alpha, beta, row, col, ws, ws_bytes: int, stats):
+    """``cmve_l2_count`` or ``cmve_l2_count_resolved`` (``entry``: one argument list; the rest as ``_count_tail``)."""
     check(getattr(lib, entry)(h, C.byref(a_set.desc), C.byref(b_set.desc), float(alpha), float(beta),
-                              _ptr(roff), _ptr(rsc) if ritems else None, ritems, rn, _ptr(rpos),
-                              _ptr(coff), _ptr(csc) if citems else None, citems, cn, _ptr(cpos),
-                              _ptr(ws) if ws_bytes else None, ws_bytes, _ptr(stats)), entry)
+                              *_count_tail(row, col, ws, ws_bytes, stats)), entry)
 
 
 def _item_scores_into(out, a, b, metric, alpha, beta, score_dtype, off, idx, n_items, col_dir, idx_base):
@@ -424,25 +429,32 @@ def _l1_applies(metric: int, score_dtype) -> bool:
     return metric == _lib.PW_L1 and score_dtype == torch.float64
 
 
-def _l1_forced(name: str, filter, metric: int, alpha: float, beta: float, score_dtype) -> bool:
-    """Whether ``filter`` is the forced value ``"l1"``; ValueError when the SAD filter cannot speak for the call."""
-    if not (isinstance(filter, str) and filter == "l1"):
-        return False
-    if not (_l1_applies(metric, score_dtype) and _l2_scaling_ok(alpha, beta)):
-        raise ValueError(f'{name}: filter="l1" needs PW_L1 with float64 score words, alpha finite and non-zero, '
-                         "beta finite")
-    return True
-
-
-def _l1_auto(filter, metric: int, alpha: float, beta: float, score_dtype, pairs: int, d: int) -> bool:
-    """Whether ``filter=None`` takes the SAD filter at this size (never hands the entry what it refuses)."""
-    return (filter is None and L1_FILTER_MIN_PAIRS is not None and _l1_applies(metric, score_dtype)
-            and _l2_scaling_ok(alpha, beta) and pairs >= L1_FILTER_MIN_PAIRS and d <= L1_D_MAX)
-
-
-def _l1_count_stats(host) -> dict:
-    """{decided, band, rescored, overflow} of ``cmve_l1_count``: ``cmve_l2_count_resolved``'s four words."""
-    return _l2_count_stats(host)
+def _filter_route(name: str, filter, metric: int, alpha: float, beta: float, score_dtype, l2_scaling: bool,
+                  size=None) -> Optional[str]:
+    """THE route of a count: None (fp64), ``"l2"`` (the MFMA filter) or ``"l1"`` (the SAD filter), at two moments.
+    size None -- before any operand is touched: a forced value (True, ``"l1"``) gives its route, or ValueError where
+    that filter cannot speak for the call; ``filter=True`` judges alpha / beta here only with ``l2_scaling`` (else a
+    bad scaling is the C entry's to refuse).  size = (na * nb, d, the sets are ones the Euclidean entries take) --
+    the auto rule of ``filter=None``, which never hands an entry what it refuses."""
+    scaling = _l2_scaling_ok(alpha, beta)
+    if size is None:
+        if isinstance(filter, str) and filter == "l1":
+            if not (_l1_applies(metric, score_dtype) and scaling):
+                raise ValueError(f'{name}: filter="l1" needs PW_L1 with float64 score words, alpha finite and '
+                                 "non-zero, beta finite")
+            return "l1"
+        if filter:
+            if not (_l2_applies(metric, score_dtype) and (scaling or not l2_scaling)):
+                raise ValueError(f"{name}: filter=True needs PW_L2 with float64 score words"
+                                 + (", alpha finite and non-zero, beta finite" if l2_scaling else ""))
+            return "l2"
+        return None
+    pairs, d, sets_ok = size
+    if filter is not None or not scaling:
+        return None
+    if _l1_applies(metric, score_dtype):
+        return "l1" if L1_FILTER_MIN_PAIRS is not None and pairs >= L1_FILTER_MIN_PAIRS and d <= L1_D_MAX else None
+    return "l2" if _l2_applies(metric, score_dtype) and pairs >= L2_FILTER_MIN_PAIRS and sets_ok else None
 
 
 def l1_pack_size(n: int, d: int) -> Tuple[int, int]:
@@ -509,16 +521,12 @@ def _l1_sets(a, b, a_set: Optional["L1Set"], b_set: Optional["L1Set"]):
 
 
 def _l1_count_call(h, a_set: "L1Set", b_set: "L1Set", alpha, beta, row, col, ws, ws_bytes: int, stats):
-    """``cmve_l1_count``.  row / col: (offsets, item scores, items, n, positions) of the direction; ws: the band
-    list's tensor, ws_bytes of it handed over."""
-    (roff, rsc, ritems, rn, rpos), (coff, csc, citems, cn, cpos) = row, col
+    """``cmve_l1_count`` (row / col / ws / stats as ``_count_tail``)."""
     a, b = a_set.raw, b_set.raw
     check(lib.cmve_l1_count(h, _ptr(a), _dtype_code(a), _pw_ld(a), a_set.n, _ptr(a_set.codes), _ptr(a_set.err),
                             _ptr(b), _dtype_code(b), _pw_ld(b), b_set.n, _ptr(b_set.codes), _ptr(b_set.err), a_set.d,
-                            _ptr(a_set.grid), float(alpha), float(beta),
-                            _ptr(roff), _ptr(rsc) if ritems else None, ritems, rn, _ptr(rpos),
-                            _ptr(coff), _ptr(csc) if citems else None, citems, cn, _ptr(cpos),
-                            _ptr(ws) if ws_bytes else None, ws_bytes, _ptr(stats)), "cmve_l1_count")
+                            _ptr(a_set.grid), float(alpha), float(beta), *_count_tail(row, col, ws, ws_bytes, stats)),
+          "cmve_l1_count")
 
 
 class _PairwisePositions:
@@ -539,10 +547,7 @@ class _PairwisePositions:
 
     def __init__(self, a, b, metric, alpha, beta, score_dtype, row_lists=None, col_lists=None, filter=None):
         self.filter_stats = None
-        applies = _l2_applies(metric, score_dtype)
-        l1 = _l1_forced("pairwise_gt_positions", filter, metric, alpha, beta, score_dtype)
-        if filter and not l1 and not applies:
-            raise ValueError("pairwise_gt_positions: filter=True needs PW_L2 with float64 score words")
+        route = _filter_route("pairwise_gt_positions", filter, metric, alpha, beta, score_dtype, False)
         a, b = _pw_pair(a, b, "pairwise_gt_positions")
         na, nb, dev = a.shape[0], b.shape[0], a.device
         if row_lists is not None and len(row_lists) != na:
@@ -560,14 +565,11 @@ class _PairwisePositions:
             items = sum(len(l) for l in lists)
             sides.append((off, idx, items, torch.empty(max(items, 1), dtype=torch.int32, device=dev)))
         (roff, ridx, ritems, rpos), (coff, cidx, citems, cpos) = sides
-        l1 = l1 or _l1_auto(filter, metric, alpha, beta, score_dtype, na * nb, a.shape[1])
-        if filter is None:
-            filter = applies and na * nb >= L2_FILTER_MIN_PAIRS and _l2_scaling_ok(alpha, beta)
+        route = route or _filter_route("pairwise_gt_positions", filter, metric, alpha, beta, score_dtype, False,
+                                       (na * nb, a.shape[1], True))
         sc = None
-        if l1 and na and nb and ritems + citems:
-            sc = self._filtered_l1(a, b, alpha, beta, sides)
-        elif filter and not l1 and na and nb and ritems + citems:
-            sc = self._filtered(a, b, alpha, beta, sides)
+        if route and na and nb and ritems + citems:
+            sc = (self._filtered_l1 if route == "l1" else self._filtered)(a, b, alpha, beta, sides)
         if sc is None:
             nbytes = pairwise_positions_workspace(na, nb, ritems, citems, metric)
             ws = torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=dev)
@@ -579,27 +581,36 @@ class _PairwisePositions:
             sc = ws.cpu().numpy()
         self._collect(sides, sc)
 
+    def _filter_pass(self, a, b, metric, alpha, beta, sides):
+        """What the two filtered routes share.  The items' scores are computed into ONE device buffer with room for the
+        counters; the run(call, nbytes) returned makes a workspace of nbytes, has call(row, col, ws, nbytes, stats)
+        count into the sides' position buffers, and brings scores and counters to the host in one copy: (scores,
+        {decided, band, rescored, overflow})."""
+        (roff, _, ritems, rpos), (coff, _, citems, cpos) = sides
+        na, nb, items = a.shape[0], b.shape[0], sides[0][2] + sides[1][2]
+        buf = self._item_scores(a, b, metric, alpha, beta, sides)
+        row, col = (roff, buf[:ritems], ritems, nb, rpos), (coff, buf[ritems:items], citems, na, cpos)
+
+        def run(call, nbytes):
+            ws = torch.empty(max(nbytes // 8, 1), dtype=torch.int64, device=a.device)
+            call(row, col, ws, nbytes, buf[items:])
+            host = buf.cpu().numpy()
+            return host[:items], _l2_count_stats(host[items:].view(np.int64))
+        return run
+
     def _filtered(self, a, b, alpha, beta, sides):
         """The K19 route into the sides' position buffers; the items' scores (host), or None when the band is too
         large for the filter to pay (the caller then runs the fp64 route)."""
-        (roff, ridx, ritems, rpos), (coff, cidx, citems, cpos) = sides
-        na, nb, dev, h = a.shape[0], b.shape[0], a.device, handle(a.device)
+        dev, h, pairs = a.device, handle(a.device), a.shape[0] * b.shape[0]
         ra, rb = RowSet(a, with_lo=False, device=dev), RowSet(b, with_lo=False, device=dev)
-        a, b = ra.raw, rb.raw
-        buf = self._item_scores(a, b, _lib.PW_L2, alpha, beta, sides)
-        rsc, csc, stats = buf[:ritems], buf[ritems:ritems + citems], buf[ritems + citems:]
-        pairs = na * nb
+        run = self._filter_pass(ra.raw, rb.raw, _lib.PW_L2, alpha, beta, sides)
         cap = l2_band_cap(pairs)
         for attempt in range(2):
-            nbytes = l2_count_workspace(ra, rb, cap)
-            ws = torch.empty(max(nbytes // 8, 1), dtype=torch.int64, device=dev)
-            _l2_count_call("cmve_l2_count", h, ra, rb, alpha, beta, (roff, rsc, ritems, nb, rpos),
-                           (coff, csc, citems, na, cpos), ws, nbytes, stats)
-            host = buf.cpu().numpy()
-            st = _l2_count_stats(host[ritems + citems:].view(np.int64))
+            sc, st = run(lambda *tail: _l2_count_call("cmve_l2_count", h, ra, rb, alpha, beta, *tail),
+                         l2_count_workspace(ra, rb, cap))
             self.filter_stats = dict(st, redone=attempt > 0, fallback=False)
             if not st["overflow"]:
-                return host[:ritems + citems]
+                return sc
             cap = l2_band_plan(pairs, st["band"], st["overflow"], cap)  # (the call zeroes the positions again)
             if attempt or cap is None:
                 break
@@ -626,19 +637,13 @@ class _PairwisePositions:
     def _filtered_l1(self, a, b, alpha, beta, sides):
         """The K22 route into the sides' position buffers; the items' scores (host).  ONE ``cmve_l1_count`` call:
         a band list that overflows is resolved on the device (``fallback``: the canonical count ran), never redone."""
-        (roff, ridx, ritems, rpos), (coff, cidx, citems, cpos) = sides
-        na, nb, dev = a.shape[0], b.shape[0], a.device
+        h = handle(a.device)
         sa, sb = _l1_sets(a, b, None, None)
-        buf = self._item_scores(a, b, _lib.PW_L1, alpha, beta, sides)
-        rsc, csc, stats = buf[:ritems], buf[ritems:ritems + citems], buf[ritems + citems:]
-        nbytes = l1_count_workspace(l2_band_cap(na * nb))
-        ws = torch.empty(max(nbytes // 8, 1), dtype=torch.int64, device=dev)
-        _l1_count_call(handle(dev), sa, sb, alpha, beta, (roff, rsc, ritems, nb, rpos), (coff, csc, citems, na, cpos),
-                       ws, nbytes, stats)
-        host = buf.cpu().numpy()
-        st = _l1_count_stats(host[ritems + citems:].view(np.int64))
+        run = self._filter_pass(a, b, _lib.PW_L1, alpha, beta, sides)
+        sc, st = run(lambda *tail: _l1_count_call(h, sa, sb, alpha, beta, *tail),
+                     l1_count_workspace(l2_band_cap(a.shape[0] * b.shape[0])))
         self.filter_stats = dict(st, redone=False, fallback=bool(st["overflow"]))
-        return host[:ritems + citems]
+        return sc
 
     def _collect(self, sides, sc):
         self.pos, self.nan = [], []
@@ -754,11 +759,7 @@ def pairwise_count(a, b, metric: int, alpha: float, beta: float, score_dtype, ro
     na * nb reaches ``L1_FILTER_MIN_PAIRS`` (never while that is None).  a / b may then be an ``L1Set`` (a resident
     side packed once; the other side is packed on its grid inside the call) -- plain rows on both sides share a
     grid made from both.  ``band`` / ``return_stats`` as above."""
-    applies = _l2_applies(metric, score_dtype) and _l2_scaling_ok(alpha, beta)
-    l1 = _l1_forced("pairwise_count", filter, metric, alpha, beta, score_dtype)
-    if filter and not l1 and not applies:
-        raise ValueError("pairwise_count: filter=True needs PW_L2 with float64 score words, alpha finite and "
-                         "non-zero, beta finite")
+    route = _filter_route("pairwise_count", filter, metric, alpha, beta, score_dtype, True)
     a_l1, b_l1 = (a if isinstance(a, L1Set) else None), (b if isinstance(b, L1Set) else None)
     a_set = a if isinstance(a, RowSet) else None
     b_set = b if isinstance(b, RowSet) else None
@@ -777,29 +778,26 @@ def pairwise_count(a, b, metric: int, alpha: float, beta: float, score_dtype, ro
             raise TypeError("pairwise_count: item scores are contiguous float64")
         sides.append((off, sc, sc.numel(), int(n), torch.empty(max(sc.numel(), 1), dtype=torch.int32, device=dev)))
     (roff, rsc, ritems, rn, rpos), (coff, csc, citems, cn, cpos) = sides
-    l1 = l1 or _l1_auto(filter, metric, alpha, beta, score_dtype, na * nb, a.shape[1])
-    if filter is None:  # auto never hands the entry what it refuses; filter=True does, and the entry says so
-        filter = applies and na * nb >= L2_FILTER_MIN_PAIRS and _l2_set_ok(a_set) and _l2_set_ok(b_set)
+    # (auto never hands the entry what it refuses; filter=True does, and the entry says so)
+    route = route or _filter_route("pairwise_count", filter, metric, alpha, beta, score_dtype, True,
+                                   (na * nb, a.shape[1], _l2_set_ok(a_set) and _l2_set_ok(b_set)))
     stats = None
-    if (l1 or filter) and band is not None and (band.dtype != torch.int64 or not band.is_contiguous()
-                                                or band.device != dev):
-        raise TypeError("pairwise_count: band is a contiguous int64 tensor on the rows' device")
-    if l1:
-        a_l1, b_l1 = _l1_sets(a, b, a_l1, b_l1)
+    if route:
         if band is None:
             band = torch.empty(l2_band_cap(na * nb), dtype=torch.int64, device=dev)
+        elif band.dtype != torch.int64 or not band.is_contiguous() or band.device != dev:
+            raise TypeError("pairwise_count: band is a contiguous int64 tensor on the rows' device")
         stats = torch.empty(4, dtype=torch.int64, device=dev)
+    if route == "l1":
+        a_l1, b_l1 = _l1_sets(a, b, a_l1, b_l1)
         _l1_count_call(handle(dev), a_l1, b_l1, alpha, beta, sides[0], sides[1], band, _nbytes(band), stats)
-    elif filter:
+    elif route == "l2":
         if a_l1 is not None or b_l1 is not None:
             raise TypeError("pairwise_count: an L1Set is packed for filter=\"l1\"; the Euclidean filter takes a RowSet")
         if a_set is None:
             a_set = RowSet(a, with_lo=False, device=dev)
         if b_set is None:
             b_set = RowSet(b, with_lo=False, device=dev)
-        if band is None:
-            band = torch.empty(l2_band_cap(na * nb), dtype=torch.int64, device=dev)
-        stats = torch.empty(4, dtype=torch.int64, device=dev)
         _l2_count_call("cmve_l2_count_resolved", handle(dev), a_set, b_set, alpha, beta, sides[0], sides[1], band,
                        _nbytes(band), stats)
     else:

@@ -42,14 +42,6 @@ void dist_release(cmve_handle* h);
 // k-way merge of sorted top-k runs (merge.hip): entry (q, run l, pos p) at q * q_stride + l * l_stride + p
 int merge_topk_launch(hipStream_t s, const int64_t* ids, const double* scores, int64_t n_q, int lists, int k_in,
                       int64_t q_stride, int64_t l_stride, int k_out, int64_t* out_ids, double* out_scores);
-// cmve_pairwise_count's counting tiles (pairwise_rank.hip) under `metric` = CMVE_PW_L2 or CMVE_PW_L1 with fp64 score
-// words, gated: a bounded grid whose blocks return at once when *gate is 0 and loop over the tiles otherwise (K21
-// cmve_l2_count_resolved, K22 cmve_l1_count).  pos must be zero where *gate is not.
-void pwr_count_gated_launch(hipStream_t st, const void* A, int32_t a_dtype, int64_t lda, int64_t na, const void* B,
-                            int32_t b_dtype, int64_t ldb, int64_t nb, int64_t d, int32_t metric, double alpha,
-                            double beta, const int64_t* row_off, const double* row_sc, int64_t row_n, int32_t* row_pos,
-                            const int64_t* col_off, const double* col_sc, int64_t col_n, int32_t* col_pos,
-                            const unsigned long long* gate);
 // Kernel-exact launch timing: when armed, the next launch made through cmve::launch records its own start
 // and stop on these events (hipExtLaunchKernelGGL: the dispatch's timestamps, the duration rocprofv3
 // reports -- events recorded around a launch also count its dispatch gap)

@@ -17,6 +17,7 @@
 //                    (a straight copy of the packed block; k-major, so a thread's 8 rows of a code dword are two
 //                    ds_read_b128); fp64 epilogue as l2f_main_kernel's: interval test against each item, band append,
 //                    counts (shuffle / LDS partial sums, one integer atomic per (item, tile): bit-reproducible)
+#include "filter_count.h"
 #include "l1_filter_tile.h"
 
 namespace cmve {
@@ -479,70 +480,32 @@ extern "C" int cmve_l1_count(cmve_handle_t h, const void* A, int32_t a_dtype, in
                              int64_t ws_bytes, int64_t* stats) {
   const char* name = "cmve_l1_count";
   CMVE_REQUIRE(h && stats && (A || !na) && (B || !nb), "%s: NULL argument", name);
-  CMVE_REQUIRE(alpha != 0.0 && std::isfinite(alpha) && std::isfinite(beta),
-               "%s: alpha must be finite and non-zero, beta finite (%g, %g)", name, alpha, beta);
-  CMVE_REQUIRE(d > 0 && d <= L1F_D_MAX, "%s: d must be in [1, %lld] (%lld): the u32 SAD is exact up to there", name,
-               (long long)L1F_D_MAX, (long long)d);
-  CMVE_REQUIRE(na >= 0 && nb >= 0 && na < (1ll << 31) && nb < (1ll << 31) && lda >= d && ldb >= d, "%s: bad shape",
-               name);
-  CMVE_REQUIRE(l1f_dtype_ok(a_dtype) && l1f_dtype_ok(b_dtype), "%s: rows must be CMVE_F32/CMVE_F64", name);
-  CMVE_REQUIRE(grid && ((a_codes && a_err) || !na) && ((b_codes && b_err) || !nb),
-               "%s: the codes, the row errors or the grid are missing (cmve_l1_grid, cmve_l1_pack)", name);
-  CMVE_REQUIRE(((((uintptr_t)a_codes) | ((uintptr_t)b_codes)) & 15) == 0, "%s: codes must be 16-byte aligned", name);
-  if (!row_pos) row_items = 0;
-  if (!col_pos) col_items = 0;
-  CMVE_REQUIRE(row_items >= 0 && col_items >= 0 && row_n >= 0 && col_n >= 0 && row_n < (1ll << 31) &&
-                   col_n < (1ll << 31) && row_items < (1ll << 31) * 256 && col_items < (1ll << 31) * 256,
-               "%s: bad counts (%lld, %lld items; n %lld, %lld)", name, (long long)row_items, (long long)col_items,
-               (long long)row_n, (long long)col_n);
-  CMVE_REQUIRE(!row_pos || (row_off && (row_sc || !row_items)), "%s: row lists missing", name);
-  CMVE_REQUIRE(!col_pos || (col_off && (col_sc || !col_items)), "%s: column lists missing", name);
-  CMVE_REQUIRE(ws_bytes >= 0 && (ws || ws_bytes < 8), "%s: workspace missing", name);
-  CMVE_REQUIRE((((uintptr_t)ws) & 7) == 0, "%s: workspace must be 8-byte aligned", name);
-  const int64_t tiles_a = (na + L1F_BM - 1) / L1F_BM, tiles_b = (nb + L1F_BN - 1) / L1F_BN;
-  CMVE_REQUIRE(tiles_a * tiles_b < (1ll << 31), "%s: too many tiles (%lld x %lld)", name, (long long)tiles_a,
-               (long long)tiles_b);
-  const hipStream_t st = h->stream;
-  CMVE_HIP(hipMemsetAsync(stats, 0, 4 * sizeof(int64_t), st));
-  if (row_items + col_items == 0) return CMVE_OK;
-  if (row_items) CMVE_HIP(hipMemsetAsync(row_pos, 0, sizeof(int32_t) * row_items, st));
-  if (col_items) CMVE_HIP(hipMemsetAsync(col_pos, 0, sizeof(int32_t) * col_items, st));
-  // the NaN items' words are the caller's n, whatever this call's own na / nb
-  if (row_items && row_n && na) l2f_nan_launch(st, row_off, row_sc, na, row_n, row_pos);
-  if (col_items && col_n && nb) l2f_nan_launch(st, col_off, col_sc, nb, col_n, col_pos);
-  if (na == 0 || nb == 0) return check_launch("l1_count");
-  int64_t n_pad = 0, d_pad = 0;
-  l1f_pads(na, d, n_pad, d_pad);
-  L1fArgs g;
-  g.a_codes = (const uint32_t*)a_codes;
-  g.b_codes = (const uint32_t*)b_codes;
-  g.a_err = a_err;
-  g.b_err = b_err;
-  g.grid = grid;
-  g.na = na;
-  g.nb = nb;
-  g.nkt = (int)(d_pad / L1F_BK);
-  g.alpha = alpha;
-  g.beta = beta;
-  g.rho = 2.0 * ((double)d + 16.0) * L2F_U;     // DESIGN s4 (K22)
-  g.lim = (1e300 - fabs(beta)) / fabs(alpha);   // below it the canonical word alpha * S + beta cannot overflow
-  g.row_off = row_off;
-  g.row_sc = row_sc;
-  g.row_pos = row_items ? row_pos : nullptr;
-  g.col_off = col_off;
-  g.col_sc = col_sc;
-  g.col_pos = col_items ? col_pos : nullptr;
-  g.band = (int2*)ws;
-  g.cap = ws_bytes / (int64_t)sizeof(int2);
-  g.stats = (l2f_u64*)stats;
-  g.tiles_a = (int)tiles_a;
-  g.tiles_b = (int)tiles_b;
-  hipLaunchKernelGGL(l1f_main_kernel, dim3((unsigned)(tiles_a * tiles_b)), dim3(256), 0, st, g);
-  if (g.cap > 0)
-    l2f_fixup_launch(st, CMVE_PW_L1, A, a_dtype, lda, B, b_dtype, ldb, d, alpha, beta, row_off, row_sc, g.row_pos,
-                     col_off, col_sc, g.col_pos, g.band, g.cap, stats);
-  // an overflowing list is resolved on the device, from the start: no entry leaves it to the host
-  l2f_resolve_launch(st, CMVE_PW_L1, A, a_dtype, lda, na, B, b_dtype, ldb, nb, d, alpha, beta, row_off, row_sc,
-                     row_items, row_n, g.row_pos, col_off, col_sc, col_items, col_n, g.col_pos, stats);
-  return check_launch("l1_count");
+  auto own_checks = [&]() -> int {
+    CMVE_REQUIRE(d > 0 && d <= L1F_D_MAX, "%s: d must be in [1, %lld] (%lld): the u32 SAD is exact up to there", name,
+                 (long long)L1F_D_MAX, (long long)d);
+    CMVE_REQUIRE(na >= 0 && nb >= 0 && na < (1ll << 31) && nb < (1ll << 31) && lda >= d && ldb >= d, "%s: bad shape",
+                 name);
+    CMVE_REQUIRE(l1f_dtype_ok(a_dtype) && l1f_dtype_ok(b_dtype), "%s: rows must be CMVE_F32/CMVE_F64", name);
+    CMVE_REQUIRE(grid && ((a_codes && a_err) || !na) && ((b_codes && b_err) || !nb),
+                 "%s: the codes, the row errors or the grid are missing (cmve_l1_grid, cmve_l1_pack)", name);
+    CMVE_REQUIRE(((((uintptr_t)a_codes) | ((uintptr_t)b_codes)) & 15) == 0, "%s: codes must be 16-byte aligned", name);
+    return CMVE_OK;
+  };
+  auto main_launch = [&](hipStream_t st, const FltArgs& f) {
+    int64_t n_pad = 0, d_pad = 0;
+    l1f_pads(na, d, n_pad, d_pad);
+    // (the kernel's own flat argument block: embedding FltArgs moved its scalar loads and cost the kernel 1.2%)
+    const FltLists& l = f.lists;
+    const L1fArgs g{(const uint32_t*)a_codes, (const uint32_t*)b_codes, a_err, b_err, grid, f.na, f.nb,
+                    (int)(d_pad / L1F_BK), f.alpha, f.beta,
+                    2.0 * ((double)d + 16.0) * L2F_U,    // rho: DESIGN s4 (K22)
+                    (1e300 - fabs(beta)) / fabs(alpha),  // lim: below it alpha * S + beta cannot overflow
+                    l.row_off, l.row_sc, l.row_pos, l.col_off, l.col_sc, l.col_pos, f.band.band, f.band.cap,
+                    f.band.stats, f.tiles_a, f.tiles_b};
+    hipLaunchKernelGGL(l1f_main_kernel, dim3((unsigned)(f.tiles_a * f.tiles_b)), dim3(256), 0, st, g);
+  };
+  // (resolve: an overflowing list is resolved on the device, from the start -- no entry leaves it to the host)
+  return flt_count_run(name, "l1_count", h, CMVE_PW_L1, FltRows{A, a_dtype, lda, na, B, b_dtype, ldb, nb, d}, alpha, beta,
+                       {row_off, row_sc, row_items, row_n, row_pos, col_off, col_sc, col_items, col_n, col_pos}, ws,
+                       ws_bytes, stats, true, own_checks, main_launch);
 }

@@ -58,21 +58,5 @@ __device__ __forceinline__ void l1f_interval(uint32_t sad, double s, double ea, 
   dhi = ok ? hi : (double)NAN;
 }
 
-// ---- what l2_filter.hip shares with l1_filter.hip: the launches of a filtered count that do not depend on how the
-// pairs were filtered (defined in l2_filter.hip; `metric` is CMVE_PW_L2 or CMVE_PW_L1) ----
-// the NaN items' words of one direction (n_lists lists, the caller's n)
-void l2f_nan_launch(hipStream_t st, const int64_t* off, const double* sc, int64_t n_lists, int64_t n, int32_t* pos);
-// the band list's pairs on the canonical chain (returns at once on the device when the list overflowed)
-void l2f_fixup_launch(hipStream_t st, int32_t metric, const void* A, int32_t a_dtype, int64_t lda, const void* B,
-                      int32_t b_dtype, int64_t ldb, int64_t d, double alpha, double beta, const int64_t* row_off,
-                      const double* row_sc, int32_t* row_pos, const int64_t* col_off, const double* col_sc,
-                      int32_t* col_pos, const void* band, int64_t cap, int64_t* stats);
-// the overflow resolved on the device: zero the words, then cmve_pairwise_count's tiles, both gated on stats[3]
-void l2f_resolve_launch(hipStream_t st, int32_t metric, const void* A, int32_t a_dtype, int64_t lda, int64_t na,
-                        const void* B, int32_t b_dtype, int64_t ldb, int64_t nb, int64_t d, double alpha, double beta,
-                        const int64_t* row_off, const double* row_sc, int64_t row_items, int64_t row_n,
-                        int32_t* row_pos, const int64_t* col_off, const double* col_sc, int64_t col_items,
-                        int64_t col_n, int32_t* col_pos, const int64_t* stats);
-
 }  // namespace cmve
 #endif

@@ -18,7 +18,7 @@
 // K21 (cmve_l2_count_resolved): the same launches, then two that read the overflow word and do nothing when it is 0 --
 //   l2f_gated_zero_kernel zeroes the words, pairwise_rank.hip's gated pwr_count_kernel counts every pair on the
 //   canonical chain -- so the words are cmve_pairwise_count's whatever the band did, with no host read in between.
-#include "l1_filter_tile.h"  // (l2_filter_tile.h, and the launches this file defines for both filters)
+#include "filter_count.h"
 
 namespace cmve {
 namespace {
@@ -30,19 +30,9 @@ struct L2fArgs {
   const double* b_inv;
   const float* a_err;   // >= || x_hat - h16 ||
   const float* b_err;
-  int64_t na, nb, d_pad;
-  double alpha, beta;
+  int64_t d_pad;
   L2fConsts c;   // gamma, theta, kappa, rho (l2_filter_tile.h)
-  const int64_t* row_off;
-  const double* row_sc;
-  int32_t* row_pos;
-  const int64_t* col_off;
-  const double* col_sc;
-  int32_t* col_pos;
-  int2* band;
-  int64_t cap;
-  l2f_u64* stats;  // {decided, band found, band re-scored, overflow}
-  int tiles_a, tiles_b;
+  FltArgs f;
 };
 
 // the epilogue's LDS, laid over the staging buffers once the K loop is done
@@ -63,7 +53,7 @@ __global__ __launch_bounds__(256, 2) void l2f_main_kernel(L2fArgs a) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1, fr = lane & 15, fq = lane >> 4;
   int ta, tb_;
-  l2f_tile_of_block(blockIdx.x, a.tiles_a, a.tiles_b, ta, tb_);
+  l2f_tile_of_block(blockIdx.x, a.f.tiles_a, a.f.tiles_b, ta, tb_);
   const int64_t i0 = (int64_t)ta * L2F_BM, j0 = (int64_t)tb_ * L2F_BN;
 
   // ---- the GEMM: c[tm][tn] = 16 x 16 blocks of the wave's 64 x 64 (rows below n_pad, a multiple of 256: in bounds)
@@ -78,11 +68,11 @@ __global__ __launch_bounds__(256, 2) void l2f_main_kernel(L2fArgs a) {
   __syncthreads();
   if (tid < L2F_BM) {
     const int64_t i = i0 + tid;
-    const bool v = i < a.na;
+    const bool v = i < a.f.na;
     E.an[tid] = l2f_side_norm(i, v, a.a_inv);
     E.ae[tid] = l2f_side_err(i, v, a.a_err, a.c.theta);
-    const int64_t o = (v && a.row_pos) ? a.row_off[i] : 0;
-    const int m = (v && a.row_pos) ? (int)(a.row_off[i + 1] - o) : 0;
+    const int64_t o = (v && a.f.lists.row_pos) ? a.f.lists.row_off[i] : 0;
+    const int m = (v && a.f.lists.row_pos) ? (int)(a.f.lists.row_off[i + 1] - o) : 0;
     E.ro[tid] = o;
     E.mr[tid] = m;
     E.rc[tid] = 0;
@@ -90,11 +80,11 @@ __global__ __launch_bounds__(256, 2) void l2f_main_kernel(L2fArgs a) {
   } else {
     const int t = tid - L2F_BM;
     const int64_t j = j0 + t;
-    const bool v = j < a.nb;
+    const bool v = j < a.f.nb;
     E.bn[t] = l2f_side_norm(j, v, a.b_inv);
     E.be[t] = l2f_side_err(j, v, a.b_err, a.c.theta);
-    const int64_t o = (v && a.col_pos) ? a.col_off[j] : 0;
-    const int m = (v && a.col_pos) ? (int)(a.col_off[j + 1] - o) : 0;
+    const int64_t o = (v && a.f.lists.col_pos) ? a.f.lists.col_off[j] : 0;
+    const int m = (v && a.f.lists.col_pos) ? (int)(a.f.lists.col_off[j + 1] - o) : 0;
     E.co[t] = o;
     E.mc[t] = m;
     E.cc[t] = 0;
@@ -111,7 +101,7 @@ __global__ __launch_bounds__(256, 2) void l2f_main_kernel(L2fArgs a) {
     for (int r = 0; r < 4; ++r)
 #pragma unroll
       for (int n = 0; n < 4; ++n)
-        if (i0 + rbase + 16 * m + r < a.na && j0 + cbase + 16 * n < a.nb) valid |= 1ull << ((m * 4 + r) * 4 + n);
+        if (i0 + rbase + 16 * m + r < a.f.na && j0 + cbase + 16 * n < a.f.nb) valid |= 1ull << ((m * 4 + r) * 4 + n);
 
   // one round: item `it` of every row and column list.  PASS 0 marks the pairs some item cannot decide, PASS 1
   // counts the decided ones.
@@ -120,19 +110,19 @@ __global__ __launch_bounds__(256, 2) void l2f_main_kernel(L2fArgs a) {
       if (tid < L2F_BM) {
         double tb = (double)NAN, tn = (double)NAN;
         const bool has = it < E.mr[tid];
-        if (has) l2f_thresholds(a.row_sc[E.ro[tid] + it], a.alpha, a.beta, a.c.rho, tb, tn);
+        if (has) l2f_thresholds(a.f.lists.row_sc[E.ro[tid] + it], a.f.alpha, a.f.beta, a.c.rho, tb, tn);
         E.rtb[tid] = tb;
         E.rtn[tid] = tn;
       } else {
         const int t = tid - L2F_BM;
         double tb = (double)NAN, tn = (double)NAN;
         const bool has = it < E.mc[t];
-        if (has) l2f_thresholds(a.col_sc[E.co[t] + it], a.alpha, a.beta, a.c.rho, tb, tn);
+        if (has) l2f_thresholds(a.f.lists.col_sc[E.co[t] + it], a.f.alpha, a.f.beta, a.c.rho, tb, tn);
         E.ctb[t] = tb;
         E.ctn[t] = tn;
       }
       __syncthreads();
-      const bool pos = a.alpha > 0.0;
+      const bool pos = a.f.alpha > 0.0;
       int ccnt[4] = {0, 0, 0, 0};
 #pragma unroll
       for (int m = 0; m < 4; ++m) {
@@ -194,12 +184,12 @@ __global__ __launch_bounds__(256, 2) void l2f_main_kernel(L2fArgs a) {
       if (pass == 1) {  // one integer atomic per (item, tile)
         if (tid < L2F_BM) {
           const int c = E.rc[tid];
-          if (c && it < E.mr[tid]) gadd(a.row_pos + E.ro[tid] + it, (int32_t)c);
+          if (c && it < E.mr[tid]) gadd(a.f.lists.row_pos + E.ro[tid] + it, (int32_t)c);
           E.rc[tid] = 0;
         } else {
           const int t = tid - L2F_BM;
           const int c = E.cc[t];
-          if (c && it < E.mc[t]) gadd(a.col_pos + E.co[t] + it, (int32_t)c);
+          if (c && it < E.mc[t]) gadd(a.f.lists.col_pos + E.co[t] + it, (int32_t)c);
           E.cc[t] = 0;
         }
         // (the next round's threshold writes and this read touch different words; its barrier orders the counters)
@@ -227,13 +217,13 @@ __global__ __launch_bounds__(256, 2) void l2f_main_kernel(L2fArgs a) {
       __syncthreads();
       if (tid == 0) {
         const int total = E.band_cnt;
-        const int nv = (int)(min<int64_t>(L2F_BM, a.na - i0) * min<int64_t>(L2F_BN, a.nb - j0));
+        const int nv = (int)(min<int64_t>(L2F_BM, a.f.na - i0) * min<int64_t>(L2F_BN, a.f.nb - j0));
         long long base = 0;
         if (total) {
-          base = (long long)gadd(a.stats + 1, (l2f_u64)total);
-          if (base + total > a.cap) gmax(a.stats + 3, (l2f_u64)1);
+          base = (long long)gadd(a.f.band.stats + 1, (l2f_u64)total);
+          if (base + total > a.f.band.cap) gmax(a.f.band.stats + 3, (l2f_u64)1);
         }
-        if (nv - total) gadd(a.stats + 0, (l2f_u64)(nv - total));
+        if (nv - total) gadd(a.f.band.stats + 0, (l2f_u64)(nv - total));
         E.band_base = base;
       }
       __syncthreads();
@@ -244,7 +234,7 @@ __global__ __launch_bounds__(256, 2) void l2f_main_kernel(L2fArgs a) {
           const int bit = __ffsll((long long)b) - 1;
           b &= b - 1;
           const int n = bit & 3, r = (bit >> 2) & 3, m = bit >> 4;
-          if (p < a.cap) a.band[p] = make_int2((int)(i0 + rbase + 16 * m + r), (int)(j0 + cbase + 16 * n));
+          if (p < a.f.band.cap) a.f.band.band[p] = make_int2((int)(i0 + rbase + 16 * m + r), (int)(j0 + cbase + 16 * n));
           ++p;
         }
       }
@@ -320,40 +310,34 @@ __global__ __launch_bounds__(256) void l2f_gated_zero_kernel(int32_t* __restrict
 
 }  // namespace
 
-// ---- the launches K22's SAD filter shares (l1_filter_tile.h) -------------------------------------------------------------
+// ---- the launches every filtered count shares (filter_count.h) -------------------------------------------------------------
 void l2f_nan_launch(hipStream_t st, const int64_t* off, const double* sc, int64_t n_lists, int64_t n, int32_t* pos) {
   hipLaunchKernelGGL(l2f_nan_kernel, dim3((unsigned)((n_lists + 255) / 256)), dim3(256), 0, st, off, sc, n_lists, n,
                      pos);
 }
 
-void l2f_fixup_launch(hipStream_t st, int32_t metric, const void* A, int32_t a_dtype, int64_t lda, const void* B,
-                      int32_t b_dtype, int64_t ldb, int64_t d, double alpha, double beta, const int64_t* row_off,
-                      const double* row_sc, int32_t* row_pos, const int64_t* col_off, const double* col_sc,
-                      int32_t* col_pos, const void* band, int64_t cap, int64_t* stats) {
-  const int fix_blocks = (int)std::max<int64_t>(1, std::min<int64_t>(8 * device_cus(), (cap + 255) / 256));
+void l2f_fixup_launch(hipStream_t st, int32_t metric, const FltRows& r, double alpha, double beta, const FltLists& l,
+                      const FltBand& b) {
+  const int fix_blocks = (int)std::max<int64_t>(1, std::min<int64_t>(8 * device_cus(), (b.cap + 255) / 256));
 #define L2F_FIXUP(M)                                                                                                  \
-  PWR_TYPES(a_dtype, b_dtype, TA, TB, {                                                                               \
-    hipLaunchKernelGGL((l2f_fixup_kernel<M, TA, TB>), dim3((unsigned)fix_blocks), dim3(256), 0, st, (const TA*)A, lda, \
-                       (const TB*)B, ldb, d, alpha, beta, row_off, row_sc, row_pos, col_off, col_sc, col_pos,         \
-                       (const int2*)band, cap, (l2f_u64*)stats);                                                      \
+  PWR_TYPES(r.a_dtype, r.b_dtype, TA, TB, {                                                                           \
+    hipLaunchKernelGGL((l2f_fixup_kernel<M, TA, TB>), dim3((unsigned)fix_blocks), dim3(256), 0, st, (const TA*)r.A,   \
+                       r.lda, (const TB*)r.B, r.ldb, r.d, alpha, beta, l.row_off, l.row_sc, l.row_pos, l.col_off,     \
+                       l.col_sc, l.col_pos, (const int2*)b.band, b.cap, b.stats);                                     \
   })
   if (metric == CMVE_PW_L1) { L2F_FIXUP(CMVE_PW_L1) } else { L2F_FIXUP(CMVE_PW_L2) }
 #undef L2F_FIXUP
 }
 
-void l2f_resolve_launch(hipStream_t st, int32_t metric, const void* A, int32_t a_dtype, int64_t lda, int64_t na,
-                        const void* B, int32_t b_dtype, int64_t ldb, int64_t nb, int64_t d, double alpha, double beta,
-                        const int64_t* row_off, const double* row_sc, int64_t row_items, int64_t row_n,
-                        int32_t* row_pos, const int64_t* col_off, const double* col_sc, int64_t col_items,
-                        int64_t col_n, int32_t* col_pos, const int64_t* stats) {
+void l2f_resolve_launch(hipStream_t st, int32_t metric, const FltRows& r, double alpha, double beta, const FltLists& l,
+                        const l2f_u64* stats) {
   // the list overflowed (decided on the device: both launches do nothing otherwise): the words so far are
   // dropped and cmve_pairwise_count's kernel counts every pair on the canonical chain, NaN items included
-  const int64_t items = std::max(row_items, col_items);
+  const int64_t items = std::max(l.row_items, l.col_items);
   const int zero_blocks = (int)std::max<int64_t>(1, std::min<int64_t>(8 * device_cus(), (items + 255) / 256));
-  hipLaunchKernelGGL(l2f_gated_zero_kernel, dim3((unsigned)zero_blocks), dim3(256), 0, st, row_pos, row_items, col_pos,
-                     col_items, (const l2f_u64*)stats + 3);
-  pwr_count_gated_launch(st, A, a_dtype, lda, na, B, b_dtype, ldb, nb, d, metric, alpha, beta, row_off, row_sc, row_n,
-                         row_pos, col_off, col_sc, col_n, col_pos, (const l2f_u64*)stats + 3);
+  hipLaunchKernelGGL(l2f_gated_zero_kernel, dim3((unsigned)zero_blocks), dim3(256), 0, st, l.row_pos, l.row_items,
+                     l.col_pos, l.col_items, stats + 3);
+  pwr_count_gated_launch(st, metric, r, alpha, beta, l, stats + 3);
 }
 
 }  // namespace cmve
@@ -371,81 +355,29 @@ extern "C" int cmve_l2_count_workspace(const cmve_rows_t* a, const cmve_rows_t* 
   return CMVE_OK;
 }
 
-// cmve_l2_count and cmve_l2_count_resolved: the checks (refusals name the entry) and K19's launches; `resolved` adds
+// cmve_l2_count and cmve_l2_count_resolved: the sets' own checks and the main launch of flt_count_run; `resolved` adds
 // the two launches gated on the overflow word
 static int l2_count_run(const char* name, bool resolved, cmve_handle_t h, const cmve_rows_t* a, const cmve_rows_t* b,
-                        double alpha, double beta, const int64_t* row_off, const double* row_sc, int64_t row_items,
-                        int64_t row_n, int32_t* row_pos, const int64_t* col_off, const double* col_sc,
-                        int64_t col_items, int64_t col_n, int32_t* col_pos, void* ws, int64_t ws_bytes,
-                        int64_t* stats) {
+                        double alpha, double beta, const FltLists& lists, void* ws, int64_t ws_bytes, int64_t* stats) {
   CMVE_REQUIRE(h && a && b && stats, "%s: NULL argument", name);
-  CMVE_REQUIRE(alpha != 0.0 && std::isfinite(alpha) && std::isfinite(beta),
-               "%s: alpha must be finite and non-zero, beta finite (%g, %g)", name, alpha, beta);
-  if (int rc = l2f_check_sets(name, a, b)) return rc;
-  const int64_t na = a->n, nb = b->n, d = a->d;
-  if (!row_pos) row_items = 0;
-  if (!col_pos) col_items = 0;
-  CMVE_REQUIRE(row_items >= 0 && col_items >= 0 && row_n >= 0 && col_n >= 0 && row_n < (1ll << 31) &&
-                   col_n < (1ll << 31) && row_items < (1ll << 31) * 256 && col_items < (1ll << 31) * 256,
-               "%s: bad counts (%lld, %lld items; n %lld, %lld)", name, (long long)row_items,
-               (long long)col_items, (long long)row_n, (long long)col_n);
-  CMVE_REQUIRE(!row_pos || (row_off && (row_sc || !row_items)), "%s: row lists missing", name);
-  CMVE_REQUIRE(!col_pos || (col_off && (col_sc || !col_items)), "%s: column lists missing", name);
-  CMVE_REQUIRE(ws_bytes >= 0 && (ws || ws_bytes < 8), "%s: workspace missing", name);
-  CMVE_REQUIRE((((uintptr_t)ws) & 7) == 0, "%s: workspace must be 8-byte aligned", name);
-  const int64_t tiles_a = (na + L2F_BM - 1) / L2F_BM, tiles_b = (nb + L2F_BN - 1) / L2F_BN;
-  CMVE_REQUIRE(tiles_a * tiles_b < (1ll << 31), "%s: too many tiles (%lld x %lld)", name, (long long)tiles_a,
-               (long long)tiles_b);
-  const hipStream_t st = h->stream;
-  CMVE_HIP(hipMemsetAsync(stats, 0, 4 * sizeof(int64_t), st));
-  if (row_items + col_items == 0) return CMVE_OK;
-  if (row_items) CMVE_HIP(hipMemsetAsync(row_pos, 0, sizeof(int32_t) * row_items, st));
-  if (col_items) CMVE_HIP(hipMemsetAsync(col_pos, 0, sizeof(int32_t) * col_items, st));
-  // the NaN items' words are the caller's n, whatever this call's own na / nb
-  if (row_items && row_n && na) l2f_nan_launch(st, row_off, row_sc, na, row_n, row_pos);
-  if (col_items && col_n && nb) l2f_nan_launch(st, col_off, col_sc, nb, col_n, col_pos);
-  if (na == 0 || nb == 0) return check_launch("l2_count");
-  L2fArgs g;
-  g.a16 = a->h16;
-  g.b16 = b->h16;
-  g.a_inv = a->inv_norm;
-  g.b_inv = b->inv_norm;
-  g.a_err = a->err_h16;
-  g.b_err = b->err_h16;
-  g.na = na;
-  g.nb = nb;
-  g.d_pad = a->d_pad;
-  g.alpha = alpha;
-  g.beta = beta;
-  g.c = l2f_consts(d, a->d_pad);  // DESIGN s4 (K19)
-  g.row_off = row_off;
-  g.row_sc = row_sc;
-  g.row_pos = row_items ? row_pos : nullptr;
-  g.col_off = col_off;
-  g.col_sc = col_sc;
-  g.col_pos = col_items ? col_pos : nullptr;
-  g.band = (int2*)ws;
-  g.cap = ws_bytes / (int64_t)sizeof(int2);
-  g.stats = (l2f_u64*)stats;
-  g.tiles_a = (int)tiles_a;
-  g.tiles_b = (int)tiles_b;
-  hipLaunchKernelGGL(l2f_main_kernel, dim3((unsigned)(tiles_a * tiles_b)), dim3(256), 0, st, g);
-  if (g.cap > 0)
-    l2f_fixup_launch(st, CMVE_PW_L2, a->raw, a->raw_dtype, a->raw_ld, b->raw, b->raw_dtype, b->raw_ld, d, alpha, beta,
-                     row_off, row_sc, g.row_pos, col_off, col_sc, g.col_pos, g.band, g.cap, stats);
-  if (resolved)
-    l2f_resolve_launch(st, CMVE_PW_L2, a->raw, a->raw_dtype, a->raw_ld, na, b->raw, b->raw_dtype, b->raw_ld, nb, d, alpha,
-                       beta, row_off, row_sc, row_items, row_n, g.row_pos, col_off, col_sc, col_items, col_n, g.col_pos,
-                       stats);
-  return check_launch(resolved ? "l2_count_resolved" : "l2_count");
+  const FltRows rows{a->raw, a->raw_dtype, a->raw_ld, a->n, b->raw, b->raw_dtype, b->raw_ld, b->n, a->d};
+  return flt_count_run(
+      name, resolved ? "l2_count_resolved" : "l2_count", h, CMVE_PW_L2, rows, alpha, beta, lists, ws, ws_bytes, stats,
+      resolved, [&] { return l2f_check_sets(name, a, b); },
+      [&](hipStream_t st, const FltArgs& f) {
+        const L2fArgs g{a->h16,     b->h16,   a->inv_norm, b->inv_norm,
+                        a->err_h16, b->err_h16, a->d_pad,  l2f_consts(a->d, a->d_pad), f};  // DESIGN s4 (K19)
+        hipLaunchKernelGGL(l2f_main_kernel, dim3((unsigned)(f.tiles_a * f.tiles_b)), dim3(256), 0, st, g);
+      });
 }
 
 extern "C" int cmve_l2_count(cmve_handle_t h, const cmve_rows_t* a, const cmve_rows_t* b, double alpha, double beta,
                              const int64_t* row_off, const double* row_sc, int64_t row_items, int64_t row_n,
                              int32_t* row_pos, const int64_t* col_off, const double* col_sc, int64_t col_items,
                              int64_t col_n, int32_t* col_pos, void* ws, int64_t ws_bytes, int64_t* stats) {
-  return l2_count_run("cmve_l2_count", false, h, a, b, alpha, beta, row_off, row_sc, row_items, row_n, row_pos, col_off,
-                      col_sc, col_items, col_n, col_pos, ws, ws_bytes, stats);
+  return l2_count_run("cmve_l2_count", false, h, a, b, alpha, beta,
+                      {row_off, row_sc, row_items, row_n, row_pos, col_off, col_sc, col_items, col_n, col_pos}, ws,
+                      ws_bytes, stats);
 }
 
 extern "C" int cmve_l2_count_resolved(cmve_handle_t h, const cmve_rows_t* a, const cmve_rows_t* b, double alpha,
@@ -453,6 +385,7 @@ extern "C" int cmve_l2_count_resolved(cmve_handle_t h, const cmve_rows_t* a, con
                                       int64_t row_n, int32_t* row_pos, const int64_t* col_off, const double* col_sc,
                                       int64_t col_items, int64_t col_n, int32_t* col_pos, void* ws, int64_t ws_bytes,
                                       int64_t* stats) {
-  return l2_count_run("cmve_l2_count_resolved", true, h, a, b, alpha, beta, row_off, row_sc, row_items, row_n, row_pos,
-                      col_off, col_sc, col_items, col_n, col_pos, ws, ws_bytes, stats);
+  return l2_count_run("cmve_l2_count_resolved", true, h, a, b, alpha, beta,
+                      {row_off, row_sc, row_items, row_n, row_pos, col_off, col_sc, col_items, col_n, col_pos}, ws,
+                      ws_bytes, stats);
 }

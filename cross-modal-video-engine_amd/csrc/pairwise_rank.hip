@@ -16,7 +16,7 @@
 //              merged into the running best by K12f (cmve_topk_dense_merge); a small-row geometry of the tile
 //              loop serves n_q <= 8 (inference.py's single caption).  With few queries the chunk is cut into
 //              column segments so that K12f has a block per (segment, query), and C3's k-way merge joins them.
-#include "pairwise_tile.h"
+#include "filter_count.h"  // (pairwise_tile.h; the lists of a count, and the gated launch the filters use)
 
 namespace cmve {
 
@@ -325,22 +325,19 @@ static void pwr_count_launch(hipStream_t st, const void* A, int32_t a_dtype, int
   }))
 }
 
-void pwr_count_gated_launch(hipStream_t st, const void* A, int32_t a_dtype, int64_t lda, int64_t na, const void* B,
-                            int32_t b_dtype, int64_t ldb, int64_t nb, int64_t d, int32_t metric, double alpha,
-                            double beta, const int64_t* row_off, const double* row_sc, int64_t row_n, int32_t* row_pos,
-                            const int64_t* col_off, const double* col_sc, int64_t col_n, int32_t* col_pos,
-                            const unsigned long long* gate) {
+void pwr_count_gated_launch(hipStream_t st, int32_t metric, const FltRows& r, double alpha, double beta,
+                            const FltLists& l, const l2f_u64* gate) {
   // pwr_count_launch's tiles (at least one block row and column: the NaN-item rule) over at most 64 blocks per compute
   // unit: few enough that a shut gate costs microseconds, many enough that an open one keeps the plain grid's balance
   // (8 per compute unit left whole rounds of resident blocks half empty: +1.3 ms on a 13 ms count, DESIGN s4 K21)
-  const int64_t tiles_x = std::max<int64_t>(1, (nb + PW_TB - 1) / PW_TB);
-  const int64_t tiles = tiles_x * std::max<int64_t>(1, (na + PW_TA - 1) / PW_TA);
+  const int64_t tiles_x = std::max<int64_t>(1, (r.nb + PW_TB - 1) / PW_TB);
+  const int64_t tiles = tiles_x * std::max<int64_t>(1, (r.na + PW_TA - 1) / PW_TA);
   const unsigned blocks = (unsigned)std::min<int64_t>(tiles, 64 * (int64_t)device_cus());
 #define PWR_GATED(M)                                                                                                  \
-  PWR_TYPES(a_dtype, b_dtype, TA, TB, {                                                                               \
-    hipLaunchKernelGGL((pwr_count_kernel<M, TA, TB, true>), dim3(blocks), dim3(256), 0, st, (const TA*)A, lda, na,    \
-                       (const TB*)B, ldb, nb, d, alpha, beta, 0, row_off, row_sc, row_n, row_pos, col_off, col_sc,    \
-                       col_n, col_pos, gate, (unsigned)tiles_x, tiles);                                               \
+  PWR_TYPES(r.a_dtype, r.b_dtype, TA, TB, {                                                                           \
+    hipLaunchKernelGGL((pwr_count_kernel<M, TA, TB, true>), dim3(blocks), dim3(256), 0, st, (const TA*)r.A, r.lda,    \
+                       r.na, (const TB*)r.B, r.ldb, r.nb, r.d, alpha, beta, 0, l.row_off, l.row_sc, l.row_n,          \
+                       l.row_pos, l.col_off, l.col_sc, l.col_n, l.col_pos, gate, (unsigned)tiles_x, tiles);           \
   })
   if (metric == CMVE_PW_L1) { PWR_GATED(CMVE_PW_L1) } else { PWR_GATED(CMVE_PW_L2) }
 #undef PWR_GATED
@@ -441,25 +438,18 @@ extern "C" int cmve_pairwise_count(cmve_handle_t h, const void* A, int32_t a_dty
                "cmve_pairwise_count: bad shape");
   CMVE_REQUIRE(pwr_dtypes_ok(a_dtype, b_dtype, score_dtype), "cmve_pairwise_count: dtypes must be CMVE_F32/CMVE_F64");
   CMVE_REQUIRE(metric >= CMVE_PW_SQ_L2 && metric <= CMVE_PW_DOT, "cmve_pairwise_count: unknown metric %d", metric);
-  if (!row_pos) row_items = 0;
-  if (!col_pos) col_items = 0;
-  CMVE_REQUIRE(row_items >= 0 && col_items >= 0 && row_n >= 0 && col_n >= 0 && row_n < (1ll << 31) &&
-                   col_n < (1ll << 31) && row_items < (1ll << 31) * 256 && col_items < (1ll << 31) * 256,
-               "cmve_pairwise_count: bad counts (%lld, %lld items; n %lld, %lld)", (long long)row_items,
-               (long long)col_items, (long long)row_n, (long long)col_n);
-  CMVE_REQUIRE(!row_pos || (row_off && (row_sc || !row_items)), "cmve_pairwise_count: row lists missing");
-  CMVE_REQUIRE(!col_pos || (col_off && (col_sc || !col_items)), "cmve_pairwise_count: column lists missing");
-  if (row_items + col_items == 0) return CMVE_OK;
+  FltLists l{row_off, row_sc, row_items, row_n, row_pos, col_off, col_sc, col_items, col_n, col_pos};
+  if (int rc = flt_check_lists("cmve_pairwise_count", l)) return rc;
+  if (l.row_items + l.col_items == 0) return CMVE_OK;
   CMVE_REQUIRE((na + PW_TA - 1) / PW_TA < 65536, "cmve_pairwise_count: too many rows in A (%lld)", (long long)na);
   const hipStream_t st = h->stream;
-  if (row_items) CMVE_HIP(hipMemsetAsync(row_pos, 0, sizeof(int32_t) * row_items, st));
-  if (col_items) CMVE_HIP(hipMemsetAsync(col_pos, 0, sizeof(int32_t) * col_items, st));
+  if (l.row_items) CMVE_HIP(hipMemsetAsync(l.row_pos, 0, sizeof(int32_t) * l.row_items, st));
+  if (l.col_items) CMVE_HIP(hipMemsetAsync(l.col_pos, 0, sizeof(int32_t) * l.col_items, st));
   // an empty shard has no pair to count; it still runs one block row / column where a direction has items AND an n
   // to apply: the NaN items' words are the caller's n, not this shard's
-  if ((na == 0 || nb == 0) && !(row_items && row_n) && !(col_items && col_n)) return CMVE_OK;
+  if ((na == 0 || nb == 0) && !(l.row_items && row_n) && !(l.col_items && col_n)) return CMVE_OK;
   pwr_count_launch(st, A, a_dtype, lda, na, B, b_dtype, ldb, nb, d, metric, alpha, beta, score_dtype == CMVE_F32,
-                   row_off, row_sc, row_n, row_items ? row_pos : nullptr, col_off, col_sc, col_n,
-                   col_items ? col_pos : nullptr);
+                   row_off, row_sc, row_n, l.row_pos, col_off, col_sc, col_n, l.col_pos);
   return check_launch("pairwise_count");
 }
 

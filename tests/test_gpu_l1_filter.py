@@ -431,3 +431,29 @@ def test_refusals_of_the_entry():
         rc = _lib.lib.cmve_l1_pack(engine.handle(dev), engine._ptr(b), _lib.CMVE_F64, 67, 50, 67, engine._ptr(sa.grid),
                                    engine._ptr(sb.codes), np_, dp_, engine._ptr(sb.err))
         assert rc < 0 and b"short pad" in _lib.lib.cmve_last_error()
+
+
+# ---- 8. a tile without a list (both filters share the epilogue's branch for it) -------------------------------------------
+
+@pytest.mark.parametrize("flt", ["l1", True], ids=["l1", "l2"])
+def test_a_tile_with_no_list_in_it(flt):
+    """256 x 130 x 33: the tiles of rows 128..255 hold no list at all (empty row lists, no column lists), so the count
+    epilogue has nothing to decide there -- but row 200 holds a NaN, its pairs have no interval, and every one of
+    them must still reach the band list so that decided + band = pairs."""
+    import torch
+    from cmve import _lib, engine
+    na, nb, d = 256, 130, 33
+    rng = np.random.default_rng(22)
+    a, b = rng.standard_normal((na, d)), rng.standard_normal((nb, d))
+    a[200, 5] = np.nan
+    rows = [[i % nb] if i < 128 else [] for i in range(na)]
+    metric = _lib.PW_L1 if flt == "l1" else _lib.PW_L2
+    a, b = engine.to_device(a), engine.to_device(b)
+    f = engine._PairwisePositions(a, b, metric, 1.0, 0.0, torch.float64, rows, None, filter=flt)
+    e = engine._PairwisePositions(a, b, metric, 1.0, 0.0, torch.float64, rows, None, filter=False)
+    assert e.filter_stats is None
+    _assert_same_words(f, e)
+    st = f.filter_stats
+    assert st is not None and st["decided"] + st["band"] == na * nb
+    assert st["band"] >= nb
+    assert st["rescored"] == st["band"] and st["overflow"] == 0

@@ -271,3 +271,56 @@ def test_refusals_launch_nothing():
         engine.pairwise_gt_ranks(a, b, _lib.PW_L1, 1.0, 0.0, torch.float64, rows, None, filter=True)
     with pytest.raises(_lib.CmveError, match="alpha"):
         engine.pairwise_gt_ranks(a, b, _lib.PW_L2, 0.0, 0.0, torch.float64, rows, None, filter=True)
+
+
+# ---- the four count entries share one check of the lists (flt_check_lists) ------------------------------------------------
+
+def test_the_four_count_entries_refuse_bad_lists_alike():
+    """cmve_pairwise_count, cmve_l2_count, cmve_l2_count_resolved and cmve_l1_count on 4 x 4 rows of d = 4: the same
+    bad lists get the same code and, past the entry's name, the same words.  Every refusal precedes the first
+    launch."""
+    import torch
+    from cmve import _lib, engine
+    lib = _lib.lib
+    rng = np.random.default_rng(4)
+    a, b = engine.to_device(rng.standard_normal((4, 4))), engine.to_device(rng.standard_normal((4, 4)))
+    dev = a.device
+    h = engine.handle(dev)
+    ra, rb = engine.RowSet(a, with_lo=False, device=dev), engine.RowSet(b, with_lo=False, device=dev)
+    sa = engine.L1Set(a)
+    sb = engine.L1Set(b, grid=sa.grid)
+    off = torch.arange(5, dtype=torch.int64, device=dev)
+    sc = torch.zeros(4, dtype=torch.float64, device=dev)
+    pos = torch.zeros(4, dtype=torch.int32, device=dev)
+    ws = torch.empty(64, dtype=torch.int64, device=dev)
+    stats = torch.zeros(4, dtype=torch.int64, device=dev)
+    p = engine._ptr
+    raw = lambda x: (p(x), _lib.CMVE_F64, 4, 4)
+    tail = (p(ws), 8 * 64, p(stats))
+    entries = {
+        "cmve_pairwise_count": lambda l: lib.cmve_pairwise_count(h, *raw(a), *raw(b), 4, _lib.PW_L2, 1.0, 0.0,
+                                                                 _lib.CMVE_F64, *l),
+        "cmve_l2_count": lambda l: lib.cmve_l2_count(h, C.byref(ra.desc), C.byref(rb.desc), 1.0, 0.0, *l, *tail),
+        "cmve_l2_count_resolved": lambda l: lib.cmve_l2_count_resolved(h, C.byref(ra.desc), C.byref(rb.desc), 1.0, 0.0,
+                                                                       *l, *tail),
+        "cmve_l1_count": lambda l: lib.cmve_l1_count(h, *raw(a), p(sa.codes), p(sa.err), *raw(b), p(sb.codes),
+                                                     p(sb.err), 4, p(sa.grid), 1.0, 0.0, *l, *tail),
+    }
+    good_row, no_col = (p(off), p(sc), 4, 4, p(pos)), (None, None, 0, 0, None)
+    bad = {
+        "negative row_items": (p(off), p(sc), -1, 4, p(pos)) + no_col,
+        "row_n = 2^31": (p(off), p(sc), 4, 1 << 31, p(pos)) + no_col,
+        "row_pos without row_off": (None, p(sc), 4, 4, p(pos)) + no_col,
+        "col_pos without col_sc": good_row + (p(off), None, 4, 4, p(pos)),
+    }
+    for what, lists in bad.items():
+        seen = set()
+        for name, call in entries.items():
+            rc = call(lists)
+            msg = lib.cmve_last_error()
+            assert rc < 0 and msg.startswith(name.encode() + b": "), (what, name, rc, msg)
+            seen.add((rc, msg[len(name):]))
+        assert len(seen) == 1, (what, seen)
+    assert {m for _, m in seen} == {b": column lists missing"}
+    torch.cuda.synchronize()
+    assert not bool(stats.any()) and not bool(pos.any())  # nothing ran

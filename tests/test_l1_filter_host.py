@@ -80,7 +80,7 @@ def test_filter_l1_refuses_before_any_device_call():
         engine.pairwise_count(a, b, _lib.PW_L1, 1.0, 0.0, torch.float64, filter=True)
     # the auto threshold: off, or above the 300 x 520 an existing test expects on the fp64 route
     assert engine.L1_FILTER_MIN_PAIRS is None or engine.L1_FILTER_MIN_PAIRS > 300 * 520
-    assert engine._l1_count_stats(np.array([7, 5, 3, 1], np.int64)) == dict(decided=7, band=5, rescored=3, overflow=1)
+    assert engine._l2_count_stats(np.array([7, 5, 3, 1], np.int64)) == dict(decided=7, band=5, rescored=3, overflow=1)
 
 
 # ---- the bound of DESIGN s4 (K22), restated in numpy ---------------------------------------------------------------------

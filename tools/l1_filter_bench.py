@@ -103,7 +103,7 @@ def bench_headline(doc, save, n_q, n_g, d, warmup, reps):
     for r in range(warmup + reps):
         ts = event_time(fp64_step)[0]
         tt = stage_times(stages)
-        nan_stats = engine._l1_count_stats(cnt.cpu().numpy())
+        nan_stats = engine._l2_count_stats(cnt.cpu().numpy())
         if r >= warmup:
             step.append(ts)
             for k, v in tt.items():
