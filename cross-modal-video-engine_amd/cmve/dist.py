@@ -33,10 +33,15 @@ Top-k merges the shards' local lists on score = -error.  The words are those of 
 Collectives go through a communicator object: ``TorchComm`` is the torch.distributed process
 group (backend "nccl" = RCCL on the GPU, gloo in the CPU tests); ``LocalGroup`` runs N shards in
 ONE process, one thread and HIP stream per shard (a host driving several shards -- on one GPU or
-several -- with the same coordination code).  ``ShardedGallery``'s shard-local arithmetic is a
-handful of methods (``_pack``, ``_row_gt``, ``_col_gt``, ``_count``, ``_ranks``, ``_positions``; under a
-measure ``_pw_rows``, ``_pw_items``, ``_pw_count``, ``_pw_ranks``, ``_pw_topk``)
-over the HIP kernels; the coordination above them is shared by every communicator.
+several -- with the same coordination code).
+
+``ShardedGallery(...)`` is the one constructor and the base class: the layout, the collectives and the endings of
+cal_perf / evaluate / topk that both families share.  It builds a ``CosineShardedGallery`` (``shard``: a RowSet, ``ws``,
+``eps``; the first protocol above) or a ``MeasureShardedGallery`` (``shard``: a Tensor, the filters' pack, band list,
+latch and counters; the second), each with its own bodies of the eight public methods.  A family's shard-local
+arithmetic is a handful of methods over the HIP kernels (``_pack``, ``_row_gt``, ``_col_gt``, ``_count``, ``_ranks``,
+``_positions``; ``_pw_rows``, ``_pw_items``, ``_pw_count``, ``_pw_ranks``, ``_pw_topk``): the seam a test's oracle
+subclass replaces.  The coordination above them is the same for every communicator.
 """
 from __future__ import annotations
 
@@ -476,37 +481,110 @@ _L2_MEASURES = ('euclidean', 'l2', 'l2_norm')  # CMVE_PW_L2 with fp64 score word
 
 
 class ShardedGallery:
-    """This rank's gallery shard [offset, offset + n) of an n_global-video gallery, packed in HBM.
+    """This rank's gallery shard [offset, offset + n) of an n_global-video gallery, resident in HBM: the constructor
+    of both families and what they share -- the layout, the collectives and the endings of cal_perf, evaluate and
+    topk.  ``ShardedGallery(...)`` builds a ``CosineShardedGallery`` under measure='cosine' (the default) and a
+    ``MeasureShardedGallery`` under one of evaluation.py's non-cosine measures (ValueError on an unknown one); each
+    family's docstring names the arguments it reads, and it ignores the others.  A family built directly takes its own
+    measures only, and code that overrides the shard-local arithmetic subclasses a family, not this base: ValueError.
 
     ``comm``: a communicator (default: TorchComm over torch.distributed's process group).
-    ``measure``: 'cosine' (the default: packed rows, the fp16 MFMA rank GEMM) or one of evaluation.py's
-    non-cosine measures: the rows stay resident unnormalised in the measure's input dtype, every method keeps its
-    return types, ``mode`` arguments are ignored and top-k returns errors (ascending).
-    ``filter`` (euclidean / l2 / l2_norm; ValueError when True under any other measure): the route of the evaluation's
-    count pass over this shard -- False: the fp64 chain (K18); True: the fp16 MFMA filter (K21,
-    ``engine.pairwise_count(filter=True)``: the same words, an overflowing band list resolved on the device, so
-    nothing synchronises and no flag rides a collective); None: the filter from ``engine.L2_FILTER_MIN_PAIRS``
-    (captions x this shard's videos).  ``band_cap``: the slots of the shard's first band list (default
-    ``engine.l2_band_cap`` of the first filtered pass); the methods that end on the host grow it, or switch this
-    shard's later passes to the fp64 route, from the counters (``filter_stats``)."""
+    ``filter=True`` needs a Euclidean measure: ValueError under any other, cosine included."""
+
+    def __new__(cls, *args, **kw):
+        if cls is ShardedGallery:  # measure: __init__'s 10th argument
+            cls = _family(kw.get('measure', args[9] if len(args) > 9 else 'cosine'))
+        return object.__new__(cls)
 
     def __init__(self, local_embs, offset: int, n_global: int, with_lo: bool = False, eps: float = 0.0,
                  device: Optional[torch.device] = None, with_f16: bool = True, comm=None, cap: int = 1 << 22,
                  measure: str = 'cosine', filter: Optional[bool] = None, band_cap: Optional[int] = None):
         if filter and measure not in _L2_MEASURES:
             raise ValueError(f"ShardedGallery: filter=True needs a Euclidean measure {_L2_MEASURES}, not {measure!r}")
-        self._pw_filter = filter
-        self._pw_band_cap = band_cap
-        self._pw_stats = None
+        if not isinstance(self, _family(measure)):  # a family built directly, or a subclass of this base alone
+            raise ValueError(f"ShardedGallery: measure {measure!r} needs a {_family(measure).__name__}, "
+                             f"not a {type(self).__name__}")
         self.comm = _comm(comm)
         self.rank, self.world = self.comm.rank, self.comm.world
         self.offset = int(offset)
         self.n_global = int(n_global)
         self.measure = measure
-        if measure == 'cosine':
-            self._setup(local_embs, with_lo, eps, device, with_f16, cap)
+        # the family's own state: shard, device, n and what its route needs
+        self._init_shard(local_embs, device, with_lo=with_lo, eps=eps, with_f16=with_f16, cap=cap, filter=filter,
+                         band_cap=band_cap)
+
+    @property
+    def filter_stats(self):
+        """The counters of the last pass's filtered count over this shard, or None: that pass ran no filter."""
+        return None
+
+    def local_v2t_lists(self, v2t_gts_global):
+        return [list(v2t_gts_global[self.offset + j]) for j in range(self.n)]
+
+    # ---- collectives ----
+    def all_gather_rows(self, x_local: torch.Tensor) -> torch.Tensor:
+        return all_gather_rows(x_local, self.comm)
+
+    def gather_rows_async(self, x_local: torch.Tensor, out: torch.Tensor):
+        """gather_rows_async for this shard's communicator.  Issue it BEFORE enqueueing the compute that
+        should overlap it -- the collective first waits for the work already on the current stream --
+        and call .wait() on the returned Work before reading `out`."""
+        return gather_rows_async(x_local, out, self.comm)
+
+    def _check_layout(self):
+        """Gathers in rank order must reproduce the global video order: shard r = [offset_r, offset_r + n_r),
+        contiguous and increasing with r."""
+        if self.world == 1:
+            if self.offset != 0 or self.n != self.n_global:
+                raise ValueError("ShardedGallery: a world-1 shard must hold the whole gallery")
+            return
+        t = torch.tensor([[self.offset, self.n]], dtype=torch.int64, device=self.device)
+        lay = all_gather_rows(t, self.comm).cpu().numpy()
+        ends = lay[:, 0] + lay[:, 1]
+        if lay[0, 0] != 0 or ends[-1] != self.n_global or not np.array_equal(lay[1:, 0], ends[:-1]):
+            raise ValueError(f"ShardedGallery: shards are not contiguous in rank order: {lay.tolist()}")
+
+    # ---- the endings both families share ----
+    def _ranks_to_host(self, t2v, v2t, *more):
+        """The evaluation's ending on the host: this shard's v2t ranks become those of ALL videos (the layout is
+        checked, then one gather in rank order), and every device result an int64 host array (None stays None)."""
+        if v2t is not None:
+            self._check_layout()
+            v2t = all_gather_var(v2t, self.comm)
+        return tuple(None if x is None else x.cpu().numpy().astype(np.int64) for x in (t2v, v2t) + more)
+
+    def _perf_lists(self, n_q: int, v2t_gt, t2v_gt):
+        """cal_perf's (v2t, t2v) GT lists in global video / caption order."""
+        t2v_lists = [t2v_gt[i] for i in range(n_q)]  # KeyError on a caption without GT, like metrics.py:142
+        return [v2t_gt[j] for j in range(self.n_global)], t2v_lists
+
+    def _perf(self, t2v, v2t, t2v_map: float, aps):
+        """cal_perf's two 6-tuples from the global ranks, the t2v mAP and this shard's videos' v2t APs."""
+        s = torch.tensor([float(np.sum(aps))], dtype=torch.float64, device=self.device)
+        v2t_map = float(reduce_counts(s, self.comm).item()) / self.n_global
+        return (tuple(metrics_from_ranks(v2t)) + (v2t_map,), tuple(metrics_from_ranks(t2v)) + (t2v_map,))
+
+    def _merge_local_topk(self, local, n_q: int, k: int, to_host: bool):
+        """merge_topk of every shard's contribution of k columns.  local: this shard's (local ids int64, scores)
+        [n_q, <= k] on the device, best first, or None when it has nothing to offer: k empty slots."""
+        if local is None:
+            idx = torch.full((n_q, k), -1, dtype=torch.int64, device=self.device)
+            sc = torch.full((n_q, k), float("nan"), dtype=torch.float64, device=self.device)
         else:
-            self._pw_setup(local_embs, device)
+            idx, sc = local
+            idx = torch.where(idx >= 0, idx + self.offset, idx)
+            idx, sc = pad_topk(idx, sc, k)  # (shards may hold fewer than k rows)
+        return merge_topk(idx, sc, k, self.comm, to_host=to_host)
+
+
+class CosineShardedGallery(ShardedGallery):
+    """The shard under measure='cosine': rows packed once (``shard``: a RowSet), ranked by the fp16 MFMA rank GEMM
+    with its fp64 fix-up.  ``with_lo`` / ``with_f16`` / ``eps``: the pack's; ``cap``: the slots of the undecided-pair
+    list (``ws``), grown by the methods that end on the host when a pass overflows it.  ``mode``: a SIM_* scoring
+    mode.  Top-k returns cosines (descending)."""
+
+    def _init_shard(self, local_embs, device, with_lo, eps, with_f16, cap, **_):
+        self._setup(local_embs, with_lo, eps, device, with_f16, cap)
 
     def _setup(self, local_embs, with_lo, eps, device, with_f16, cap):
         self.shard = engine.RowSet(local_embs, eps=eps, with_lo=with_lo, device=device, with_f16=with_f16)
@@ -557,10 +635,157 @@ class ShardedGallery:
         """1-based positions of every GT caption of every shard video among all captions (v2t mAP)."""
         return engine.gt_positions_fused(self.shard, q, lists, mode=mode)
 
-    # ---- a non-cosine measure: shard-local arithmetic (HIP kernels: K18's launches, csrc/pairwise_rank.hip) ----
-    def _pw_setup(self, local_embs, device):
+    # ---- GT lists restricted to this shard ----
+    def local_gt_csr(self, gts_global: Sequence[Sequence[int]]):
+        """t2v: every caption's GT videos inside this shard, re-indexed locally."""
+        return self._csr(local_gt_lists(gts_global, self.offset, self.offset + self.n))
+
+    def local_v2t_csr(self, v2t_gts_global: Sequence[Sequence[int]]):
+        """v2t: the GT captions (gathered order) of this shard's videos."""
+        return self._csr(self.local_v2t_lists(v2t_gts_global))
+
+    # ---- t2v only (the gallery_shard bench leg) ----
+    def rank_queries(self, q_local: torch.Tensor, gt_csr, n_q: int, mode: int = _lib.SIM_F16, events=None,
+                     return_host: bool = True, chunks: int = 1):
+        """Global 1-based GT ranks of all gathered queries (t2v direction).
+
+        q_local: this rank's [n_local, D] query embeddings (equal n_local on every rank);
+        gt_csr: (off, idx) from ``local_gt_csr`` for the GATHERED query order.  The overflow flag of
+        the undecided-pair list rides the counts' all-reduce, so every rank sees the same flag: all of
+        them grow their lists and redo the batch together (a rank that trusted its own flag alone would
+        return incomplete counts while another waited in the next all-gather)."""
+        q_all = self.all_gather_rows(q_local)
+        for _attempt in range(4):
+            ranks, ovf = self.rank_queries_device(q_all, gt_csr, n_q, mode, events, chunks)
+            if not bool(ovf.item()):
+                break
+            self._grow()  # every rank: the flag is the all-reduced one
+        else:
+            raise _lib.CmveError("ShardedGallery.rank_queries: undecided-pair list kept overflowing")
+        if not return_host:
+            return ranks
+        return ranks.cpu().numpy().astype(np.int64)
+
+    def rank_queries_device(self, q_all: torch.Tensor, gt_csr, n_q: int, mode: int = _lib.SIM_F16, events=None,
+                            chunks: int = 1):
+        """rank_queries on already-gathered queries with no host synchronisation: returns
+        (ranks int64 [n_q] on the device, overflow flag bool [] on the device).  A set flag means the
+        undecided-pair list overflowed and the counts are incomplete: grow the workspace and redo."""
+        q = self._pack(q_all, mode)
+        sgt = merge_gt_scores(self._row_gt(q, gt_csr, mode), self.comm)
+        cnt, _, ovf = self._count(q, mode, sgt, None, events=events, chunks=chunks)
+        if self.world > 1:  # the overflow flag rides the counts' all-reduce(SUM): one collective, all ranks agree
+            both = reduce_counts(torch.cat([cnt, ovf.to(cnt.dtype).reshape(1)]), self.comm)
+            cnt, ovf = both[:-1], both[-1] > 0
+        return self._ranks(cnt, sgt, n_q, self.n_global), ovf
+
+    # ---- both directions (cal_perf) ----
+    def evaluate_device(self, q_all: torch.Tensor, row_csr, col_csr, n_q: int, mode: int = _lib.SIM_F16,
+                        events=None, q=None):
+        """One exact two-direction evaluation of the gathered captions against every shard, no host
+        synchronisation.  row_csr: t2v GT lists restricted to this shard (``local_gt_csr``) or None;
+        col_csr: this shard's v2t GT lists into the gathered captions (``local_v2t_csr``) or None.
+        Returns (t2v ranks int64 [n_q] | None -- global, equal on every rank; v2t ranks int64 [n] | None
+        -- this shard's videos; v2t recall sums int64 [4] | None -- all shards; overflow bool []).  q: the
+        captions already packed (``_pack(q_all, mode)``), reused across passes over the same captions."""
+        if q is None:
+            q = self._pack(q_all, mode)
+        sgt_r = merge_gt_scores(self._row_gt(q, row_csr, mode), self.comm) if row_csr is not None else None
+        col = self._col_gt(q, col_csr, mode) if (col_csr is not None and self.n > 0) else None
+        rc, cc, ovf = self._count(q, mode, sgt_r, col, events=events)
+        v2t = self._ranks(cc, col[0], self.n, n_q) if col is not None else None
+        if col_csr is not None and self.n == 0:  # an empty shard (shard_bounds' last rank): no videos to rank
+            v2t = torch.zeros(0, dtype=torch.int64, device=ovf.device)
+        parts = []
+        if rc is not None:
+            parts.append(rc[:n_q].to(torch.int64))
+        v2t_rec = recall_counts_device(v2t) if v2t is not None else torch.zeros(4, dtype=torch.int64,
+                                                                                   device=ovf.device)
+        parts += [v2t_rec, ovf.to(torch.int64).reshape(1)]
+        # ONE all-reduce(SUM): the t2v counts, the v2t R@K sums and the overflow flag
+        both = reduce_counts(torch.cat(parts), self.comm)
+        ovf = both[-1] > 0
+        rec = both[-5:-1] if col_csr is not None else None
+        t2v = self._ranks(both[:n_q].to(torch.int32), sgt_r, n_q, self.n_global) if row_csr is not None else None
+        return t2v, v2t, rec, ovf
+
+    def evaluate(self, q_local: torch.Tensor, t2v_gts=None, v2t_gts=None, mode: int = _lib.SIM_F16):
+        """Exact global ranks of both directions, on every rank (host int64 arrays): captions = the
+        rank-ordered gather of every rank's q_local (row counts may differ); t2v_gts[i] = GT video ids
+        (global) of gathered caption i; v2t_gts[v] = GT caption ids (gathered order) of global video v.
+        Returns (t2v ranks [n_q] | None, v2t ranks [n_global] | None)."""
+        q_all = all_gather_var(q_local, self.comm)
+        return self._evaluate_gathered(q_all, self._pack(q_all, mode), t2v_gts, v2t_gts, mode)
+
+    def _evaluate_gathered(self, q_all, q, t2v_gts, v2t_gts, mode: int):
+        """evaluate() on captions already gathered (q_all) and packed (q)."""
+        n_q = q_all.shape[0]
+        row_csr = self.local_gt_csr(t2v_gts) if t2v_gts is not None else None
+        col_csr = self.local_v2t_csr(v2t_gts) if v2t_gts is not None else None
+        for _attempt in range(4):
+            t2v, v2t, _, ovf = self.evaluate_device(q_all, row_csr, col_csr, n_q, mode, q=q)
+            if not bool(ovf.item()):
+                break
+            self._grow()
+        else:
+            raise _lib.CmveError("ShardedGallery.evaluate: undecided-pair list kept overflowing")
+        return self._ranks_to_host(t2v, v2t)
+
+    def cal_perf(self, q_local: torch.Tensor, v2t_gt, t2v_gt, mode: int = _lib.SIM_F16):
+        """``LINAS-engine/validate.py:15-54`` cal_perf over the sharded gallery: the reference's two
+        6-tuples (v2t (r1, r5, r10, medr, meanr, mAP), t2v (...)) on every rank.  v2t_gt: list over the
+        n_global videos of GT caption ids (gathered order); t2v_gt: dict or list over the captions of GT
+        video ids (metrics.get_gt's outputs).  t2v mAP is the AP of each caption's FIRST GT
+        (metrics.py:61-79); v2t mAP is over every GT caption of a video (metrics.py:83-102)."""
+        # the captions are gathered and packed ONCE; every pass below (both directions, the first-GT t2v pass, the
+        # v2t GT positions) reuses them
+        q_all = all_gather_var(q_local, self.comm)
+        q = self._pack(q_all, mode)
+        v2t_lists, t2v_lists = self._perf_lists(q_all.shape[0], v2t_gt, t2v_gt)
+        t2v, v2t = self._evaluate_gathered(q_all, q, t2v_lists, v2t_lists, mode)
+        if all(len(l) == 1 for l in t2v_lists):
+            t2v_first = t2v
+        else:
+            t2v_first, _ = self._evaluate_gathered(q_all, q, [[l[0]] for l in t2v_lists], None, mode)
+        local = self.local_v2t_lists(v2t_lists)
+        if all(len(l) <= 1 for l in v2t_lists):
+            aps = [1.0 / v2t[self.offset + j] if local[j] else 0.0 for j in range(self.n)]
+        else:
+            aps = [ap_from_positions(p) for p in self._positions(q, local, mode)]
+        return self._perf(t2v, v2t, float(np.mean(1.0 / t2v_first)), aps)
+
+    def topk(self, q_local: torch.Tensor, k: int, mode: int = _lib.SIM_F16):
+        """Global exact top-k (global ids int64, fp64 cosines; host arrays) of all gathered queries (equal row
+        counts on every rank), ordered (cosine desc, global id asc)."""
+        q_all = self.all_gather_rows(q_local)
+        q = engine.RowSet(q_all, with_lo=self.shard.has_lo, with_f16=self.shard.has_f16, device=self.device)
+        kk = min(k, self.n)
+        local = None  # an empty shard (shard_bounds' last rank)
+        if kk >= 1:
+            idx, sc = engine.topk(q, self.shard, kk, mode=mode, to_host=False)
+            local = idx.to(torch.int64), sc
+        return self._merge_local_topk(local, q.n, k, to_host=True)
+
+
+class MeasureShardedGallery(ShardedGallery):
+    """The shard under euclidean / l1 / l2 / l1_norm / l2_norm / jaccard: the rows stay resident unnormalised in the
+    measure's input dtype (``shard``: a Tensor) and K18's launches (csrc/pairwise_rank.hip) do the arithmetic.  The
+    methods have the cosine family's signatures and return types; their ``mode`` / ``events`` / ``chunks`` are unused,
+    no pass can overflow (the flags they return are never set) and top-k returns errors (ascending).
+    ``filter`` (euclidean / l2 / l2_norm): the route of the evaluation's count pass over this shard -- False: the
+    fp64 chain (K18); True: the fp16 MFMA filter (K21, ``engine.pairwise_count(filter=True)``: the same words, an
+    overflowing band list resolved on the device, so nothing synchronises and no flag rides a collective); None: the
+    filter from ``engine.L2_FILTER_MIN_PAIRS`` (captions x this shard's videos).  ``band_cap``: the slots of the
+    shard's first band list (default ``engine.l2_band_cap`` of the first filtered pass); the methods that end on the
+    host grow it, or switch this shard's later passes to the fp64 route, from the counters (``filter_stats``)."""
+
+    # ---- shard-local arithmetic (HIP kernels) ----
+    def _init_shard(self, local_embs, device, filter, band_cap, **_):
         from .linas.evaluation import measure_spec
         measure_spec(self.measure, 1)  # ValueError on an unknown measure
+        self._pw_filter = filter
+        self._pw_band_cap = band_cap
+        self._pw_stats = None
         self._pw_device = device
         self.shard = self._pw_rows(local_embs)  # resident, unnormalised, in the measure's input dtype
         self.device = self.shard.device
@@ -651,7 +876,7 @@ class ShardedGallery:
         self._pw_filter_off = st is not None and st["fallback"]
         return idx, err
 
-    # ---- a non-cosine measure: coordination (every communicator) ----
+    # ---- coordination (every communicator) ----
     def _pw_csr(self, lists, n_other: Optional[int], what: str):
         """(off, idx, items, end) of GT lists with GLOBAL ids, end = the largest id + 1 (a host int: _pw_pass checks
         it where the other side's size is known).  An id outside [0, n_other) has no owner: ValueError."""
@@ -709,158 +934,51 @@ class ShardedGallery:
         row = self._pw_csr(t2v_gts, self.n_global, "GT video") if t2v_gts is not None else None
         col = self._pw_csr(self.local_v2t_lists(v2t_gts), n_q, "GT caption") if v2t_gts is not None else None
         t2v, t2v_pos, v2t, v2t_pos, _ = self._pw_pass(q, n_q, row, col)
-        if v2t is not None:
-            self._check_layout()
-            v2t = all_gather_var(v2t, self.comm).cpu().numpy().astype(np.int64)
-            v2t_pos = v2t_pos.cpu().numpy().astype(np.int64)
-        if t2v is not None:
-            t2v, t2v_pos = t2v.cpu().numpy().astype(np.int64), t2v_pos.cpu().numpy().astype(np.int64)
+        t2v, v2t, t2v_pos, v2t_pos = self._ranks_to_host(t2v, v2t, t2v_pos, v2t_pos)
         self._pw_plan()  # (after the result copies: the stream has drained)
         return t2v, t2v_pos, v2t, v2t_pos
 
-    def _pw_cal_perf(self, q_local, v2t_gt, t2v_gt):
-        q_all = all_gather_var(q_local, self.comm)
-        n_q = q_all.shape[0]
-        t2v_lists = [t2v_gt[i] for i in range(n_q)]  # KeyError on a caption without GT, like metrics.py:142
-        v2t_lists = [v2t_gt[j] for j in range(self.n_global)]
-        t2v, t2v_pos, v2t, v2t_pos = self._pw_evaluate_gathered(self._pw_rows(q_all), n_q, t2v_lists, v2t_lists)
-        # both mAPs from the positions of that one pass: the first GT's position is among every item's
-        firsts = np.cumsum([0] + [len(l) for l in t2v_lists])[:-1]
-        t2v_map = float(np.mean([1.0 / (t2v_pos[f] + 1) if l else 0.0 for f, l in zip(firsts, t2v_lists)]))
-        offs = np.cumsum([0] + [len(l) for l in self.local_v2t_lists(v2t_lists)])
-        aps = [ap_from_positions(v2t_pos[offs[j]:offs[j + 1]] + 1) for j in range(self.n)]
-        s = torch.tensor([float(np.sum(aps))], dtype=torch.float64, device=self.device)
-        v2t_map = float(reduce_counts(s, self.comm).item()) / self.n_global
-        return (tuple(metrics_from_ranks(v2t)) + (v2t_map,), tuple(metrics_from_ranks(t2v)) + (t2v_map,))
-
-    def _pw_topk_merged(self, q_local, k: int):
-        q = self._pw_rows(all_gather_var(q_local, self.comm))  # a single caption may sit on one rank alone
-        k = int(min(k, self.n_global))  # as cmve_pairwise_topk clamps k to the gallery
-        if k < 1:
-            return np.zeros((q.shape[0], 0), np.int64), np.zeros((q.shape[0], 0))
-        if k > _lib.TOPK_MAX:
-            raise ValueError(f"ShardedGallery.topk: k <= {_lib.TOPK_MAX}")
-        if self.n < 1:  # an empty shard: k empty slots
-            idx = torch.full((q.shape[0], k), -1, dtype=torch.int64, device=self.device)
-            sc = torch.full((q.shape[0], k), float("nan"), dtype=torch.float64, device=self.device)
-        else:
-            idx, err = self._pw_topk(q, min(k, self.n))
-            idx = torch.where(idx >= 0, idx + self.offset, idx)
-            idx, sc = pad_topk(idx, -err, k)  # the merge orders by score descending: score = -error
-        ids, sc = merge_topk(idx, sc, k, self.comm, to_host=False)
-        return ids.cpu().numpy(), (-sc).cpu().numpy()
-
-    # ---- GT lists restricted to this shard ----
+    # ---- GT lists: global ids ----
     def local_gt_csr(self, gts_global: Sequence[Sequence[int]]):
-        """t2v: every caption's GT videos inside this shard, re-indexed locally.  Under a non-cosine measure:
-        (off, idx, items, end) of ALL of them with global ids -- the same on every rank (the items are scored where
-        they live)."""
-        if self.measure != 'cosine':
-            return self._pw_csr(gts_global, self.n_global, "GT video")
-        return self._csr(local_gt_lists(gts_global, self.offset, self.offset + self.n))
+        """t2v: (off, idx, items, end) of every caption's GT videos with GLOBAL ids -- the same on every rank (the
+        items are scored where they live)."""
+        return self._pw_csr(gts_global, self.n_global, "GT video")
 
     def local_v2t_csr(self, v2t_gts_global: Sequence[Sequence[int]]):
-        """v2t: the GT captions (gathered order) of this shard's videos (a measure: (off, idx, items, end); the
-        caption ids are checked against n_q where it is known, in the evaluation)."""
-        if self.measure != 'cosine':
-            return self._pw_csr(self.local_v2t_lists(v2t_gts_global), None, "GT caption")
-        return self._csr(self.local_v2t_lists(v2t_gts_global))
+        """v2t: (off, idx, items, end) of the GT captions (gathered order) of this shard's videos; the caption ids
+        are checked against n_q where it is known, in the evaluation."""
+        return self._pw_csr(self.local_v2t_lists(v2t_gts_global), None, "GT caption")
 
-    def local_v2t_lists(self, v2t_gts_global):
-        return [list(v2t_gts_global[self.offset + j]) for j in range(self.n)]
-
-    # ---- collectives ----
-    def all_gather_rows(self, x_local: torch.Tensor) -> torch.Tensor:
-        return all_gather_rows(x_local, self.comm)
-
-    def gather_rows_async(self, x_local: torch.Tensor, out: torch.Tensor):
-        """gather_rows_async for this shard's communicator.  Issue it BEFORE enqueueing the compute that
-        should overlap it -- the collective first waits for the work already on the current stream --
-        and call .wait() on the returned Work before reading `out`."""
-        return gather_rows_async(x_local, out, self.comm)
-
-    # ---- t2v only (the gallery_shard bench leg) ----
+    # ---- t2v only ----
     def rank_queries(self, q_local: torch.Tensor, gt_csr, n_q: int, mode: int = _lib.SIM_F16, events=None,
                      return_host: bool = True, chunks: int = 1):
-        """Global 1-based GT ranks of all gathered queries (t2v direction).
-
-        q_local: this rank's [n_local, D] query embeddings (equal n_local on every rank);
-        gt_csr: (off, idx) from ``local_gt_csr`` for the GATHERED query order.  The overflow flag of
-        the undecided-pair list rides the counts' all-reduce, so every rank sees the same flag: all of
-        them grow their lists and redo the batch together (a rank that trusted its own flag alone would
-        return incomplete counts while another waited in the next all-gather).  Under a non-cosine measure
-        gt_csr is ``local_gt_csr``'s global-id lists and nothing can overflow."""
-        q_all = self.all_gather_rows(q_local)
-        if self.measure != 'cosine':
-            ranks, _ = self.rank_queries_device(q_all, gt_csr, n_q)
-            if not return_host:
-                return ranks
-            ranks = ranks.cpu().numpy().astype(np.int64)
-            self._pw_plan()
-            return ranks
-        for _attempt in range(4):
-            ranks, ovf = self.rank_queries_device(q_all, gt_csr, n_q, mode, events, chunks)
-            if not bool(ovf.item()):
-                break
-            self._grow()  # every rank: the flag is the all-reduced one
-        else:
-            raise _lib.CmveError("ShardedGallery.rank_queries: undecided-pair list kept overflowing")
+        """Global 1-based GT ranks of all gathered queries (t2v direction).  q_local: this rank's [n_local, D]
+        query embeddings (equal n_local on every rank); gt_csr: ``local_gt_csr``'s tuple for the GATHERED order."""
+        ranks, _ = self.rank_queries_device(self.all_gather_rows(q_local), gt_csr, n_q)
         if not return_host:
             return ranks
-        return ranks.cpu().numpy().astype(np.int64)
+        ranks = ranks.cpu().numpy().astype(np.int64)
+        self._pw_plan()
+        return ranks
 
     def rank_queries_device(self, q_all: torch.Tensor, gt_csr, n_q: int, mode: int = _lib.SIM_F16, events=None,
                             chunks: int = 1):
-        """rank_queries on already-gathered queries with no host synchronisation: returns
-        (ranks int64 [n_q] on the device, overflow flag bool [] on the device).  A set flag means the
-        undecided-pair list overflowed and the counts are incomplete: grow the workspace and redo (never set
-        under a non-cosine measure)."""
-        if self.measure != 'cosine':
-            t2v = self._pw_pass(self._pw_rows(q_all), n_q, gt_csr, None)[0]
-            return t2v, torch.zeros((), dtype=torch.bool, device=self.device)
-        q = self._pack(q_all, mode)
-        sgt = merge_gt_scores(self._row_gt(q, gt_csr, mode), self.comm)
-        cnt, _, ovf = self._count(q, mode, sgt, None, events=events, chunks=chunks)
-        if self.world > 1:  # the overflow flag rides the counts' all-reduce(SUM): one collective, all ranks agree
-            both = reduce_counts(torch.cat([cnt, ovf.to(cnt.dtype).reshape(1)]), self.comm)
-            cnt, ovf = both[:-1], both[-1] > 0
-        return self._ranks(cnt, sgt, n_q, self.n_global), ovf
+        """rank_queries on already-gathered queries with no host synchronisation: (ranks int64 [n_q] on the
+        device, an overflow flag bool [] that is never set)."""
+        t2v = self._pw_pass(self._pw_rows(q_all), n_q, gt_csr, None)[0]
+        return t2v, torch.zeros((), dtype=torch.bool, device=self.device)
 
     # ---- both directions (cal_perf) ----
     def evaluate_device(self, q_all: torch.Tensor, row_csr, col_csr, n_q: int, mode: int = _lib.SIM_F16,
                         events=None, q=None):
         """One exact two-direction evaluation of the gathered captions against every shard, no host
-        synchronisation.  row_csr: t2v GT lists restricted to this shard (``local_gt_csr``) or None;
-        col_csr: this shard's v2t GT lists into the gathered captions (``local_v2t_csr``) or None.
-        Returns (t2v ranks int64 [n_q] | None -- global, equal on every rank; v2t ranks int64 [n] | None
-        -- this shard's videos; v2t recall sums int64 [4] | None -- all shards; overflow bool []).  q: the
-        captions already packed (``_pack(q_all, mode)``), reused across passes over the same captions.
-        Under a non-cosine measure row_csr / col_csr are ``local_gt_csr``'s / ``local_v2t_csr``'s tuples (a GT
-        video id outside the gallery or a GT caption id outside [0, n_q) raises ValueError),
-        q the captions' rows (``_pw_rows``), and the flag is never set."""
-        if self.measure != 'cosine':
-            t2v, _, v2t, _, rec = self._pw_pass(self._pw_rows(q_all) if q is None else q, n_q, row_csr, col_csr)
-            return t2v, v2t, rec, torch.zeros((), dtype=torch.bool, device=self.device)
-        if q is None:
-            q = self._pack(q_all, mode)
-        sgt_r = merge_gt_scores(self._row_gt(q, row_csr, mode), self.comm) if row_csr is not None else None
-        col = self._col_gt(q, col_csr, mode) if (col_csr is not None and self.n > 0) else None
-        rc, cc, ovf = self._count(q, mode, sgt_r, col, events=events)
-        v2t = self._ranks(cc, col[0], self.n, n_q) if col is not None else None
-        if col_csr is not None and self.n == 0:  # an empty shard (shard_bounds' last rank): no videos to rank
-            v2t = torch.zeros(0, dtype=torch.int64, device=ovf.device)
-        parts = []
-        if rc is not None:
-            parts.append(rc[:n_q].to(torch.int64))
-        v2t_rec = recall_counts_device(v2t) if v2t is not None else torch.zeros(4, dtype=torch.int64,
-                                                                                   device=ovf.device)
-        parts += [v2t_rec, ovf.to(torch.int64).reshape(1)]
-        # ONE all-reduce(SUM): the t2v counts, the v2t R@K sums and the overflow flag
-        both = reduce_counts(torch.cat(parts), self.comm)
-        ovf = both[-1] > 0
-        rec = both[-5:-1] if col_csr is not None else None
-        t2v = self._ranks(both[:n_q].to(torch.int32), sgt_r, n_q, self.n_global) if row_csr is not None else None
-        return t2v, v2t, rec, ovf
+        synchronisation.  row_csr / col_csr: ``local_gt_csr``'s / ``local_v2t_csr``'s tuples or None (a GT video id
+        outside the gallery or a GT caption id outside [0, n_q) raises ValueError); q: the captions' rows
+        (``_pw_rows(q_all)``) when the caller holds them.  Returns (t2v ranks int64 [n_q] | None -- global, equal on
+        every rank; v2t ranks int64 [n] | None -- this shard's videos; v2t recall sums int64 [4] | None -- all
+        shards; an overflow flag bool [] that is never set)."""
+        t2v, _, v2t, _, rec = self._pw_pass(self._pw_rows(q_all) if q is None else q, n_q, row_csr, col_csr)
+        return t2v, v2t, rec, torch.zeros((), dtype=torch.bool, device=self.device)
 
     def evaluate(self, q_local: torch.Tensor, t2v_gts=None, v2t_gts=None, mode: int = _lib.SIM_F16):
         """Exact global ranks of both directions, on every rank (host int64 arrays): captions = the
@@ -868,90 +986,43 @@ class ShardedGallery:
         (global) of gathered caption i; v2t_gts[v] = GT caption ids (gathered order) of global video v.
         Returns (t2v ranks [n_q] | None, v2t ranks [n_global] | None)."""
         q_all = all_gather_var(q_local, self.comm)
-        if self.measure != 'cosine':
-            t2v, _, v2t, _ = self._pw_evaluate_gathered(self._pw_rows(q_all), q_all.shape[0], t2v_gts, v2t_gts)
-            return t2v, v2t
-        return self._evaluate_gathered(q_all, self._pack(q_all, mode), t2v_gts, v2t_gts, mode)
-
-    def _evaluate_gathered(self, q_all, q, t2v_gts, v2t_gts, mode: int):
-        """evaluate() on captions already gathered (q_all) and packed (q)."""
-        n_q = q_all.shape[0]
-        row_csr = self.local_gt_csr(t2v_gts) if t2v_gts is not None else None
-        col_csr = self.local_v2t_csr(v2t_gts) if v2t_gts is not None else None
-        for _attempt in range(4):
-            t2v, v2t, _, ovf = self.evaluate_device(q_all, row_csr, col_csr, n_q, mode, q=q)
-            if not bool(ovf.item()):
-                break
-            self._grow()
-        else:
-            raise _lib.CmveError("ShardedGallery.evaluate: undecided-pair list kept overflowing")
-        t2v_h = t2v.cpu().numpy().astype(np.int64) if t2v is not None else None
-        v2t_h = None
-        if v2t is not None:
-            self._check_layout()
-            v2t_h = all_gather_var(v2t, self.comm).cpu().numpy().astype(np.int64)
-        return t2v_h, v2t_h
-
-    def _check_layout(self):
-        """Gathers in rank order must reproduce the global video order: shard r = [offset_r, offset_r + n_r),
-        contiguous and increasing with r."""
-        if self.world == 1:
-            if self.offset != 0 or self.n != self.n_global:
-                raise ValueError("ShardedGallery: a world-1 shard must hold the whole gallery")
-            return
-        t = torch.tensor([[self.offset, self.n]], dtype=torch.int64, device=self.device)
-        lay = all_gather_rows(t, self.comm).cpu().numpy()
-        ends = lay[:, 0] + lay[:, 1]
-        if lay[0, 0] != 0 or ends[-1] != self.n_global or not np.array_equal(lay[1:, 0], ends[:-1]):
-            raise ValueError(f"ShardedGallery: shards are not contiguous in rank order: {lay.tolist()}")
+        t2v, _, v2t, _ = self._pw_evaluate_gathered(self._pw_rows(q_all), q_all.shape[0], t2v_gts, v2t_gts)
+        return t2v, v2t
 
     def cal_perf(self, q_local: torch.Tensor, v2t_gt, t2v_gt, mode: int = _lib.SIM_F16):
-        """``LINAS-engine/validate.py:15-54`` cal_perf over the sharded gallery: the reference's two
-        6-tuples (v2t (r1, r5, r10, medr, meanr, mAP), t2v (...)) on every rank.  v2t_gt: list over the
-        n_global videos of GT caption ids (gathered order); t2v_gt: dict or list over the captions of GT
-        video ids (metrics.get_gt's outputs).  t2v mAP is the AP of each caption's FIRST GT
-        (metrics.py:61-79); v2t mAP is over every GT caption of a video (metrics.py:83-102).  Under a
-        non-cosine measure ranks and both mAPs come from the positions of ONE pass, multi-GT lists included."""
-        if self.measure != 'cosine':
-            return self._pw_cal_perf(q_local, v2t_gt, t2v_gt)
-        # the captions are gathered and packed ONCE; every pass below (both directions, the first-GT t2v pass, the
-        # v2t GT positions) reuses them
+        """``LINAS-engine/validate.py:15-54`` cal_perf over the sharded gallery: the reference's two 6-tuples
+        (v2t (r1, r5, r10, medr, meanr, mAP), t2v (...)) on every rank, v2t_gt / t2v_gt as metrics.get_gt returns
+        them (gathered caption order).  Ranks and both mAPs (t2v: each caption's FIRST GT; v2t: every GT caption
+        of a video) come from the positions of ONE pass, multi-GT lists included."""
         q_all = all_gather_var(q_local, self.comm)
         n_q = q_all.shape[0]
-        q = self._pack(q_all, mode)
-        t2v_lists = [t2v_gt[i] for i in range(n_q)]  # KeyError on a caption without GT, like metrics.py:142
-        v2t_lists = [v2t_gt[j] for j in range(self.n_global)]
-        t2v, v2t = self._evaluate_gathered(q_all, q, t2v_lists, v2t_lists, mode)
-        firsts = [[l[0]] for l in t2v_lists]
-        if all(len(l) == 1 for l in t2v_lists):
-            t2v_first = t2v
-        else:
-            t2v_first, _ = self._evaluate_gathered(q_all, q, firsts, None, mode)
-        t2v_map = float(np.mean(1.0 / t2v_first))
-        local = self.local_v2t_lists(v2t_lists)
-        if all(len(l) <= 1 for l in v2t_lists):
-            aps = [1.0 / v2t[self.offset + j] if local[j] else 0.0 for j in range(self.n)]
-        else:
-            aps = [ap_from_positions(p) for p in self._positions(q, local, mode)]
-        s = torch.tensor([float(np.sum(aps))], dtype=torch.float64, device=self.device)
-        v2t_map = float(reduce_counts(s, self.comm).item()) / self.n_global
-        return (tuple(metrics_from_ranks(v2t)) + (v2t_map,), tuple(metrics_from_ranks(t2v)) + (t2v_map,))
+        v2t_lists, t2v_lists = self._perf_lists(n_q, v2t_gt, t2v_gt)
+        t2v, t2v_pos, v2t, v2t_pos = self._pw_evaluate_gathered(self._pw_rows(q_all), n_q, t2v_lists, v2t_lists)
+        # the first GT's position is among every item's
+        firsts = np.cumsum([0] + [len(l) for l in t2v_lists])[:-1]
+        t2v_map = float(np.mean([1.0 / (t2v_pos[f] + 1) if l else 0.0 for f, l in zip(firsts, t2v_lists)]))
+        offs = np.cumsum([0] + [len(l) for l in self.local_v2t_lists(v2t_lists)])
+        aps = [ap_from_positions(v2t_pos[offs[j]:offs[j + 1]] + 1) for j in range(self.n)]
+        return self._perf(t2v, v2t, t2v_map, aps)
 
     def topk(self, q_local: torch.Tensor, k: int, mode: int = _lib.SIM_F16):
-        """Global exact top-k (global ids, fp64 cosines) of all gathered queries.  Under a non-cosine measure:
-        (ids int64, ERRORS fp64) ordered (error asc, global id asc), NaN last, k clamped to the gallery -- the
-        order of cmve_pairwise_topk on the whole gallery (inference.py:78-80)."""
-        if self.measure != 'cosine':
-            return self._pw_topk_merged(q_local, k)
-        q_all = self.all_gather_rows(q_local)
-        q = engine.RowSet(q_all, with_lo=self.shard.has_lo, with_f16=self.shard.has_f16, device=self.device)
-        kk = min(k, self.shard.n)
-        if kk < 1:  # an empty shard (shard_bounds' last rank): contributes k empty slots
-            idx = torch.full((q.n, k), -1, dtype=torch.int64, device=self.device)
-            sc = torch.full((q.n, k), float("nan"), dtype=torch.float64, device=self.device)
-        else:
-            idx, sc = engine.topk(q, self.shard, kk, mode=mode, to_host=False)
-            idx = idx.to(torch.int64)
-            idx = torch.where(idx >= 0, idx + self.offset, idx)
-            idx, sc = pad_topk(idx, sc, k)  # every rank contributes k columns (shards may hold fewer rows)
-        return merge_topk(idx, sc, k, self.comm)
+        """Global exact top-k of all gathered queries (row counts may differ: a single caption may sit on one
+        rank alone): host (ids int64, ERRORS fp64) ordered (error asc, global id asc), NaN last, k clamped to the
+        gallery -- the order of cmve_pairwise_topk on the whole gallery (inference.py:78-80)."""
+        q = self._pw_rows(all_gather_var(q_local, self.comm))
+        k = int(min(k, self.n_global))  # as cmve_pairwise_topk clamps k to the gallery
+        if k < 1:
+            return np.zeros((q.shape[0], 0), np.int64), np.zeros((q.shape[0], 0))
+        if k > _lib.TOPK_MAX:
+            raise ValueError(f"ShardedGallery.topk: k <= {_lib.TOPK_MAX}")
+        local = None  # an empty shard
+        if self.n >= 1:
+            idx, err = self._pw_topk(q, min(k, self.n))
+            local = idx, -err  # the merge orders by score descending: score = -error
+        ids, sc = self._merge_local_topk(local, q.shape[0], k, to_host=False)
+        return ids.cpu().numpy(), (-sc).cpu().numpy()
+
+
+def _family(measure) -> type:
+    """The ONE dispatch on the measure: the class that ``ShardedGallery(..., measure=)`` builds."""
+    return CosineShardedGallery if measure == 'cosine' else MeasureShardedGallery

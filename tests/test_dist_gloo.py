@@ -31,7 +31,7 @@ def _free_port():
 def _oracle_shard_class():
     from cmve import dist as D
 
-    class OracleShard(D.ShardedGallery):
+    class OracleShard(D.CosineShardedGallery):
         """ShardedGallery whose shard-local arithmetic is the fp64 oracle (test infrastructure)."""
 
         def _setup(self, local_embs, with_lo, eps, device, with_f16, cap):

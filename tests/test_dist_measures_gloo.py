@@ -35,7 +35,7 @@ def _oracle_shard_class():
     from cmve import dist as D
     from oracle import measures as OM
 
-    class OracleShard(D.ShardedGallery):
+    class OracleShard(D.MeasureShardedGallery):
         """ShardedGallery(measure=) whose shard-local arithmetic is the oracle (test infrastructure)."""
         count_calls = 0
         craft = None     # {item: value}: row items whose score is replaced where this shard owns them

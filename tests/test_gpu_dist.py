@@ -106,6 +106,29 @@ def test_sharded_gallery_world1_methods(torch_cuda):
     assert np.isnan(o_s.cpu().numpy()[0, 5:]).all()
 
 
+def test_topk_with_an_empty_shard_equals_the_unsharded_words(torch_cuda):
+    """ShardedGallery.topk over two in-process shards of 5 and 0 rows, k = 7 beyond the gallery: ids and cosines are
+    engine.topk's on the whole gallery word for word, the slots past the five videos -1 / NaN, on both ranks."""
+    torch = torch_cuda
+    from cmve import engine, dist as D
+    rng = np.random.default_rng(8)
+    n_g, d, k = 5, 8, 7
+    gal = rng.standard_normal((n_g, d)).astype(np.float32)
+    qs = rng.standard_normal((6, d)).astype(np.float32)  # 3 queries on each rank
+    want_i, want_s = engine.topk(engine.RowSet(qs, with_lo=False), engine.RowSet(gal, with_lo=False), k)
+    assert want_i.shape == (6, n_g) and want_s.dtype == np.float64
+
+    def body(r, comm):
+        lo, hi = (0, n_g) if r == 0 else (n_g, n_g)
+        sh = D.ShardedGallery(gal[lo:hi], offset=lo, n_global=n_g, comm=comm)
+        return sh.topk(torch.from_numpy(qs[3 * r:3 * r + 3]).cuda(), k)
+
+    for ids, sc in D.LocalGroup(2).run(body):
+        assert ids.shape == sc.shape == (6, k) and ids.dtype == np.int64 and sc.dtype == np.float64
+        assert np.array_equal(ids[:, :n_g], want_i) and (ids[:, n_g:] == -1).all()
+        assert np.array_equal(sc[:, :n_g].view(np.int64), want_s.view(np.int64)) and np.isnan(sc[:, n_g:]).all()
+
+
 # ---- the two-direction sharded evaluation (cal_perf over N shards), LocalGroup: one thread + HIP stream per shard ----
 
 def test_local_group_evaluate_and_cal_perf_match_oracle(torch_cuda):

@@ -99,6 +99,69 @@ def test_sharded_filter_true_needs_a_euclidean_measure(m):
         ShardedGallery(np.zeros((4, 8), np.float32), offset=0, n_global=4, comm=NoComm(), measure=m, filter=True)
 
 
+@pytest.fixture
+def cpu_families(monkeypatch):
+    """cmve.dist with both families' device-side set-up replaced by CPU tensors (oracle-style, as the gloo tests)."""
+    import torch
+    from cmve import dist as D
+
+    def setup(self, local_embs, with_lo, eps, device, with_f16, cap):
+        self.shard, self.n, self.device = torch.as_tensor(local_embs), len(local_embs), torch.device("cpu")
+        self.eps, self.ws = eps, object()
+
+    monkeypatch.setattr(D.CosineShardedGallery, "_setup", setup)
+    monkeypatch.setattr(D.MeasureShardedGallery, "_pw_rows", lambda self, x: torch.as_tensor(x))
+    return D
+
+
+class _World1:
+    rank, world = 0, 1
+
+
+def test_the_one_constructor_builds_the_family_of_the_measure(cpu_families):
+    D = cpu_families
+    rows = np.zeros((4, 8), np.float32)
+    cos = D.ShardedGallery(rows, offset=0, n_global=4, comm=_World1())
+    assert type(cos) is D.CosineShardedGallery and isinstance(cos, D.ShardedGallery) and cos.measure == "cosine"
+    for m in ("euclidean", "l1", "l2", "l1_norm", "l2_norm", "jaccard"):
+        sh = D.ShardedGallery(rows, offset=0, n_global=4, comm=_World1(), measure=m)
+        assert type(sh) is D.MeasureShardedGallery and isinstance(sh, D.ShardedGallery) and sh.measure == m
+    # the measure given by position, as the signature allows
+    assert type(D.ShardedGallery(rows, 0, 4, False, 0.0, None, True, _World1(), 8, "l1")) is D.MeasureShardedGallery
+    with pytest.raises(ValueError, match="unknown measure"):
+        D.ShardedGallery(rows, offset=0, n_global=4, comm=_World1(), measure="chebyshev")
+
+    # a family named directly, or a subclass of one, is itself
+    class Mine(D.MeasureShardedGallery):
+        pass
+
+    assert type(D.CosineShardedGallery(rows, offset=0, n_global=4, comm=_World1())) is D.CosineShardedGallery
+    assert type(D.MeasureShardedGallery(rows, offset=0, n_global=4, comm=_World1(), measure="l2")) \
+        is D.MeasureShardedGallery
+    assert type(Mine(rows, offset=0, n_global=4, comm=_World1(), measure="jaccard")) is Mine
+
+    # ... for its own measures only; what overrides the arithmetic subclasses a family, not the base alone
+    class Bare(D.ShardedGallery):
+        pass
+
+    for cls, m in ((D.CosineShardedGallery, "l1"), (D.MeasureShardedGallery, "cosine"), (Mine, "cosine"),
+                   (Bare, "cosine"), (Bare, "l2")):
+        with pytest.raises(ValueError, match="needs a (Cosine|Measure)ShardedGallery"):
+            cls(rows, offset=0, n_global=4, comm=_World1(), measure=m)
+
+
+def test_each_family_holds_its_own_state_only(cpu_families):
+    D = cpu_families
+    rows = np.zeros((4, 8), np.float32)
+    cos = D.ShardedGallery(rows, offset=0, n_global=4, comm=_World1())
+    assert not [a for a in dir(cos) if a.startswith("_pw_")]
+    assert hasattr(cos, "ws") and cos.eps == 0.0 and cos.filter_stats is None
+    for m, f in (("l1", None), ("l2", None), ("l2", True), ("euclidean", False)):
+        sh = D.ShardedGallery(rows, offset=0, n_global=4, comm=_World1(), measure=m, filter=f)
+        assert not hasattr(sh, "ws") and not hasattr(sh, "eps") and sh.filter_stats is None
+        assert sh._pw_packed is None and sh._pw_band is None and sh._pw_filter_off is False and sh.n == 4
+
+
 def test_one_decoder_names_the_four_counters():
     from cmve import engine
     st = engine._l2_count_stats(np.array([7, 5, 3, 1], np.int64))
