@@ -881,19 +881,91 @@ def l2_topk(q: "RowSet", g: "RowSet", alpha: float, beta: float, k: int, cand_ca
     return idx, err, _stats4(("excluded", "candidates", "rescored", "unresolved"), st.cpu().numpy())
 
 
-def _topk_filtered(q, g, alpha, beta, k, cand_cap, sample_rows, ws=None):
-    """The K20 route of ``pairwise_topk``: (idx, err) on the device with the same words as the fp64 route, and the
-    ``topk_stats`` record; idx is None when the whole call has to take the fp64 route."""
-    rq = q if isinstance(q, RowSet) else RowSet(q, with_lo=False, device=g.device)
-    idx, err, stats = l2_topk(rq, g, alpha, beta, k, cand_cap, sample_rows, ws)
+L1_TOPK_CAND_MAX = L2_TOPK_CAND_MAX  # cmve_l1_topk's limit on cand_cap: the same last launch, the same LDS
+# Auto dispatch of the K23 filter (``filter=None``), a rule of its own beside K20's (None in a constant switches its
+# clause off: "never taken automatically", as K22 allowed for ``L1_FILTER_MIN_PAIRS``).  From tools/l1_topk_bench.py ->
+# profiles/l1_topk.json (top-10, D = 1024, fp64 rows, l1, medians of 5 alternating repeats, fp64 route / filter in ms;
+# "wins" = by more than the two spreads together; the constants were None while it ran).  Against a gallery that is
+# already packed (an L1Set: GalleryScorer, the sharded gallery) the filter won at 64 x 131,072 (1.91 / 1.19), 1000 x
+# 131,072 (18.0 / 4.17), 16,384 x 131,072 (327.1 / 64.7) and over 1,048,576 rows at every n_q: 1 (3.27 / 3.02,
+# spreads 0.08 + 0.05), 64 (11.85 / 3.85), 1000 (141.7 / 19.4); it lost at 1 x 131,072 (0.88 / 1.09: both are launch
+# gaps).  A packed gallery takes it from MIN_GALLERY rows or MIN_PAIRS pairs, the smallest sizes measured to win.  A
+# gallery given as plain rows pays the grid and both packs inside the call (0.78 ms at 131,072 rows, 4.8 ms at
+# 1,048,576): it won at 64 x 1,048,576 (11.72 / 8.63), 1000 x 131,072 (17.9 / 5.07), 1000 x 1,048,576 (141.5 / 24.5) and
+# 16,384 x 131,072 (326.0 / 65.6), tied at 64 x 131,072 (1.93 / 1.99) and lost at one query (3.26 / 7.76 over
+# 1,048,576): plain rows take it from MIN_Q queries AND MIN_PLAIN_PAIRS pairs.  Between the measured sizes the pair
+# rules are an interpolation.
+L1_TOPK_FILTER_MIN_GALLERY = 1 << 20      # packed: 1 x 1,048,576
+L1_TOPK_FILTER_MIN_PAIRS = 1 << 23        # packed: 64 x 131,072
+L1_TOPK_FILTER_MIN_Q = 64                 # plain rows
+L1_TOPK_FILTER_MIN_PLAIN_PAIRS = 1 << 26  # plain rows: 64 x 1,048,576
+
+
+def l1_topk_auto(n_q: int, n_g: int, packed: bool = False) -> bool:
+    """Whether ``pairwise_topk(filter=None)`` takes the K23 filter at this size (given PW_L1 with fp64 words);
+    ``packed``: the gallery is an L1Set already.  A constant left None switches its clause off."""
+    if n_q < 1 or n_g < 1:
+        return False
+    if packed:
+        return ((L1_TOPK_FILTER_MIN_GALLERY is not None and n_g >= L1_TOPK_FILTER_MIN_GALLERY)
+                or (L1_TOPK_FILTER_MIN_PAIRS is not None and n_q * n_g >= L1_TOPK_FILTER_MIN_PAIRS))
+    return (L1_TOPK_FILTER_MIN_Q is not None and L1_TOPK_FILTER_MIN_PLAIN_PAIRS is not None
+            and n_q >= L1_TOPK_FILTER_MIN_Q and n_q * n_g >= L1_TOPK_FILTER_MIN_PLAIN_PAIRS)
+
+
+def _n_rows(s) -> int:
+    return int(s.n) if hasattr(s, "n") else int(s)
+
+
+def l1_topk_workspace(q, g, k: int, cand_cap: Optional[int] = None, sample_rows: Optional[int] = None) -> int:
+    """Bytes of workspace ``cmve_l1_topk`` needs (host only: no launch).  q / g: an ``L1Set`` or a row count."""
+    n = C.c_int64()
+    check(lib.cmve_l1_topk_workspace(_n_rows(q), _n_rows(g), int(k),
+                                     L1_TOPK_CAND_MAX if cand_cap is None else int(cand_cap),
+                                     int(sample_rows or 0), C.byref(n)), "cmve_l1_topk_workspace")
+    return n.value
+
+
+def l1_topk(q: "L1Set", g: "L1Set", alpha: float, beta: float, k: int, cand_cap: Optional[int] = None,
+            sample_rows: Optional[int] = None, ws: Optional[torch.Tensor] = None):
+    """``cmve_l1_topk`` (K23): (idx int64 [n_q, k], err fp64 [n_q, k]) on the device and the stats dict
+    {excluded, candidates, rescored, unresolved} (one small copy to the host), as ``l2_topk``.  Both sets are packed
+    on ONE grid (ValueError otherwise).  An unresolved query has idx[i, 0] == -2 and the rest of its row unwritten.
+    k must not exceed the gallery.  ws: a caller-held device workspace, used when it holds ``l1_topk_workspace``
+    bytes (a fresh one otherwise)."""
+    q, g = _l1_sets(None, None, q, g)
+    if q.d != g.d:
+        raise ValueError(f"l1_topk: dimensions differ ({q.d}, {g.d})")
+    cap = L1_TOPK_CAND_MAX if cand_cap is None else int(cand_cap)
+    nbytes = l1_topk_workspace(q, g, k, cap, sample_rows)
+    dev = g.device
+    if ws is None or _nbytes(ws) < nbytes or ws.data_ptr() % 8:
+        ws = torch.empty(max(nbytes // 8, 1), dtype=torch.int64, device=dev)
+    idx = torch.empty((q.n, int(k)), dtype=torch.int64, device=dev)
+    err = torch.empty((q.n, int(k)), dtype=torch.float64, device=dev)
+    st = torch.empty(4, dtype=torch.int64, device=dev)
+    a, b = q.raw, g.raw
+    check(lib.cmve_l1_topk(handle(dev), _ptr(a), _dtype_code(a), _pw_ld(a), q.n, _ptr(q.codes), _ptr(q.err),
+                           _ptr(b), _dtype_code(b), _pw_ld(b), g.n, _ptr(g.codes), _ptr(g.err), g.d, _ptr(g.grid),
+                           float(alpha), float(beta), int(k), cap, int(sample_rows or 0), _ptr(ws), nbytes, _ptr(idx),
+                           _ptr(err), _ptr(st)), "cmve_l1_topk")
+    return idx, err, _stats4(("excluded", "candidates", "rescored", "unresolved"), st.cpu().numpy())
+
+
+def _topk_filtered(metric: int, filtered, q, g, alpha, beta, k):
+    """A filtered route of ``pairwise_topk`` (K20: ``metric`` PW_L2, K23: PW_L1): ``filtered()`` is the filter's call
+    and returns (idx, err, stats) as ``l2_topk`` / ``l1_topk`` do; q / g are the raw rows.  Returns (idx, err) on the
+    device with the same words as the fp64 route, and the ``topk_stats`` record; idx is None when the whole call has
+    to take the fp64 route."""
+    idx, err, stats = filtered()
+    n_q = q.shape[0]
     stats.update(fallback_rows=0, fallback=False)
     if stats["unresolved"]:
-        if stats["unresolved"] > L2_TOPK_MAX_UNRESOLVED * rq.n:
-            stats.update(fallback_rows=rq.n, fallback=True)
+        if stats["unresolved"] > L2_TOPK_MAX_UNRESOLVED * n_q:
+            stats.update(fallback_rows=n_q, fallback=True)
             return None, None, stats
         rows = (idx[:, 0] == -2).nonzero().flatten()
-        sub_i, sub_e = pairwise_topk(rq.raw[rows], g.raw, _lib.PW_L2, alpha, beta, torch.float64, k, to_host=False,
-                                     filter=False)
+        sub_i, sub_e = pairwise_topk(q[rows], g, metric, alpha, beta, torch.float64, k, to_host=False, filter=False)
         idx[rows], err[rows] = sub_i, sub_e
         stats["fallback_rows"] = int(rows.numel())
     return idx, err, stats
@@ -919,14 +991,23 @@ def pairwise_topk(q, g, metric: int, alpha: float, beta: float, score_dtype, k: 
     accelerator: queries it leaves unresolved are re-run on the fp64 route and scattered back, more than
     ``L2_TOPK_MAX_UNRESOLVED`` of them (and k > ``L2_TOPK_CAND_MAX``) send the whole call there.  ``cand_cap`` /
     ``sample_rows``: ``cmve_l2_topk``'s.  ``return_stats``: also return ``topk_stats`` -- {excluded, candidates,
-    rescored, unresolved, fallback_rows, fallback}, or None when the filter was not tried."""
+    rescored, unresolved, fallback_rows, fallback}, or None when the filter was not tried.
+
+    ``filter="l1"`` -- the K23 route for ``PW_L1`` with float64 score words (``cmve_l1_topk``: the integer SAD filter of
+    K22, canonical re-score of the candidates: the same words), ValueError unless the metric is ``PW_L1`` with
+    float64 score words, alpha finite and non-zero and beta finite; None also takes it when it applies and
+    ``l1_topk_auto`` says it pays (never while its ``L1_TOPK_FILTER_MIN_*`` are None).  g (and q) may then be an
+    ``L1Set``: a resident gallery is packed once on its own grid and the queries are packed on ``g.grid`` inside the
+    call; plain rows on both sides share a grid made from both; two ``L1Set`` on different grids are a ValueError.
+    Unresolved queries, the whole-call fallback, ``cand_cap`` / ``sample_rows`` and ``topk_stats``: as above."""
+    route = _filter_route("pairwise_topk", filter, metric, alpha, beta, score_dtype, False)
     g_set = g if isinstance(g, RowSet) else None
     q_set = q if isinstance(q, RowSet) else None
-    q, g = _pw_pair(q_set.raw if q_set is not None else q, g_set.raw if g_set is not None else g, "pairwise_topk")
+    g_l1 = g if isinstance(g, L1Set) else None
+    q_l1 = q if isinstance(q, L1Set) else None
+    q, g = _pw_pair(q.raw if isinstance(q, (RowSet, L1Set)) else q, g.raw if isinstance(g, (RowSet, L1Set)) else g,
+                    "pairwise_topk")
     n_q, n_g = q.shape[0], g.shape[0]
-    applies = _l2_applies(metric, score_dtype)
-    if filter and not applies:
-        raise ValueError("pairwise_topk: filter=True needs PW_L2 with float64 score words")
 
     def result(idx, err, stats):
         out = (idx.cpu().numpy(), err.cpu().numpy()) if to_host and torch.is_tensor(idx) else (idx, err)
@@ -937,15 +1018,30 @@ def pairwise_topk(q, g, metric: int, alpha: float, beta: float, score_dtype, k: 
         return result(np.zeros((n_q, 0), np.int64), np.zeros((n_q, 0)), None)
     if k > _lib.TOPK_MAX:
         raise ValueError(f"pairwise_topk: k <= {_lib.TOPK_MAX}")
-    if filter is None:  # auto never hands the entry what it refuses; filter=True does, and the entry says so
-        filter = (applies and l2_topk_auto(n_q, n_g, g_set is not None) and _l2_scaling_ok(alpha, beta)
-                  and _l2_set_ok(q_set) and _l2_set_ok(g_set))
+    if filter is None and _l2_scaling_ok(alpha, beta):
+        # auto never hands an entry what it refuses; a forced route does, and the entry says so
+        if _l2_applies(metric, score_dtype):
+            if l2_topk_auto(n_q, n_g, g_set is not None) and _l2_set_ok(q_set) and _l2_set_ok(g_set):
+                route = "l2"
+        elif _l1_applies(metric, score_dtype):
+            if l1_topk_auto(n_q, n_g, g_l1 is not None) and q.shape[1] <= L1_D_MAX:
+                route = "l1"
     topk_stats = None
-    if filter and n_q > 0 and k <= L2_TOPK_CAND_MAX:
-        if g_set is None:
-            g_set = RowSet(g, with_lo=False, device=g.device)
-        idx, err, topk_stats = _topk_filtered(q_set if q_set is not None else q, g_set, alpha, beta, k, cand_cap,
-                                              sample_rows, ws)
+    if route and n_q > 0 and k <= L2_TOPK_CAND_MAX:
+        if route == "l1":
+            if q_set is not None or g_set is not None:
+                raise TypeError('pairwise_topk: a RowSet is packed for the Euclidean filter; filter="l1" takes an L1Set')
+            q_l1, g_l1 = _l1_sets(q, g, q_l1, g_l1)
+            filtered = lambda: l1_topk(q_l1, g_l1, alpha, beta, k, cand_cap, sample_rows, ws)  # noqa: E731
+        else:
+            if q_l1 is not None or g_l1 is not None:
+                raise TypeError('pairwise_topk: an L1Set is packed for filter="l1"; the Euclidean filter takes a RowSet')
+            if g_set is None:
+                g_set = RowSet(g, with_lo=False, device=g.device)
+            if q_set is None:
+                q_set = RowSet(q, with_lo=False, device=g.device)
+            filtered = lambda: l2_topk(q_set, g_set, alpha, beta, k, cand_cap, sample_rows, ws)  # noqa: E731
+        idx, err, topk_stats = _topk_filtered(metric, filtered, q, g, alpha, beta, k)
         if idx is not None:
             return result(idx, err, topk_stats)
     lo, rec = pairwise_topk_workspace(n_q, n_g, k, metric)

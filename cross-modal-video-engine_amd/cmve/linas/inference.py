@@ -55,7 +55,15 @@ class GalleryScorer:
     gallery rows or ``engine.L2_TOPK_FILTER_MIN_PAIRS`` pairs per call (``engine.l2_topk_auto``); True / False force it / the fp64 route of K18 (False
     also skips the pack).  The pack's bf16 plane is not read by K20 (the pack kernel always writes it): half of the
     extra bytes serve the cosine kernels' layout only.  A call that falls back to the fp64 route as a whole turns the
-    automatic filter off for this scorer.  'l1', 'l1_norm' and 'jaccard' have no dot-product form and stay on K18."""
+    automatic filter off for this scorer.
+
+    Under 'l1' and 'l1_norm' the SAD-filtered top-k of K23 serves (``engine.pairwise_topk(filter="l1")``: the same ids,
+    the same words): ``filter="l1"`` forces it, None takes it when ``engine.l1_topk_auto(n_q, n_g, packed=True)``
+    says it pays, False is the fp64 route of K18 and skips the pack; ``filter=True`` speaks for the Euclidean
+    measures alone and is ignored here (no pack).  The gallery is then packed once as an ``engine.L1Set`` on its own
+    grid -- uint16 codes, 2 bytes per element beside the fp64 rows, plus 8 bytes per row; the rows are not copied --
+    and each call packs its queries on that grid.  One workspace stays resident, sized for the route taken, and a
+    call handed back whole turns the automatic filter off, as above.  'jaccard' has no such form and stays on K18."""
 
     def __init__(self, video_embs, video_ids=None, with_lo=True, measure='cosine', filter=None):
         self.measure = measure
@@ -70,6 +78,14 @@ class GalleryScorer:
             if measure in ('euclidean', 'l2', 'l2_norm') and filter is not False and self.gallery.shape[0]:
                 self._packed = engine.RowSet(self.gallery, eps=0.0, with_lo=False, device=self.gallery.device)
                 self.gallery = self._packed.raw  # the pack keeps the rows it was given: no second copy
+            # l1 / l1_norm (K23): packed when forced, or when the auto rule could take some call over this gallery
+            # (never while its constants are None); filter=True speaks for the Euclidean measures alone
+            n_g = self.gallery.shape[0]
+            if measure in ('l1', 'l1_norm') and n_g and 1 <= self.gallery.shape[1] <= engine.L1_D_MAX and (
+                    (isinstance(filter, str) and filter == "l1")
+                    or (filter is None and engine.l1_topk_auto(1 << 30, n_g, packed=True))):
+                self._packed = engine.L1Set(self.gallery)
+                self.gallery = self._packed.raw
             return
         emb = video_embs if hasattr(video_embs, "data_ptr") else np.asarray(video_embs)
         self.gallery = engine.RowSet(emb, eps=0.0, with_lo=with_lo)
@@ -116,12 +132,17 @@ class GalleryScorer:
         # the route this call will take, as engine.pairwise_topk decides it; a gallery whose calls fell back to the
         # fp64 route as a whole (rows clustered far from the origin) is not asked again under filter=None
         flt = False
+        l1 = isinstance(self._packed, engine.L1Set)
         if self._packed is not None and q.shape[0] and 1 <= k <= engine.L2_TOPK_CAND_MAX:
-            flt = self.filter is True or (self.filter is None and not self._filter_off
-                                          and engine.l2_topk_auto(q.shape[0], g.shape[0], packed=True))
+            forced = (isinstance(self.filter, str) and self.filter == "l1") if l1 else self.filter is True
+            auto = engine.l1_topk_auto if l1 else engine.l2_topk_auto
+            flt = forced or (self.filter is None and not self._filter_off
+                             and auto(q.shape[0], g.shape[0], packed=True))
         # ONE workspace stays resident between calls, sized for that route only and grown when a call needs more
         need = 0
-        if flt:
+        if flt and l1:
+            need = engine.l1_topk_workspace(q.shape[0], g.shape[0], k)  # (the queries are packed on the gallery's grid)
+        elif flt:
             q = engine.RowSet(q, eps=0.0, with_lo=False, device=g.device)
             need = engine.l2_topk_workspace(q, self._packed, k)
         elif 1 <= k <= engine._lib.TOPK_MAX:
@@ -129,7 +150,7 @@ class GalleryScorer:
         if need and (self._ws is None or self._ws.numel() < need):
             self._ws = torch.empty(need, dtype=torch.uint8, device=g.device)
         idx, _, st = engine.pairwise_topk(q, self._packed if flt else g, metric, alpha, beta, sc_dt, k, ws=self._ws,
-                                          filter=flt, return_stats=True)
+                                          filter=("l1" if l1 else True) if flt else False, return_stats=True)
         if st is not None and st["fallback"]:
             self._filter_off = True
         return idx

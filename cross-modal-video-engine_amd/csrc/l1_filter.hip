@@ -172,7 +172,9 @@ __global__ __launch_bounds__(256, 4) void l1f_main_kernel(L1fArgs a) {
   const int64_t i0 = (int64_t)ta * L1F_BM, j0 = (int64_t)tb_ * L1F_BN;
 
   // ---- the SADs: acc[u][v] of the pair (A row i0 + l1f_row(ty, u), B row j0 + l1f_row(tx, v)); the tiles' blocks lie
-  // below the sets' n_pad (a multiple of 128) and d_pad: in bounds
+  // below the sets' n_pad (a multiple of 128) and d_pad: in bounds.  l1t_pass_kernel (l1_topk.hip, K23) carries a COPY
+  // of this K loop, so that this kernel keeps the instruction stream it is tuned on: a change to either loop is made
+  // in both.
   uint32_t acc[8][8];
 #pragma unroll
   for (int u = 0; u < 8; ++u)
@@ -407,8 +409,6 @@ __global__ __launch_bounds__(256, 4) void l1f_main_kernel(L1fArgs a) {
     }
   }
 }
-
-bool l1f_dtype_ok(int32_t t) { return t == CMVE_F32 || t == CMVE_F64; }
 
 }  // namespace
 }  // namespace cmve

@@ -31,6 +31,9 @@ static inline void l1f_pads(int64_t n, int64_t d, int64_t& n_pad, int64_t& d_pad
   d_pad = (d + L1F_BK - 1) / L1F_BK * L1F_BK;
 }
 
+// the raw rows every L1 entry takes beside the codes
+static inline bool l1f_dtype_ok(int32_t t) { return t == CMVE_F32 || t == CMVE_F64; }
+
 // THE grid (lo, s) every kernel derives from the two device words {lo, hi}: min and max of the eligible elements.
 // No eligible element (the words are still +inf, -inf), hi == lo, NaN: lo = 0, s = 1.  Any grid is a correct one --
 // a bad one only enlarges the rows' errors, and with them the band.

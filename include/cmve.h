@@ -850,6 +850,40 @@ int cmve_l2_topk(cmve_handle_t h, const cmve_rows_t* q, const cmve_rows_t* g, do
                  int64_t cand_cap, int64_t sample_rows, void* ws, int64_t ws_bytes, int64_t* out_idx, double* out_err,
                  int64_t* stats);
 
+/* K23: cmve_pairwise_topk for CMVE_PW_L1 with fp64 score words at the integer SAD rate (csrc/l1_topk.hip).
+ * Replaces, as its K18 twin does: LINAS-engine/inference.py:78-80 (cal_error(video_embs, cap_emb, measure) then
+ * np.argsort(errors[0])[:topK]) under l1 / l1_norm (LINAS-engine/evaluation.py:22-35).  Additive entries: the ABI
+ * version does not change.
+ *   Q / G: the raw rows of the captions [n_q, d] and the gallery [n_g, d] (F32 or F64: the source of every canonical
+ *   score); q_codes / q_err / g_codes / g_err their packs on `grid` (cmve_l1_grid, cmve_l1_pack: both sets on ONE
+ *   grid, pads as cmve_l1_pack_size), exactly as cmve_l1_count takes a side.  out_idx int64 [n_q, k] / out_err fp64
+ *   [n_q, k] hold, word for word, what cmve_pairwise_topk(metric = CMVE_PW_L1, score_dtype = CMVE_F64) writes for the
+ *   raw rows, alpha, beta and k: (error asc, index asc) on the canonical word, NaN last in index order, -0.0 == +0.0,
+ *   ids of G's rows.  1 <= k <= n_g (the caller clamps k to the gallery).
+ *   cmve_l2_topk's four launches per round of 1,024 queries, in the space of the L1 distance
+ *   itself: K22's SAD tile over the first sample_rows gallery rows stores every pair's upper bound on
+ *   sign(alpha) * L1(q, g); the k-th smallest per query, widened by the roundings of the canonical chain, is a
+ *   threshold beyond which a row's word is strictly worse than k rows'; the SAD tile over the whole gallery appends
+ *   every row that does not clear it (or has no interval: a NaN, infinite or huge row) to the query's candidate list;
+ *   a block per query re-scores its candidates on the canonical fp64 chain, sorts them and emits k.  The grid's
+ *   offset cancels in the SAD: rows clustered far from the origin are bracketed as tightly as rows around it.
+ *   cand_cap, sample_rows, ws (cmve_l1_topk_workspace bytes: host only, no launch; the same layout formula as
+ *   cmve_l2_topk_workspace, from n_q, n_g, k, cand_cap and sample_rows), the trailing candidate counters, the
+ *   UNRESOLVED mark out_idx[i, 0] = -2 (a list that overflows, fewer than k bounded rows in the sample, or alpha < 0
+ *   with a witness at distance 0) and stats = {pairs excluded, candidates found, candidates re-scored, unresolved
+ *   queries}: as cmve_l2_topk's.
+ *   Enqueued on the handle's stream; allocates nothing, never synchronises; integer atomics only.  Refused, before
+ *   any launch: NULL arguments, alpha 0 or non-finite, beta non-finite, d outside [1, 65,536], n >= 2^31, k < 1,
+ *   k > n_g, cand_cap outside [k, 2048], a bad sample_rows, a short or misaligned workspace, NULL outputs with
+ *   n_q > 0. */
+int cmve_l1_topk_workspace(int64_t n_q, int64_t n_g, int32_t k, int64_t cand_cap, int64_t sample_rows,
+                           int64_t* bytes);
+int cmve_l1_topk(cmve_handle_t h, const void* Q, int32_t q_dtype, int64_t ldq, int64_t n_q, const void* q_codes,
+                 const double* q_err, const void* G, int32_t g_dtype, int64_t ldg, int64_t n_g, const void* g_codes,
+                 const double* g_err, int64_t d, const double* grid, double alpha, double beta, int32_t k,
+                 int64_t cand_cap, int64_t sample_rows, void* ws, int64_t ws_bytes, int64_t* out_idx, double* out_err,
+                 int64_t* stats);
+
 /* ---- training step of the projection heads ---------------
  * K11: what LINAS-engine/model.py:984-1004 (train_emb, style 'GT') runs around the GEMMs (K3 forward,
  * cmve_gemm_f32 backward) and the losses (K6/K7).  Device pointers, fp32 rows; statistics in fp64.
