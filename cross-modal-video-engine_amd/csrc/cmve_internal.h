@@ -317,7 +317,7 @@ __device__ __forceinline__ double row_inv_norm(double ss, double eps, int flags)
 // hardware converts directly -- gfx950 has no fp64 -> fp16 instruction)
 struct PackAcc {
   double e1 = 0.0, e2 = 0.0, e3 = 0.0;
-  float e4 = 0.f;  // the bf16 residual plane's squared residuals (lo16_elem), summed in fp32
+  float e4 = 0.f;  // the 8-bit residual plane's squared residuals (lo8_elem), summed in fp32
 };
 
 // block id -> its XCD's contiguous share of [0, total): the dispatcher deals blocks to the 8 XCDs round robin, so
@@ -328,20 +328,37 @@ __device__ __forceinline__ int xcd_linear(int bid, int total) {
   return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + local;
 }
 
-// ---- the bf16 residual plane of the fp16 rank operand (K14 level-2 re-score) ----
-// An element x (fp64, normalised) is packed as xf = fp32(x), h = fp16(xf); d2 = xf - h is exact in fp32 and
-// lo = bf16(d2) (RNE) keeps its top 8 bits: x2 = h + lo with |x - x2| <= |x - xf| + |d2 - lo|, where
-// d2 - lo is exact in fp32 and |x - xf| <= 2^-24 |x|.  The bound over a row is therefore
-//   ||x - x2|| <= sqrt(sum (d2 - lo)^2) + 2^-24 ||x||     (the fp32 sum's relative error <= 1024 * 2^-24 < 1e-4)
-// lo16_elem returns lo's bits and the fp32 residual d2 - lo.
-__device__ __forceinline__ uint16_t lo16_elem(float xf, _Float16 h, float& res) {
-  const float d2 = xf - (float)h;
-  const uint16_t lo = f2bf(d2);
-  res = d2 - bf2f(lo);
-  return lo;
+// ---- the 8-bit residual plane of the fp16 rank operand (K14 level-2 re-score) ----
+// An element x (fp64, normalised) is packed as xf = fp32(x), h = fp16(xf); d2 = xf - h is exact in fp32.  With
+// E = max(h's biased exponent field, 1) (fp16 subnormals share E = 1's spacing) and scale = 2^(E - 33) = ulp16(h) / 256,
+//   q = rint(d2 / scale) clamped to [-128, 127],  stored as the byte u = q + 128,  x2 = h + q scale.
+// |d2| <= ulp16(h) / 2 = 128 scale, so only the upper clamp ever acts, on the last half step below +ulp16(h) / 2
+// (d2 / scale in [127.5, 128] -> q = 127): |xf - x2| <= scale / 2, and up to scale there (= scale at the tie
+// d2 = +ulp16(h) / 2 itself).  d2 / scale is a product with a power of two and d2 - q scale a
+// difference of two multiples of ulp32(xf) no larger than d2: both exact in fp32.  |x - x2| <= |x - xf| + |d2 - q scale|
+// with |x - xf| <= 2^-24 |x|, so the bound over a row is
+//   ||x - x2|| <= sqrt(sum (d2 - q scale)^2) + 2^-24 ||x||     (the fp32 sum's relative error <= 1024 * 2^-24 < 1e-4)
+// lo8_scale_bits: scale's fp32 bits from hf = fp32(h), whose exponent field is E + 112 for a normal h and below 113
+// for a subnormal one or zero (three integer operations; the inverse scale 2^(33 - E) is one more subtraction).
+// lo8_elem returns q as a float in [-128, 127] and the fp32 residual d2 - q scale.
+__device__ __forceinline__ uint32_t lo8_scale_bits(float hf) {
+  return max(__float_as_uint(hf) & 0x7f800000u, 113u << 23) - (18u << 23);
 }
-// the row bound from the fp32 sum of squared residuals (lo16_elem) and the fp64 norm of x (1 after normalising)
-__device__ __forceinline__ float lo16_bound(double ss_res) {
+__device__ __forceinline__ float lo8_elem(float xf, float hf, float& res) {
+  const uint32_t sb = lo8_scale_bits(hf);
+  const float d2 = xf - hf;
+  const float q = __builtin_amdgcn_fmed3f(__builtin_rintf(d2 * __uint_as_float((254u << 23) - sb)), -128.f, 127.f);
+  res = fmaf(-q, __uint_as_float(sb), d2);
+  return q;
+}
+// q (lo8_elem) of a lane's element c (0..3) into byte c of the plane's dword w: q + 128 is an integer in [0, 255]
+// (v_cvt_pk_u8_f32)
+__device__ __forceinline__ uint32_t lo8_put(uint32_t w, int c, float q) {
+  return __builtin_amdgcn_cvt_pk_u8_f32(q + 128.f, (uint32_t)c, w);
+}
+constexpr uint32_t LO8_ZERO4 = 0x80808080u;  // four elements with q = 0 (padding columns: x2 = h = 0)
+// the row bound from the fp32 sum of squared residuals (lo8_elem) and the fp64 norm of x (1 after normalising)
+__device__ __forceinline__ float lo8_bound(double ss_res) {
   return f32_round_up(sqrt(ss_res) * (1.0 + 1e-4) + 5.9605e-8 * (1.0 + 1e-6) + 1e-12);
 }
 // fp16 of a normalised element through fp32 (v_cvt_f32_f64 then v_cvt_f16_f32).  The fp32 value is made opaque
@@ -466,54 +483,52 @@ __device__ __forceinline__ double wave_cos64(const TA* xa, const TB* xb, double 
   return wave_dot64<TA, TB, LIGHT>(xa, xb, d, lane) * (inva * invb);
 }
 
-// ---- K14 level-2 re-score: one pair's score from the fp16 + bf16 residual planes (lo16_elem, cmve_internal.h) ----
-// lane L holds elements [16L, 16L + 16) of each 1024-element chunk: two 16-B fp16 loads and two 16-B bf16 loads
-// per row and chunk.  x2 = h + lo is formed by ONE fp32 add, which is exact: with xf the fp32 value the prep packed
-// (lo16_elem: h = fp16(xf), d2 = xf - h exact, lo = bf16(d2)) and u = ulp32(xf),
-//   - h is a multiple of u (fp16(xf) keeps xf's top bits, normal or subnormal, or rounds up to the next power of two),
-//     and so is lo: d2 is a multiple of u, and rounding it to 8 bits either keeps it (fewer than 8 significant bits
-//     above u) or lands on a coarser multiple;
-//   - h + lo = xf + (lo - d2) with |lo - d2| <= 2^-9 |d2|, and both roundings are monotone with every power of two
-//     on their grids, so |h + lo| cannot pass the power of two above |xf|: it is a multiple of u no larger than
-//     2^24 u, an fp32 value.
-// (Checked on the CPU: 0 inexact sums in 44 million values, Gaussians at eleven scales from 1 to 2^-30 and every fp16
-// value in [0, 1] perturbed by k 2^-13 of its ulp and of itself, |k| <= 12.)  lo may be an fp32 subnormal (|d2| < 2^-126, xf itself below
-// 2^-102): the add is exact where the mode keeps fp32 denormals, as HIP's default does, and were they flushed x2 would
-// move by at most 2^-126 per element, which the 2e-12 term below covers a hundredfold over a row.  So one
-// v_cvt_f32_f16, one shift, one v_add_f32 and one v_cvt_f64_f32 per element and side replace two fp64 conversions and
-// an fp64 add.  The products and sums are fp64 (two FMA chains per lane, even and odd elements, added once; then
-// l16_wave_sum's fixed tree), so the sum's error is a few ulps of 1:
+// ---- K14 level-2 re-score: one pair's score from the fp16 + 8-bit residual planes (lo8_elem, above) ----
+// lane L holds elements [16L, 16L + 16) of the row (d_pad <= 1024): two 16-B fp16 loads and one 16-B load of the
+// residual bytes per row.  x2 = h + (u - 128) scale is formed by two fp32 FMAs, fmaf(u, scale, fmaf(-128, scale, h)),
+// and both are exact: h is a multiple of ulp16(h) = 256 scale with at most 11 significant bits, so h - 128 scale
+// (half an ulp16 below it) has at most 12, and adding u scale (0 <= u <= 255) gives h + q scale, a multiple of scale
+// no larger than 2^20 scale in magnitude (|h| < 2^11 ulp16(h) = 2^19 scale): an fp32 value.  Every operand is zero
+// or a normal fp32 number (scale >= 2^-32, h a multiple of 2^-24), so the denormal mode does not matter.
+// (tests/test_lo8_host.py checks it for every fp16 value in [0, 1], both signs, against fp64.)  So per element
+// and side: v_cvt_f32_f16, three integer operations for the scale (lo8_scale_bits), v_cvt_f32_ubyteN, two v_fma_f32
+// and v_cvt_f64_f32.  The products and sums are fp64 (two FMA chains per lane, even and odd elements, added once;
+// then l16_wave_sum's fixed tree), so the sum's error is a few ulps of 1:
 //   |s2 - cos64| <= el_q + (1 + el_q) el_g + 2e-12
 // (the 2e-12 covers the fp64 sums here and in cos64, as score_error_bound's 1e-12 does for the MFMA bound).  The
 // order of the sum is a function of the pair's elements alone (element e of lane L, then the lane tree), not of the
 // wave, the pipeline depth or the kernel geometry: one evaluation and a batch send the same pairs to level 3.
 typedef uint32_t cmve_u32x4 __attribute__((ext_vector_type(4)));
 struct L16Frag {
-  cmve_u32x4 h0, h1, l0, l1;
+  cmve_u32x4 h0, h1, r;  // 16 fp16 values (two per dword) and their 16 residual bytes (four per dword)
 };
-__device__ __forceinline__ void l16_load(const uint16_t* __restrict__ hrow, const uint16_t* __restrict__ lrow,
+__device__ __forceinline__ void l16_load(const uint16_t* __restrict__ hrow, const uint8_t* __restrict__ rrow,
                                          int64_t k, L16Frag& f) {
   f.h0 = gld((const cmve_u32x4*)(hrow + k));
   f.h1 = gld((const cmve_u32x4*)(hrow + k + 8));
-  f.l0 = gld((const cmve_u32x4*)(lrow + k));
-  f.l1 = gld((const cmve_u32x4*)(lrow + k + 8));
+  f.r = gld((const cmve_u32x4*)(rrow + k));
 }
-__device__ __forceinline__ double l16_x(uint32_t hw, uint32_t lw, int half) {
-  const uint16_t h = (uint16_t)(hw >> (16 * half));
-  const uint32_t l = half ? (lw & 0xffff0000u) : (lw << 16);
-  return (double)((float)__builtin_bit_cast(_Float16, h) + __uint_as_float(l));  // (the fp32 add is exact: above)
+// element e (0..15) of the fragment: fp16 half e & 1 of hw, byte e & 3 of rw
+template <int E>
+__device__ __forceinline__ double l16_x(uint32_t hw, uint32_t rw) {
+  const float hf = (float)__builtin_bit_cast(_Float16, (uint16_t)(hw >> (16 * (E & 1))));
+  const float sc = __uint_as_float(lo8_scale_bits(hf));
+  const float u = (float)((rw >> (8 * (E & 3))) & 0xffu);
+  return (double)fmaf(u, sc, fmaf(-128.f, sc, hf));  // (both FMAs are exact: above)
 }
 // this lane's 16 products: even elements into one FMA chain, odd elements into another, the two added once
 __device__ __forceinline__ double l16_partial(const L16Frag& a, const L16Frag& b) {
   const uint32_t ah[8] = {a.h0.x, a.h0.y, a.h0.z, a.h0.w, a.h1.x, a.h1.y, a.h1.z, a.h1.w};
-  const uint32_t al[8] = {a.l0.x, a.l0.y, a.l0.z, a.l0.w, a.l1.x, a.l1.y, a.l1.z, a.l1.w};
+  const uint32_t ar[4] = {a.r.x, a.r.y, a.r.z, a.r.w};
   const uint32_t bh[8] = {b.h0.x, b.h0.y, b.h0.z, b.h0.w, b.h1.x, b.h1.y, b.h1.z, b.h1.w};
-  const uint32_t bl[8] = {b.l0.x, b.l0.y, b.l0.z, b.l0.w, b.l1.x, b.l1.y, b.l1.z, b.l1.w};
+  const uint32_t br[4] = {b.r.x, b.r.y, b.r.z, b.r.w};
   double acc0 = 0.0, acc1 = 0.0;
 #pragma unroll
-  for (int w = 0; w < 8; ++w) {
-    acc0 = fma(l16_x(ah[w], al[w], 0), l16_x(bh[w], bl[w], 0), acc0);
-    acc1 = fma(l16_x(ah[w], al[w], 1), l16_x(bh[w], bl[w], 1), acc1);
+  for (int w = 0; w < 8; w += 2) {  // elements 2w .. 2w + 3: one residual dword
+    acc0 = fma(l16_x<0>(ah[w], ar[w / 2]), l16_x<0>(bh[w], br[w / 2]), acc0);
+    acc1 = fma(l16_x<1>(ah[w], ar[w / 2]), l16_x<1>(bh[w], br[w / 2]), acc1);
+    acc0 = fma(l16_x<2>(ah[w + 1], ar[w / 2]), l16_x<2>(bh[w + 1], br[w / 2]), acc0);
+    acc1 = fma(l16_x<3>(ah[w + 1], ar[w / 2]), l16_x<3>(bh[w + 1], br[w / 2]), acc1);
   }
   return acc0 + acc1;
 }

@@ -79,7 +79,7 @@ __device__ __forceinline__ void pack_bounds(const EvalSide& A, int64_t row, doub
                                             double e3, int lane, float (&eb)[3], double e4 = 0.0) {
   if (lane == 0) {
     gst(A.inv + row, inv);
-    if (A.lo16) A.err_lo16[row] = lo16_bound(e4);  // (lo16_elem's residuals)
+    if (A.lo8) A.err_lo8[row] = lo8_bound(e4);  // (lo8_elem's residuals)
     // pack_row_planes' bounds
     eb[0] = bf ? f32_round_up(sqrt(e1) * (1.0 + 1e-9) + 1e-12) : INFINITY;
     eb[1] = bf ? f32_round_up(sqrt(e2) * (1.0 + 1e-9) + 1e-12) : INFINITY;
@@ -98,7 +98,7 @@ __device__ __forceinline__ void pack_regs(const EvalSide& A, const EvalCommon& c
   pack_regs_lane(A, c, row, v, inv, lane, acc);
   const bool bf = pack_bf(A, c);
   const double e1 = bf ? wave_sum(acc.e1) : 0.0, e2 = bf ? wave_sum(acc.e2) : 0.0, e3 = wave_sum(acc.e3);
-  const double e4 = A.lo16 ? wave_sum((double)acc.e4) : 0.0;
+  const double e4 = A.lo8 ? wave_sum((double)acc.e4) : 0.0;
   pack_bounds(A, row, inv, bf, e1, e2, e3, lane, eb, e4);
 }
 
@@ -110,15 +110,17 @@ __device__ __forceinline__ void pack_regs_lane(const EvalSide& A, const EvalComm
   const bool want_f16 = frow != nullptr;
   if (c.mode == CMVE_SIM_F16 && want_f16) {
     // the F16 rank GEMM reads only the fp16 plane: the bf16 planes are not written and their bounds
-    // are +inf (a stale plane can never pass for a bounded one); with A.lo16 the bf16 residual plane of the
-    // level-2 re-score is written beside it (lo16_elem: two fp32 ops and a conversion per element)
-    uint16_t* lrow16 = A.lo16 ? A.lo16 + row * c.d_pad : nullptr;
+    // are +inf (a stale plane can never pass for a bounded one); with A.lo8 the 8-bit residual plane of the
+    // level-2 re-score is written beside it (lo8_elem: a lane's four elements of a chunk are one dword)
+    uint8_t* lrow8 = A.lo8 ? A.lo8 + row * c.d_pad : nullptr;
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
       const int64_t k = (int64_t)lane * 4 + 256 * m;
       if (k >= c.d_pad) break;
-      cmve_u16x4 fv = {0, 0, 0, 0}, lv = {0, 0, 0, 0};
+      cmve_u16x4 fv = {0, 0, 0, 0};
+      uint32_t lw = LO8_ZERO4;
       if (k < c.d) {
+        lw = 0u;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           const double xh = v[m][q] * inv;
@@ -127,16 +129,16 @@ __device__ __forceinline__ void pack_regs_lane(const EvalSide& A, const EvalComm
           const double r3 = xh - (double)hf16;
           acc.e3 = fma(r3, r3, acc.e3);
           fv[q] = __builtin_bit_cast(uint16_t, hf16);
-          if (lrow16) {
+          if (lrow8) {
             float res;
-            lv[q] = lo16_elem(xf, hf16, res);
+            lw = lo8_put(lw, q, lo8_elem(xf, (float)hf16, res));
             acc.e4 = fmaf(res, res, acc.e4);
           }
         }
       }
       gst((cmve_u16x4*)(frow + k), fv);
-      if (lrow16) gst((cmve_u16x4*)(lrow16 + k), lv);
-      asm volatile("" : "+v"(acc.e3), "+v"(acc.e4));  // (pack_f16_lo16: the chunk's sums complete here)
+      if (lrow8) gst((uint32_t*)(lrow8 + k), lw);
+      asm volatile("" : "+v"(acc.e3), "+v"(acc.e4));  // (pack_f16_lo8: the chunk's sums complete here)
     }
   } else {
 #pragma unroll
@@ -448,28 +450,41 @@ __device__ __forceinline__ void eval_prep_pair_body(const EvalSide& q, const Eva
 // The paired prep of the F16 rank path with the level-2 plane (the 1k-A headline's form): rows of exactly
 // d = d_pad = 256 NM elements, read in 16-B pieces (rows_vec4), so no element guards.  The same arithmetic as
 // eval_prep_pair_body -- the norms, the GT dot, the fp16 plane and its bound in the same (m, c) fma order, so
-// h16 / inv_norm / err_h16 / the GT scores are bit-identical to it -- with the bf16 residual plane
-// (lo16_elem: the hardware bf16 conversion, fp32 residuals) written beside the fp16 plane.
+// h16 / inv_norm / err_h16 / the GT scores are bit-identical to it -- with the 8-bit residual plane
+// (lo8_elem: fp32 arithmetic and the hardware byte conversion, fp32 residuals) written beside the fp16 plane.
 template <int NM>
-__device__ __forceinline__ void pack_f16_lo16(const EvalSide& A, int64_t row, const double (&v)[NM][4], double inv,
-                                              int lane, bool store, double& e3, float& e4) {
+__device__ __forceinline__ void pack_f16_lo8(const EvalSide& A, int64_t row, const double (&v)[NM][4], double inv,
+                                             int lane, bool store, double& e3, float& e4) {
   // The planes are stored WRITE-THROUGH (sc1): their lines leave the XCD's L2 clean, so this launch's end-of-kernel
-  // release (buffer_wbl2) has ~8 MB per evaluation less to write back before the rank GEMM may start
+  // release (buffer_wbl2) has ~6 MB per evaluation less to write back before the rank GEMM may start
   // (MI355X_MICROARCH.md, visibility: a release costs ~1.7 us clean, several us freshly dirtied; the eval stamps
   // measured a 5.3 us gap between the last prep block and the first rank-GEMM block).  16-B sc1 stores cost what
-  // plain ones do, narrower ones several times more, so lanes L and L ^ 1 swap halves of two chunks (one DPP swap
-  // per dword) and each stores 16 contiguous bytes: the even lane chunk m's [4L, 4L + 8), the odd lane chunk m + 1's
-  // [4L - 4, 4L + 4).
-  uint16_t* frow = A.h16 + row * (int64_t)(NM * 256);
-  uint16_t* lrow = A.lo16 + row * (int64_t)(NM * 256);
+  // plain ones do, narrower ones several times more.  fp16 plane: lanes L and L ^ 1 swap halves of two chunks (one
+  // DPP swap per dword) and each stores 16 contiguous bytes: the even lane chunk m's [4L, 4L + 8), the odd lane chunk
+  // m + 1's [4L - 4, 4L + 4).  Residual plane: a lane's four elements of a chunk are ONE dword, so the four lanes of
+  // a quad transpose the dwords of four chunks (two DPP stages, quad_perm xor 1 then xor 2) and lane 4a + b stores
+  // chunk b's bytes [16a, 16a + 16); fewer than four chunks (NM < 4) pair up two-way for 8-B stores, and an odd
+  // NM's last chunk keeps its 4-B store.
+  // (the row is the wave's: read into a scalar, its plane addresses stay out of the vector registers; rows < 2^31)
+  const int64_t urow = (int64_t)__builtin_amdgcn_readfirstlane((int)row);
+  uint16_t* frow = A.h16 + urow * (int64_t)(NM * 256);
+  uint8_t* lrow = A.lo8 + urow * (int64_t)(NM * 256);
   const __amdgpu_buffer_rsrc_t rf = __builtin_amdgcn_make_buffer_rsrc((void*)frow, 0, NM * 512, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rl = __builtin_amdgcn_make_buffer_rsrc((void*)lrow, 0, NM * 512, 0x00020000);
-  const bool odd = lane & 1;
-  cmve_u32x2 pf = {0u, 0u}, pl = {0u, 0u};  // an even chunk's values, held for its pair
+  const __amdgpu_buffer_rsrc_t rl = __builtin_amdgcn_make_buffer_rsrc((void*)lrow, 0, NM * 256, 0x00020000);
+  const bool odd = lane & 1, up = lane & 2;
+  // the paired stores' lane offset (fp16 plane; half of it in the residual plane); the chunk's part is added to it
+  // as a constant (the instruction's immediate), NOT passed as the scalar offset: after a 16-B store with a scalar
+  // offset register the compiler overwrites the store's data registers in the next instruction, and on the MI355X
+  // lanes of the store then carried the new values (measured: the batch prep's fp16 plane held residual bytes)
+  const int pair_off = odd ? 512 + 8 * (lane - 1) : 8 * lane;
+  cmve_u32x2 pf = {0u, 0u};  // an even chunk's values, held for its pair
+  uint32_t lw[NM];           // the chunks' residual dwords
   auto swap = [](uint32_t x) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0xB1, 0xF, 0xF, false); };
+  auto swap2 = [](uint32_t x) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x4E, 0xF, 0xF, false); };
 #pragma unroll
   for (int m = 0; m < NM; ++m) {
-    cmve_u16x4 fv, lv;
+    cmve_u16x4 fv;
+    lw[m] = 0u;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const double xh = v[m][q] * inv;
@@ -478,34 +493,45 @@ __device__ __forceinline__ void pack_f16_lo16(const EvalSide& A, int64_t row, co
       const float hf = (float)h;
       const double r3 = xh - (double)hf;
       e3 = fma(r3, r3, e3);
-      const float d2 = xf - hf;
-      const __bf16 lo = (__bf16)d2;
-      const float res = d2 - (float)lo;
+      float res;
+      lw[m] = lo8_put(lw[m], q, lo8_elem(xf, hf, res));
       e4 = fmaf(res, res, e4);
       fv[q] = __builtin_bit_cast(uint16_t, h);
-      lv[q] = __builtin_bit_cast(uint16_t, lo);
     }
-    const cmve_u32x2 f2 = __builtin_bit_cast(cmve_u32x2, fv), l2 = __builtin_bit_cast(cmve_u32x2, lv);
+    const cmve_u32x2 f2 = __builtin_bit_cast(cmve_u32x2, fv);
     if (store) {
       if ((m & 1) == 0 && m + 1 < NM) {
         pf = f2;
-        pl = l2;
       } else if (m & 1) {
-        const cmve_u32x2 sf = odd ? pf : f2, sl = odd ? pl : l2;  // what the partner lane needs
-        const cmve_u32x2 rf2 = {swap(sf.x), swap(sf.y)}, rl2 = {swap(sl.x), swap(sl.y)};
+        const cmve_u32x2 sf = odd ? pf : f2;  // what the partner lane needs
+        const cmve_u32x2 rf2 = {swap(sf.x), swap(sf.y)};
         const cmve_u32x4 df = odd ? cmve_u32x4{rf2.x, rf2.y, f2.x, f2.y} : cmve_u32x4{pf.x, pf.y, rf2.x, rf2.y};
-        const cmve_u32x4 dl = odd ? cmve_u32x4{rl2.x, rl2.y, l2.x, l2.y} : cmve_u32x4{pl.x, pl.y, rl2.x, rl2.y};
-        const int off = odd ? (m * 256 + 4 * (lane - 1)) * 2 : ((m - 1) * 256 + 4 * lane) * 2;
-        __builtin_amdgcn_raw_buffer_store_b128(df, rf, off, 0, 16);  // (aux 16: sc1)
-        __builtin_amdgcn_raw_buffer_store_b128(dl, rl, off, 0, 16);
+        __builtin_amdgcn_raw_buffer_store_b128(df, rf, pair_off + (m - 1) * 512, 0, 16);  // (aux 16: sc1)
       } else {  // the last chunk of an odd NM: 8 B per lane
-        __builtin_amdgcn_raw_buffer_store_b64(f2, rf, (m * 256 + 4 * lane) * 2, 0, 16);
-        __builtin_amdgcn_raw_buffer_store_b64(l2, rl, (m * 256 + 4 * lane) * 2, 0, 16);
+        __builtin_amdgcn_raw_buffer_store_b64(f2, rf, 8 * lane + m * 512, 0, 16);
+      }
+      if constexpr (NM == 4) {
+        if (m == 3) {
+          // stage 1: lanes b, b ^ 1 exchange across chunk pairs (0, 1) and (2, 3); stage 2: lanes b, b ^ 2 across
+          // (0, 2) and (1, 3): lane b ends with chunk b's dwords of the quad's lanes 0..3, in lane order
+          const uint32_t x0 = swap(odd ? lw[0] : lw[1]), x1 = swap(odd ? lw[2] : lw[3]);
+          const uint32_t a0 = odd ? x0 : lw[0], a1 = odd ? lw[1] : x0, a2 = odd ? x1 : lw[2], a3 = odd ? lw[3] : x1;
+          const uint32_t y0 = swap2(up ? a0 : a2), y1 = swap2(up ? a1 : a3);
+          const cmve_u32x4 dl = up ? cmve_u32x4{y0, y1, a2, a3} : cmve_u32x4{a0, a1, y0, y1};
+          __builtin_amdgcn_raw_buffer_store_b128(dl, rl, (lane & 3) * 256 + 16 * (lane >> 2), 0, 16);
+        }
+      } else if (m & 1) {  // two chunks: the even lane chunk m - 1's [4L, 4L + 8), the odd lane chunk m's [4L - 4, 4L + 4)
+        const uint32_t x = swap(odd ? lw[m - 1] : lw[m]);
+        const cmve_u32x2 dl = odd ? cmve_u32x2{x, lw[m]} : cmve_u32x2{lw[m - 1], x};
+        __builtin_amdgcn_raw_buffer_store_b64(dl, rl, (pair_off >> 1) + (m - 1) * 256, 0, 16);
+      } else if (m + 1 == NM) {  // the last chunk of an odd NM: 4 B per lane
+        __builtin_amdgcn_raw_buffer_store_b32(lw[m], rl, 4 * lane + m * 256, 0, 16);
       }
     }
     // the chunk's residual sums complete here (left free, the compiler sank every fma chain below the last
-    // chunk's stores and held all 32 elements' temporaries: ~190 registers)
-    asm volatile("" : "+v"(e3), "+v"(e4));
+    // chunk's stores and held all 32 elements' temporaries: ~190 registers); so does the chunk's residual dword
+    // (left free, its four floats stayed live to the transpose)
+    asm volatile("" : "+v"(e3), "+v"(e4), "+v"(lw[m]));
   }
 }
 
@@ -595,9 +621,9 @@ __device__ __forceinline__ void eval_prep_pair_f16_body(const EvalSide& q, const
       float e4q = 0.f, e4g = 0.f;
       // (one side after the other, one 4-element chunk at a time: left to itself the scheduler interleaves the
       // two sides' chunks and holds ~190 registers, which caps the prep at two waves per SIMD)
-      pack_f16_lo16<NM>(q, i, v, invq, lane, true, e3q, e4q);
+      pack_f16_lo8<NM>(q, i, v, invq, lane, true, e3q, e4q);
       __builtin_amdgcn_sched_barrier(0);
-      pack_f16_lo16<NM>(g, p, w, invg, lane, valid, e3g, e4g);
+      pack_f16_lo8<NM>(g, p, w, invg, lane, valid, e3g, e4g);
       double e[4] = {e3q, e3g, (double)e4q, (double)e4g};
       wave_sum_k<4>(e);
       pack_bounds(q, i, invq, false, 0.0, 0.0, e[0], lane, ebq, e[2]);
@@ -857,9 +883,9 @@ __global__ __launch_bounds__(PREP_NT, CMVE_PREPFIN_WPE) void eval_prep_fin_batch
   }
 }
 
-// the specialized paired prep applies: F16 with the lo16 plane, 16-B row pieces, d = d_pad = 256 NM (NM <= 4)
+// the specialized paired prep applies: F16 with the lo8 plane, 16-B row pieces, d = d_pad = 256 NM (NM <= 4)
 static int prep_f16_nm(const EvalSide& q, const EvalSide& g, const EvalCommon& c) {
-  const bool ok = c.mode == CMVE_SIM_F16 && q.h16 && g.h16 && q.lo16 && g.lo16 && q.vec && g.vec && c.d == c.d_pad &&
+  const bool ok = c.mode == CMVE_SIM_F16 && q.h16 && g.h16 && q.lo8 && g.lo8 && q.vec && g.vec && c.d == c.d_pad &&
                   c.d_pad % 256 == 0 && c.d_pad <= 1024;
   return ok ? (int)(c.d_pad / 256) : 0;
 }

@@ -109,12 +109,12 @@ struct SimArgs {
   int64_t q_ld, g_ld, d;
   const double* q_inv;
   const double* g_inv;
-  // K14 level-2 re-score (F16 rank path): the bf16 residual planes the prep wrote beside the fp16 planes (qhi /
-  // ghi) and their per-row bounds; a band pair is decided from h16 + lo16 (lo16_elem) when its score clears the
+  // K14 level-2 re-score (F16 rank path): the 8-bit residual planes the prep wrote beside the fp16 planes (qhi /
+  // ghi) and their per-row bounds; a band pair is decided from h16 + its byte (lo8_elem) when its score clears the
   // GT score by the level-2 bound; the rest go to the level-3 list (EvalCommon::l3, re-scored in fp64 by the
   // finish), or are re-scored here when it is full.  nullptr: every pair in fp64 here
-  const uint16_t* q_lo16;
-  const uint16_t* g_lo16;
+  const uint8_t* q_lo8;
+  const uint8_t* g_lo8;
   const float* q_el;
   const float* g_el;
   unsigned* l3_count;
@@ -912,8 +912,8 @@ void sim_kernel(
           }
           if (listed) {
             CMVE_BAR_LDS();
-            if (a.q_lo16) {
-              // level 2: each wave scores its listed pairs from the fp16 + bf16 residual planes (l16_load /
+            if (a.q_lo8) {
+              // level 2: each wave scores its listed pairs from the fp16 + 8-bit residual planes (l16_load /
               // l16_partial / l16_wave_sum, cmve_internal.h) and leaves each pair's score and row bounds in LDS
               // beside its list entry; after the barrier one thread per entry decides every direction whose GT
               // score lies outside s2 +- E2, all pairs at once.  A pair with a direction left undecided goes to the
@@ -945,8 +945,8 @@ void sim_kernel(
                 const int64_t qr = m0 + (ent & 0xff), gc = n0 + ((ent >> 8) & 0xff);
                 st.elq = gld(a.q_el + qr);  // (the row bounds travel with the plane rows)
                 st.elg = gld(a.g_el + gc);
-                l16_load(a.qhi + qr * l2_ldk, a.q_lo16 + qr * l2_ldk, l2_k, st.fq);
-                l16_load(a.ghi + gc * l2_ldk, a.g_lo16 + gc * l2_ldk, l2_k, st.fg);
+                l16_load(a.qhi + qr * l2_ldk, a.q_lo8 + qr * l2_ldk, l2_k, st.fq);
+                l16_load(a.ghi + gc * l2_ldk, a.g_lo8 + gc * l2_ldk, l2_k, st.fg);
                 // (the scheduler otherwise lifts the current pair's first conversions, and with them the wait for
                 // its rows, above these loads)
                 __builtin_amdgcn_sched_barrier(0);
@@ -1085,7 +1085,7 @@ void sim_kernel(
                   if ((e >> 17) & 1u) { if (s1 > epi.sgt[BM + c1 - n0]) lds_add_u32_async(&lds_cc[c1 - n0], 1); }
                 }
               }
-            } else if (a.q_lo16) {  // level 3 after level 2 (a full level-3 list): one pair at a time per wave
+            } else if (a.q_lo8) {  // level 3 after level 2 (a full level-3 list): one pair at a time per wave
               for (int p = wave; p < ntot; p += NWT) {
                 const uint32_t e = epi.list[p];
                 if (e >> 16) rescore2(e, 0u, false);
@@ -1925,10 +1925,10 @@ extern "C" int cmve_linear(cmve_handle_t h, const cmve_rows_t* x, const cmve_row
 
 namespace {
 struct EvalWs {
-  size_t done, q_sgt, q_hi, q_lo, q_cnt, g_sgt, g_hi, g_lo, g_cnt, q_gt1, g_gt1, q_el, g_el, q_l16, g_l16, l3, cand,
+  size_t done, q_sgt, q_hi, q_lo, q_cnt, g_sgt, g_hi, g_lo, g_cnt, q_gt1, g_gt1, q_el, g_el, q_l8, g_l8, l3, cand,
       total;
 };
-// the lo16 planes: [n_pad, d_pad] bf16 each side, the level-2 re-score's residuals (lo16_elem); l3: the level-3
+// the lo8 planes: [n_pad, d_pad] bytes each side, the level-2 re-score's residuals (lo8_elem); l3: the level-3
 // list (a count word, then EVAL_L3_CAP entries)
 constexpr int EVAL_L3_CAP = 4096;
 EvalWs eval_ws_layout(int64_t nq_pad, int64_t ng_pad, int64_t d_pad, int64_t cand_cap) {
@@ -1961,10 +1961,10 @@ EvalWs eval_ws_layout(int64_t nq_pad, int64_t ng_pad, int64_t d_pad, int64_t can
   o = up(o + 4 * (size_t)nq_pad);
   w.g_el = o;
   o = up(o + 4 * (size_t)ng_pad);
-  w.q_l16 = o;
-  o = up(o + 2 * (size_t)nq_pad * (size_t)d_pad);
-  w.g_l16 = o;
-  o = up(o + 2 * (size_t)ng_pad * (size_t)d_pad);
+  w.q_l8 = o;
+  o = up(o + (size_t)nq_pad * (size_t)d_pad);
+  w.g_l8 = o;
+  o = up(o + (size_t)ng_pad * (size_t)d_pad);
   w.l3 = o;
   o = up(o + 8 + 8 * (size_t)EVAL_L3_CAP);
   w.cand = o;
@@ -2162,8 +2162,8 @@ static int eval_prepare(cmve_rows_t* q, cmve_rows_t* g, int32_t mode_flags, cons
   }
   // G64 (1k-A scale): the rank GEMM re-scores its own undecided pairs (no list, no fix-up launch)
   P.inline_fix = a.thr_gt && sim_uses_g64(q->n_pad, g->n_pad);
-  // level-2 re-score from the fp16 + bf16 residual planes: the F16 mode whose prep runs the register path (the
-  // only one that writes lo16: 16-B row pieces, d_pad <= 1024, both sides).  Level 2 runs inside the rank GEMM, which
+  // level-2 re-score from the fp16 + 8-bit residual planes: the F16 mode whose prep runs the register path (the
+  // only one that writes lo8: 16-B row pieces, d_pad <= 1024, both sides).  Level 2 runs inside the rank GEMM, which
   // counts the pairs it leaves for level 3 (out[12]).  ONE evaluation (cmve_eval_ranks, its graphs) re-scores those
   // in the GEMM too (its ~4 pairs cost the GEMM ~0.7 us and spare the finish its fp64 round trip: 32.5 -> 31.4 us
   // back to back); batches list them for the finish (in a chained run it rides in the next prep launch).  The forms
@@ -2171,14 +2171,14 @@ static int eval_prepare(cmve_rows_t* q, cmve_rows_t* g, int32_t mode_flags, cons
   // profiles/STUDIES.md
   const bool l2 = P.inline_fix && mode == CMVE_SIM_F16 && P.sq.vec && P.sg.vec && q->d_pad <= 1024;
   if (l2) {
-    P.sq.lo16 = (uint16_t*)(base + w.q_l16);
-    P.sg.lo16 = (uint16_t*)(base + w.g_l16);
-    P.sq.err_lo16 = (float*)(base + w.q_el);
-    P.sg.err_lo16 = (float*)(base + w.g_el);
-    a.q_lo16 = P.sq.lo16;
-    a.g_lo16 = P.sg.lo16;
-    a.q_el = P.sq.err_lo16;
-    a.g_el = P.sg.err_lo16;
+    P.sq.lo8 = (uint8_t*)(base + w.q_l8);
+    P.sg.lo8 = (uint8_t*)(base + w.g_l8);
+    P.sq.err_lo8 = (float*)(base + w.q_el);
+    P.sg.err_lo8 = (float*)(base + w.g_el);
+    a.q_lo8 = P.sq.lo8;
+    a.g_lo8 = P.sg.lo8;
+    a.q_el = P.sq.err_lo8;
+    a.g_el = P.sg.err_lo8;
     c.l3_count = (unsigned*)(base + w.l3);
     c.l3 = (uint64_t*)(base + w.l3 + 8);
     c.l3_cap = batch ? EVAL_L3_CAP : 0;  // (0: the finish re-scores nothing; its count still reaches out[12])
@@ -2352,8 +2352,8 @@ extern "C" int cmve_eval_batch_create(int32_t count, cmve_rows_t* const* q, cmve
       // from the first evaluation's plan: every evaluation must plan the same way -- e.g. a row-strided input whose
       // rows are not 16-B aligned takes no register prep and no residual plane, which the specialised prep would
       // still read and write through
-      CMVE_REQUIRE(P.sq.vec == P0.sq.vec && P.sg.vec == P0.sg.vec && (P.sq.lo16 != nullptr) == (P0.sq.lo16 != nullptr) &&
-                       (P.sg.lo16 != nullptr) == (P0.sg.lo16 != nullptr) &&
+      CMVE_REQUIRE(P.sq.vec == P0.sq.vec && P.sg.vec == P0.sg.vec && (P.sq.lo8 != nullptr) == (P0.sq.lo8 != nullptr) &&
+                       (P.sg.lo8 != nullptr) == (P0.sg.lo8 != nullptr) &&
                        (P.c.l3_count != nullptr) == (P0.c.l3_count != nullptr),
                    "cmve_eval_batch_create: evaluation %d's inputs take another path than the first's (row alignment "
                    "or stride: every evaluation of a batch needs 16-B aligned rows if the first has them)", i);

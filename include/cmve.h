@@ -400,10 +400,10 @@ int cmve_gt_ranks(cmve_handle_t h, const int32_t* cnt, const double* sgt, int64_
  * were empty and is counted in out[11] (0 for a valid pairing): with out[11] != 0 the ranks are undefined,
  * but no write leaves the workspace / planes.  Lists whose v2t side is not the inverse (two captions naming
  * one video) give undefined ranks: both waves write that video's row (within bounds).
- * At F16 size with d_pad <= 1024 and 16-B aligned rows the workspace also holds a bf16 residual plane of
- * each side (x_hat - fp16 plane): launch 2 decides a band pair from fp16 + residual (error <= el_q +
- * (1 + el_q) el_g, ~7e-7) and lists the pairs within that bound (out[12] counts them; ~4 per 1k-A
- * evaluation), which the last launch re-scores in fp64 before it ranks (a full list: launch 2 re-scores the
+ * At F16 size with d_pad <= 1024 and 16-B aligned rows the workspace also holds an 8-bit residual plane of
+ * each side (x_hat - fp16 plane, in units of 1/256 of the fp16 element's ulp): launch 2 decides a band pair from
+ * fp16 + residual (error <= el_q + (1 + el_q) el_g, ~1.8e-6) and lists the pairs within that bound (out[12] counts
+ * them; ~1-6 per 1k-A evaluation), which the last launch re-scores in fp64 before it ranks (a full list: launch 2 re-scores the
  * rest itself).
  */
 #define CMVE_EVAL_TIMING_SLOTS 32
