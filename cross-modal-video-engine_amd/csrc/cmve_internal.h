@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <type_traits>
 #include "../../include/cmve.h"
+#include "lo8_step.h"
 
 struct cmve_handle {
   int device;
@@ -329,34 +330,21 @@ __device__ __forceinline__ int xcd_linear(int bid, int total) {
 }
 
 // ---- the 8-bit residual plane of the fp16 rank operand (K14 level-2 re-score) ----
-// An element x (fp64, normalised) is packed as xf = fp32(x), h = fp16(xf); d2 = xf - h is exact in fp32.  With
-// E = max(h's biased exponent field, 1) (fp16 subnormals share E = 1's spacing) and scale = 2^(E - 33) = ulp16(h) / 256,
-//   q = rint(d2 / scale) clamped to [-128, 127],  stored as the byte u = q + 128,  x2 = h + q scale.
-// |d2| <= ulp16(h) / 2 = 128 scale, so only the upper clamp ever acts, on the last half step below +ulp16(h) / 2
-// (d2 / scale in [127.5, 128] -> q = 127): |xf - x2| <= scale / 2, and up to scale there (= scale at the tie
-// d2 = +ulp16(h) / 2 itself).  d2 / scale is a product with a power of two and d2 - q scale a
-// difference of two multiples of ulp32(xf) no larger than d2: both exact in fp32.  |x - x2| <= |x - xf| + |d2 - q scale|
-// with |x - xf| <= 2^-24 |x|, so the bound over a row is
-//   ||x - x2|| <= sqrt(sum (d2 - q scale)^2) + 2^-24 ||x||     (the fp32 sum's relative error <= 1024 * 2^-24 < 1e-4)
-// lo8_scale_bits: scale's fp32 bits from hf = fp32(h), whose exponent field is E + 112 for a normal h and below 113
-// for a subnormal one or zero (three integer operations; the inverse scale 2^(33 - E) is one more subtraction).
-// lo8_elem returns q as a float in [-128, 127] and the fp32 residual d2 - q scale.
-__device__ __forceinline__ uint32_t lo8_scale_bits(float hf) {
-  return max(__float_as_uint(hf) & 0x7f800000u, 113u << 23) - (18u << 23);
+// An element x (fp64, normalised) is packed as xf = fp32(x), h = fp16(xf); the plane's byte u places x2 on a grid of
+// 256 steps of ulp16(h) / 256 around h, as a step of 32 u on fp32(h)'s BIT PATTERN (lo8_step.h: the code, its edge
+// cases and why x2 is always zero or a normal fp32 number).  xf - x2 is exact in fp32 (the two lie within a factor
+// of two) and |x - x2| <= |x - xf| + |xf - x2| with |x - xf| <= 2^-24 |x|, so the bound over a row is
+//   ||x - x2|| <= sqrt(sum (xf - x2)^2) + 2^-24 ||x||     (the fp32 sum's relative error <= 1024 * 2^-24 < 1e-4)
+// lo8_elem returns the byte u and the fp32 residual xf - x2, x2 formed as the decoder forms it.
+__device__ __forceinline__ uint32_t lo8_elem(float xf, float hf, float& res) {
+  const uint32_t B = __float_as_uint(hf);
+  const uint32_t u = lo8_step_encode(__float_as_uint(xf), B);
+  res = xf - __uint_as_float(lo8_step_decode(B, u));
+  return u;
 }
-__device__ __forceinline__ float lo8_elem(float xf, float hf, float& res) {
-  const uint32_t sb = lo8_scale_bits(hf);
-  const float d2 = xf - hf;
-  const float q = __builtin_amdgcn_fmed3f(__builtin_rintf(d2 * __uint_as_float((254u << 23) - sb)), -128.f, 127.f);
-  res = fmaf(-q, __uint_as_float(sb), d2);
-  return q;
-}
-// q (lo8_elem) of a lane's element c (0..3) into byte c of the plane's dword w: q + 128 is an integer in [0, 255]
-// (v_cvt_pk_u8_f32)
-__device__ __forceinline__ uint32_t lo8_put(uint32_t w, int c, float q) {
-  return __builtin_amdgcn_cvt_pk_u8_f32(q + 128.f, (uint32_t)c, w);
-}
-constexpr uint32_t LO8_ZERO4 = 0x80808080u;  // four elements with q = 0 (padding columns: x2 = h = 0)
+// u (lo8_elem) of a lane's element c (0..3) into byte c of the plane's dword w (v_lshl_or_b32)
+__device__ __forceinline__ uint32_t lo8_put(uint32_t w, int c, uint32_t u) { return w | (u << (8 * c)); }
+constexpr uint32_t LO8_ZERO4 = 0x80808080u;  // four elements with u = 128 (padding columns: x2 = h = 0)
 // the row bound from the fp32 sum of squared residuals (lo8_elem) and the fp64 norm of x (1 after normalising)
 __device__ __forceinline__ float lo8_bound(double ss_res) {
   return f32_round_up(sqrt(ss_res) * (1.0 + 1e-4) + 5.9605e-8 * (1.0 + 1e-6) + 1e-12);
@@ -485,15 +473,13 @@ __device__ __forceinline__ double wave_cos64(const TA* xa, const TB* xb, double 
 
 // ---- K14 level-2 re-score: one pair's score from the fp16 + 8-bit residual planes (lo8_elem, above) ----
 // lane L holds elements [16L, 16L + 16) of the row (d_pad <= 1024): two 16-B fp16 loads and one 16-B load of the
-// residual bytes per row.  x2 = h + (u - 128) scale is formed by two fp32 FMAs, fmaf(u, scale, fmaf(-128, scale, h)),
-// and both are exact: h is a multiple of ulp16(h) = 256 scale with at most 11 significant bits, so h - 128 scale
-// (half an ulp16 below it) has at most 12, and adding u scale (0 <= u <= 255) gives h + q scale, a multiple of scale
-// no larger than 2^20 scale in magnitude (|h| < 2^11 ulp16(h) = 2^19 scale): an fp32 value.  Every operand is zero
-// or a normal fp32 number (scale >= 2^-32, h a multiple of 2^-24), so the denormal mode does not matter.
-// (tests/test_lo8_host.py checks it for every fp16 value in [0, 1], both signs, against fp64.)  So per element
-// and side: v_cvt_f32_f16, three integer operations for the scale (lo8_scale_bits), v_cvt_f32_ubyteN, two v_fma_f32
-// and v_cvt_f64_f32.  The products and sums are fp64 (two FMA chains per lane, even and odd elements, added once;
-// then l16_wave_sum's fixed tree), so the sum's error is a few ulps of 1:
+// residual bytes per row.  x2 = as_float(bits(fp32(h)) + 32 (u - 128)) (lo8_step.h): no float arithmetic before the
+// fp64 product, and x2 is zero or a normal fp32 number, so the denormal mode does not matter
+// (tests/test_lo8_step_host.py checks it for every fp16 value in [0, 1], both signs).  A plane dword's four top bits
+// are flipped once (u ^ 0x80 is u - 128 as a signed byte), so per element and side: v_cvt_f32_f16, v_bfe_i32 (the
+// sign-extended byte), v_lshl_add_u32 and v_cvt_f64_f32, plus a quarter of the v_xor_b32.  The products and sums are
+// fp64 (two FMA chains per lane, even and odd elements, added once; then l16_wave_sum's fixed tree), so the sum's
+// error is a few ulps of 1:
 //   |s2 - cos64| <= el_q + (1 + el_q) el_g + 2e-12
 // (the 2e-12 covers the fp64 sums here and in cos64, as score_error_bound's 1e-12 does for the MFMA bound).  The
 // order of the sum is a function of the pair's elements alone (element e of lane L, then the lane tree), not of the
@@ -508,27 +494,32 @@ __device__ __forceinline__ void l16_load(const uint16_t* __restrict__ hrow, cons
   f.h1 = gld((const cmve_u32x4*)(hrow + k + 8));
   f.r = gld((const cmve_u32x4*)(rrow + k));
 }
-// element e (0..15) of the fragment: fp16 half e & 1 of hw, byte e & 3 of rw
+// element e (0..15) of the fragment: fp16 half e & 1 of hw, byte e & 3 of rs = the plane's dword ^ 0x80808080.
+// sh is the step's shift, 5, in a register (l16_partial): with the constant the compiler merges the byte's extract
+// and the shift into a 13-bit extract at bit 8e - 5 that needs a mask of its own before the add, three integer
+// instructions instead of v_bfe_i32 and v_lshl_add_u32
 template <int E>
-__device__ __forceinline__ double l16_x(uint32_t hw, uint32_t rw) {
+__device__ __forceinline__ double l16_x(uint32_t hw, uint32_t rs, int sh) {
   const float hf = (float)__builtin_bit_cast(_Float16, (uint16_t)(hw >> (16 * (E & 1))));
-  const float sc = __uint_as_float(lo8_scale_bits(hf));
-  const float u = (float)((rw >> (8 * (E & 3))) & 0xffu);
-  return (double)fmaf(u, sc, fmaf(-128.f, sc, hf));  // (both FMAs are exact: above)
+  const int32_t q = (int32_t)(rs << (24 - 8 * (E & 3))) >> 24;  // u - 128
+  return (double)__uint_as_float(lo8_step_decode_q(__float_as_uint(hf), q, sh));
 }
 // this lane's 16 products: even elements into one FMA chain, odd elements into another, the two added once
 __device__ __forceinline__ double l16_partial(const L16Frag& a, const L16Frag& b) {
   const uint32_t ah[8] = {a.h0.x, a.h0.y, a.h0.z, a.h0.w, a.h1.x, a.h1.y, a.h1.z, a.h1.w};
-  const uint32_t ar[4] = {a.r.x, a.r.y, a.r.z, a.r.w};
+  constexpr uint32_t S = 0x80808080u;  // (u -> u - 128 as a signed byte, four elements at once)
+  const uint32_t ar[4] = {a.r.x ^ S, a.r.y ^ S, a.r.z ^ S, a.r.w ^ S};
   const uint32_t bh[8] = {b.h0.x, b.h0.y, b.h0.z, b.h0.w, b.h1.x, b.h1.y, b.h1.z, b.h1.w};
-  const uint32_t br[4] = {b.r.x, b.r.y, b.r.z, b.r.w};
+  const uint32_t br[4] = {b.r.x ^ S, b.r.y ^ S, b.r.z ^ S, b.r.w ^ S};
+  int sh = 5;
+  asm("" : "+s"(sh));  // (opaque: l16_x)
   double acc0 = 0.0, acc1 = 0.0;
 #pragma unroll
   for (int w = 0; w < 8; w += 2) {  // elements 2w .. 2w + 3: one residual dword
-    acc0 = fma(l16_x<0>(ah[w], ar[w / 2]), l16_x<0>(bh[w], br[w / 2]), acc0);
-    acc1 = fma(l16_x<1>(ah[w], ar[w / 2]), l16_x<1>(bh[w], br[w / 2]), acc1);
-    acc0 = fma(l16_x<2>(ah[w + 1], ar[w / 2]), l16_x<2>(bh[w + 1], br[w / 2]), acc0);
-    acc1 = fma(l16_x<3>(ah[w + 1], ar[w / 2]), l16_x<3>(bh[w + 1], br[w / 2]), acc1);
+    acc0 = fma(l16_x<0>(ah[w], ar[w / 2], sh), l16_x<0>(bh[w], br[w / 2], sh), acc0);
+    acc1 = fma(l16_x<1>(ah[w], ar[w / 2], sh), l16_x<1>(bh[w], br[w / 2], sh), acc1);
+    acc0 = fma(l16_x<2>(ah[w + 1], ar[w / 2], sh), l16_x<2>(bh[w + 1], br[w / 2], sh), acc0);
+    acc1 = fma(l16_x<3>(ah[w + 1], ar[w / 2], sh), l16_x<3>(bh[w + 1], br[w / 2], sh), acc1);
   }
   return acc0 + acc1;
 }

@@ -451,7 +451,8 @@ __device__ __forceinline__ void eval_prep_pair_body(const EvalSide& q, const Eva
 // d = d_pad = 256 NM elements, read in 16-B pieces (rows_vec4), so no element guards.  The same arithmetic as
 // eval_prep_pair_body -- the norms, the GT dot, the fp16 plane and its bound in the same (m, c) fma order, so
 // h16 / inv_norm / err_h16 / the GT scores are bit-identical to it -- with the 8-bit residual plane
-// (lo8_elem: fp32 arithmetic and the hardware byte conversion, fp32 residuals) written beside the fp16 plane.
+// (lo8_elem: the step code of lo8_step.h, integer work on the bit patterns of xf and fp32(h), and one fp32
+// subtraction for the residual) written beside the fp16 plane.
 template <int NM>
 __device__ __forceinline__ void pack_f16_lo8(const EvalSide& A, int64_t row, const double (&v)[NM][4], double inv,
                                              int lane, bool store, double& e3, float& e4) {

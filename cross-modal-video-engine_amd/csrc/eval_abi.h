@@ -32,7 +32,7 @@ struct EvalSide {
   int64_t* ranks;      // out: 1-based ranks of this direction
   int32_t* gt1;        // the first GT of each row (idx[off[row]], -1: none / padding), written by the prep: the
                        // rank GEMM drops that GT pair from the undecided list (it can never be counted)
-  uint8_t* lo8;        // F16 rank path: [n_pad, d_pad] 8-bit residual plane of x_hat - h16 (lo8_elem), nullptr: off
+  uint8_t* lo8;        // F16 rank path: [n_pad, d_pad] 8-bit residual plane of x_hat beside h16 (the step code, lo8_step.h), nullptr: off
   float* err_lo8;      // [n_pad] upper bound of ||x_hat - (h16 + lo8's residual)||_2 (the level-2 re-score's bound)
 };
 

@@ -401,7 +401,8 @@ int cmve_gt_ranks(cmve_handle_t h, const int32_t* cnt, const double* sgt, int64_
  * but no write leaves the workspace / planes.  Lists whose v2t side is not the inverse (two captions naming
  * one video) give undefined ranks: both waves write that video's row (within bounds).
  * At F16 size with d_pad <= 1024 and 16-B aligned rows the workspace also holds an 8-bit residual plane of
- * each side (x_hat - fp16 plane, in units of 1/256 of the fp16 element's ulp): launch 2 decides a band pair from
+ * each side (x_hat beside the fp16 plane: a byte u places it at bit pattern fp32(h) - 4096 + 32 u, steps of 1/256
+ * of the fp16 element's ulp, sign-magnitude; csrc/lo8_step.h): launch 2 decides a band pair from
  * fp16 + residual (error <= el_q + (1 + el_q) el_g, ~1.8e-6) and lists the pairs within that bound (out[12] counts
  * them; ~1-6 per 1k-A evaluation), which the last launch re-scores in fp64 before it ranks (a full list: launch 2 re-scores the
  * rest itself).
