@@ -862,6 +862,18 @@ def l2_topk_workspace(q: "RowSet", g: "RowSet", k: int, cand_cap: Optional[int] 
     return n.value
 
 
+def _filtered_topk_call(fn, name: str, head: tuple, n_q: int, k: int, nbytes: int, ws, dev):
+    """What ``l2_topk`` and ``l1_topk`` share: ``fn(handle, *head, ws, nbytes, idx, err, stats)`` with ws the caller's
+    when it holds ``nbytes`` at an 8-byte aligned address (a fresh one otherwise), fresh outputs, the stats record."""
+    if ws is None or _nbytes(ws) < nbytes or ws.data_ptr() % 8:
+        ws = torch.empty(max(nbytes // 8, 1), dtype=torch.int64, device=dev)
+    idx = torch.empty((n_q, int(k)), dtype=torch.int64, device=dev)
+    err = torch.empty((n_q, int(k)), dtype=torch.float64, device=dev)
+    st = torch.empty(4, dtype=torch.int64, device=dev)
+    check(fn(handle(dev), *head, _ptr(ws), nbytes, _ptr(idx), _ptr(err), _ptr(st)), name)
+    return idx, err, _stats4(("excluded", "candidates", "rescored", "unresolved"), st.cpu().numpy())
+
+
 def l2_topk(q: "RowSet", g: "RowSet", alpha: float, beta: float, k: int, cand_cap: Optional[int] = None,
             sample_rows: Optional[int] = None, ws: Optional[torch.Tensor] = None):
     """``cmve_l2_topk`` (K20): (idx int64 [n_q, k], err fp64 [n_q, k]) on the device and the stats dict
@@ -869,16 +881,9 @@ def l2_topk(q: "RowSet", g: "RowSet", alpha: float, beta: float, k: int, cand_ca
     idx[i, 0] == -2 and the rest of its row unwritten.  k must not exceed the gallery.  ws: a caller-held device
     workspace, used when it holds ``l2_topk_workspace`` bytes (a fresh one otherwise)."""
     cap = L2_TOPK_CAND_MAX if cand_cap is None else int(cand_cap)
-    nbytes = l2_topk_workspace(q, g, k, cap, sample_rows)
-    dev = g.device
-    if ws is None or _nbytes(ws) < nbytes or ws.data_ptr() % 8:
-        ws = torch.empty(max(nbytes // 8, 1), dtype=torch.int64, device=dev)
-    idx = torch.empty((q.n, int(k)), dtype=torch.int64, device=dev)
-    err = torch.empty((q.n, int(k)), dtype=torch.float64, device=dev)
-    st = torch.empty(4, dtype=torch.int64, device=dev)
-    check(lib.cmve_l2_topk(handle(dev), C.byref(q.desc), C.byref(g.desc), float(alpha), float(beta), int(k), cap,
-                           int(sample_rows or 0), _ptr(ws), nbytes, _ptr(idx), _ptr(err), _ptr(st)), "cmve_l2_topk")
-    return idx, err, _stats4(("excluded", "candidates", "rescored", "unresolved"), st.cpu().numpy())
+    head = (C.byref(q.desc), C.byref(g.desc), float(alpha), float(beta), int(k), cap, int(sample_rows or 0))
+    return _filtered_topk_call(lib.cmve_l2_topk, "cmve_l2_topk", head, q.n, k,
+                               l2_topk_workspace(q, g, k, cap, sample_rows), ws, g.device)
 
 
 L1_TOPK_CAND_MAX = L2_TOPK_CAND_MAX  # cmve_l1_topk's limit on cand_cap: the same last launch, the same LDS
@@ -937,19 +942,12 @@ def l1_topk(q: "L1Set", g: "L1Set", alpha: float, beta: float, k: int, cand_cap:
     if q.d != g.d:
         raise ValueError(f"l1_topk: dimensions differ ({q.d}, {g.d})")
     cap = L1_TOPK_CAND_MAX if cand_cap is None else int(cand_cap)
-    nbytes = l1_topk_workspace(q, g, k, cap, sample_rows)
-    dev = g.device
-    if ws is None or _nbytes(ws) < nbytes or ws.data_ptr() % 8:
-        ws = torch.empty(max(nbytes // 8, 1), dtype=torch.int64, device=dev)
-    idx = torch.empty((q.n, int(k)), dtype=torch.int64, device=dev)
-    err = torch.empty((q.n, int(k)), dtype=torch.float64, device=dev)
-    st = torch.empty(4, dtype=torch.int64, device=dev)
     a, b = q.raw, g.raw
-    check(lib.cmve_l1_topk(handle(dev), _ptr(a), _dtype_code(a), _pw_ld(a), q.n, _ptr(q.codes), _ptr(q.err),
-                           _ptr(b), _dtype_code(b), _pw_ld(b), g.n, _ptr(g.codes), _ptr(g.err), g.d, _ptr(g.grid),
-                           float(alpha), float(beta), int(k), cap, int(sample_rows or 0), _ptr(ws), nbytes, _ptr(idx),
-                           _ptr(err), _ptr(st)), "cmve_l1_topk")
-    return idx, err, _stats4(("excluded", "candidates", "rescored", "unresolved"), st.cpu().numpy())
+    head = (_ptr(a), _dtype_code(a), _pw_ld(a), q.n, _ptr(q.codes), _ptr(q.err), _ptr(b), _dtype_code(b), _pw_ld(b),
+            g.n, _ptr(g.codes), _ptr(g.err), g.d, _ptr(g.grid), float(alpha), float(beta), int(k), cap,
+            int(sample_rows or 0))
+    return _filtered_topk_call(lib.cmve_l1_topk, "cmve_l1_topk", head, q.n, k,
+                               l1_topk_workspace(q, g, k, cap, sample_rows), ws, g.device)
 
 
 def _topk_filtered(metric: int, filtered, q, g, alpha, beta, k):

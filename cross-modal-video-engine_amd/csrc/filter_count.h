@@ -57,16 +57,8 @@ static inline int flt_check_lists(const char* name, FltLists& l) {
   return CMVE_OK;
 }
 
-// ---- the launches that do not depend on how the pairs were filtered (`metric` is CMVE_PW_L2 or CMVE_PW_L1) ----
-// the raw rows of both sides: the operands of every canonical score
-struct FltRows {
-  const void* A;
-  int32_t a_dtype;
-  int64_t lda, na;
-  const void* B;
-  int32_t b_dtype;
-  int64_t ldb, nb, d;
-};
+// ---- the launches that do not depend on how the pairs were filtered (`metric` is CMVE_PW_L2 or CMVE_PW_L1; FltRows,
+// the raw rows of both sides, is l2_filter_tile.h's) ----
 // the NaN items' words of one direction (n_lists lists, the caller's n); l2_filter.hip
 void l2f_nan_launch(hipStream_t st, const int64_t* off, const double* sc, int64_t n_lists, int64_t n, int32_t* pos);
 // the band list's pairs on the canonical chain (returns at once on the device when the list overflowed); l2_filter.hip

@@ -13,10 +13,10 @@
 //   l1f_grid_kernel  min / max of the eligible elements into the two grid words (integer atomics on the words' bits:
 //                    order-independent), accumulating so that two sets can share one grid
 //   l1f_pack_kernel  rows -> codes in the tiled order of l1_filter_tile.h, and the rows' errors
-//   l1f_main_kernel  128 x 128 tile, 256 threads of 8 x 8 u32 accumulators, 32-element K tiles double-buffered in LDS
-//                    (a straight copy of the packed block; k-major, so a thread's 8 rows of a code dword are two
-//                    ds_read_b128); fp64 epilogue as l2f_main_kernel's: interval test against each item, band append,
-//                    counts (shuffle / LDS partial sums, one integer atomic per (item, tile): bit-reproducible)
+//   l1f_main_kernel  128 x 128 tile, 256 threads of 8 x 8 u32 accumulators: the SADs are l1f_sad_tile's
+//                    (l1_filter_tile.h; the one K loop, shared with K23's l1t_pass_kernel); fp64 epilogue as
+//                    l2f_main_kernel's: interval test against each item, band append, counts (shuffle / LDS partial
+//                    sums, one integer atomic per (item, tile): bit-reproducible)
 #include "filter_count.h"
 #include "l1_filter_tile.h"
 
@@ -160,10 +160,6 @@ struct L1fEpi {
 };
 static_assert(sizeof(L1fEpi) <= L1F_SMEM, "the epilogue's LDS fits the staging buffers");
 
-// thread (ty, tx) = (tid >> 4, tid & 15) owns the A rows arow(ty, u) and the B rows arow(tx, v), u, v < 8: two runs of
-// four consecutive rows 64 apart -- a 16-lane group's ds_read_b128 of a run covers 256 contiguous bytes
-__device__ __forceinline__ int l1f_row(int t, int u) { return (u >> 2) * 64 + t * 4 + (u & 3); }
-
 __global__ __launch_bounds__(256, 4) void l1f_main_kernel(L1fArgs a) {
   __shared__ __attribute__((aligned(16))) char smem[L1F_SMEM];
   const int tid = threadIdx.x, lane = tid & 63, tx = tid & 15, ty = tid >> 4;
@@ -172,57 +168,10 @@ __global__ __launch_bounds__(256, 4) void l1f_main_kernel(L1fArgs a) {
   const int64_t i0 = (int64_t)ta * L1F_BM, j0 = (int64_t)tb_ * L1F_BN;
 
   // ---- the SADs: acc[u][v] of the pair (A row i0 + l1f_row(ty, u), B row j0 + l1f_row(tx, v)); the tiles' blocks lie
-  // below the sets' n_pad (a multiple of 128) and d_pad: in bounds.  l1t_pass_kernel (l1_topk.hip, K23) carries a COPY
-  // of this K loop, so that this kernel keeps the instruction stream it is tuned on: a change to either loop is made
-  // in both.
+  // below the sets' n_pad (a multiple of 128) and d_pad: in bounds
   uint32_t acc[8][8];
-#pragma unroll
-  for (int u = 0; u < 8; ++u)
-#pragma unroll
-    for (int v = 0; v < 8; ++v) acc[u][v] = 0u;
-  constexpr int Q = L1F_TILE_DW / 4;  // 16-byte pieces of a block: two per thread
-  const l2f_u32x4* ga = (const l2f_u32x4*)(a.a_codes + (int64_t)ta * a.nkt * L1F_TILE_DW) + tid;
-  const l2f_u32x4* gb = (const l2f_u32x4*)(a.b_codes + (int64_t)tb_ * a.nkt * L1F_TILE_DW) + tid;
-  l2f_u32x4 ra[2], rb[2];
-#define L1F_LOAD(kt)                                      \
-  {                                                       \
-    ra[0] = ga[(int64_t)(kt) * Q];                        \
-    ra[1] = ga[(int64_t)(kt) * Q + 256];                  \
-    rb[0] = gb[(int64_t)(kt) * Q];                        \
-    rb[1] = gb[(int64_t)(kt) * Q + 256];                  \
-  }
-#define L1F_WRITE(buf)                                                             \
-  {                                                                                \
-    char* w_ = smem + (buf) * L1F_STAGE + tid * 16;                                \
-    *(l2f_u32x4*)(w_) = ra[0];                                                     \
-    *(l2f_u32x4*)(w_ + 4096) = ra[1];                                              \
-    *(l2f_u32x4*)(w_ + L1F_TILE_DW * 4) = rb[0];                                   \
-    *(l2f_u32x4*)(w_ + L1F_TILE_DW * 4 + 4096) = rb[1];                            \
-  }
-  L1F_LOAD(0)
-  L1F_WRITE(0)
-  __syncthreads();
-  for (int kt = 0; kt < a.nkt; ++kt) {
-    const int buf = kt & 1;
-    if (kt + 1 < a.nkt) L1F_LOAD(kt + 1)
-    const char* pa = smem + buf * L1F_STAGE + ty * 16;
-    const char* pb = smem + buf * L1F_STAGE + L1F_TILE_DW * 4 + tx * 16;
-#pragma unroll 2
-    for (int kd = 0; kd < L1F_KD; ++kd) {
-      const l2f_u32x4 a0 = *(const l2f_u32x4*)(pa + kd * 512), a1 = *(const l2f_u32x4*)(pa + kd * 512 + 256);
-      const l2f_u32x4 b0 = *(const l2f_u32x4*)(pb + kd * 512), b1 = *(const l2f_u32x4*)(pb + kd * 512 + 256);
-      const uint32_t av[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
-      const uint32_t bv[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
-#pragma unroll
-      for (int u = 0; u < 8; ++u)
-#pragma unroll
-        for (int v = 0; v < 8; ++v) acc[u][v] = __builtin_amdgcn_sad_u16(av[u], bv[v], acc[u][v]);
-    }
-    if (kt + 1 < a.nkt) L1F_WRITE(buf ^ 1)
-    __syncthreads();
-  }
-#undef L1F_LOAD
-#undef L1F_WRITE
+  l1f_sad_tile(a.a_codes + (int64_t)ta * a.nkt * L1F_TILE_DW, a.b_codes + (int64_t)tb_ * a.nkt * L1F_TILE_DW, a.nkt,
+               smem, acc);
 
   // ---- epilogue (every wave has passed the loop's last barrier: smem is free) ------------------------------------------
   L1fEpi& E = *(L1fEpi*)smem;

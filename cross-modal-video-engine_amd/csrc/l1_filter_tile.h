@@ -1,6 +1,7 @@
-// The integer SAD filter of the L1 measures (CMVE_PW_L1, fp64 score words: l1 / l1_norm), K22 -- the pieces its
-// kernels share (l1_filter.hip): the grid both sets are quantised on, the tiled order of the uint16 codes, the
-// interval of a pair's L1 distance and the pads.  The derivation is DESIGN s4, "K22".
+// The integer SAD filter of the L1 measures (CMVE_PW_L1, fp64 score words: l1 / l1_norm) -- the pieces its kernels
+// share (K22, l1_filter.hip: the count pass; K23, l1_topk.hip: the witness / candidate passes of the top-k): the grid
+// both sets are quantised on, the tiled order of the uint16 codes, the pads, one 128 x 128 tile of SADs (l1f_sad_tile)
+// and the interval of a pair's L1 distance.  The derivation is DESIGN s4, "K22".
 //   codes  a row's elements as q_k = clamp(rint((x_k - lo) / s), 0, 65535) on ONE grid (lo, s) for both sets; two
 //          codes to a dword, stored [row tile of 128][K tile of 32 elements][16 code dwords][128 rows]: a (row tile,
 //          K tile) block is 8 KiB that the main kernel copies to LDS as it lies, and the 8 rows a thread owns of one
@@ -59,6 +60,69 @@ __device__ __forceinline__ void l1f_interval(uint32_t sad, double s, double ea, 
   const bool ok = hi < lim;  // false for NaN and +inf
   dlo = ok ? m - W : (double)NAN;
   dhi = ok ? hi : (double)NAN;
+}
+
+// thread (ty, tx) = (tid >> 4, tid & 15) of a tile's 256 owns the A rows l1f_row(ty, u) and the B rows l1f_row(tx, v) of
+// the tile, u, v < 8: two runs of four consecutive rows 64 apart -- a 16-lane group's ds_read_b128 of a run covers 256
+// contiguous bytes
+__device__ __forceinline__ int l1f_row(int t, int u) { return (u >> 2) * 64 + t * 4 + (u & 3); }
+
+// The SADs of one tile, 256 threads of 8 x 8 u32 accumulators: 32-element K tiles double-buffered in smem (L1F_SMEM
+// bytes, 16-byte aligned; register staged, a straight copy of the packed blocks -- k-major, so a thread's 8 rows of a
+// code dword are two ds_read_b128).  a_blk / b_blk: the first (row tile, K tile) block of the tile's A rows / B rows in
+// the tiled codes; the nkt (>= 1) blocks of either side follow one another.  On return acc[u][v] is the SAD of the pair
+// (A row l1f_row(ty, u), B row l1f_row(tx, v)) of the tile, and every wave has passed the loop's last barrier: smem is
+// free.  The blocks are read whole: the row tiles must lie below the sets' n_pad (a multiple of 128; cmve_l1_pack_size).
+__device__ __forceinline__ void l1f_sad_tile(const uint32_t* __restrict__ a_blk, const uint32_t* __restrict__ b_blk,
+                                             int nkt, char* smem, uint32_t (&acc)[8][8]) {
+  const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+#pragma unroll
+  for (int u = 0; u < 8; ++u)
+#pragma unroll
+    for (int v = 0; v < 8; ++v) acc[u][v] = 0u;
+  constexpr int Q = L1F_TILE_DW / 4;  // 16-byte pieces of a block: two per thread
+  const l2f_u32x4* ga = (const l2f_u32x4*)a_blk + tid;
+  const l2f_u32x4* gb = (const l2f_u32x4*)b_blk + tid;
+  l2f_u32x4 ra[2], rb[2];
+#define L1F_LOAD(kt)                       \
+  {                                        \
+    ra[0] = ga[(int64_t)(kt) * Q];         \
+    ra[1] = ga[(int64_t)(kt) * Q + 256];   \
+    rb[0] = gb[(int64_t)(kt) * Q];         \
+    rb[1] = gb[(int64_t)(kt) * Q + 256];   \
+  }
+#define L1F_WRITE(buf)                                    \
+  {                                                       \
+    char* w_ = smem + (buf) * L1F_STAGE + tid * 16;       \
+    *(l2f_u32x4*)(w_) = ra[0];                            \
+    *(l2f_u32x4*)(w_ + 4096) = ra[1];                     \
+    *(l2f_u32x4*)(w_ + L1F_TILE_DW * 4) = rb[0];          \
+    *(l2f_u32x4*)(w_ + L1F_TILE_DW * 4 + 4096) = rb[1];   \
+  }
+  L1F_LOAD(0)
+  L1F_WRITE(0)
+  __syncthreads();
+  for (int kt = 0; kt < nkt; ++kt) {
+    const int buf = kt & 1;
+    if (kt + 1 < nkt) L1F_LOAD(kt + 1)
+    const char* pa = smem + buf * L1F_STAGE + ty * 16;
+    const char* pb = smem + buf * L1F_STAGE + L1F_TILE_DW * 4 + tx * 16;
+#pragma unroll 2
+    for (int kd = 0; kd < L1F_KD; ++kd) {
+      const l2f_u32x4 a0 = *(const l2f_u32x4*)(pa + kd * 512), a1 = *(const l2f_u32x4*)(pa + kd * 512 + 256);
+      const l2f_u32x4 b0 = *(const l2f_u32x4*)(pb + kd * 512), b1 = *(const l2f_u32x4*)(pb + kd * 512 + 256);
+      const uint32_t av[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
+      const uint32_t bv[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
+#pragma unroll
+      for (int u = 0; u < 8; ++u)
+#pragma unroll
+        for (int v = 0; v < 8; ++v) acc[u][v] = __builtin_amdgcn_sad_u16(av[u], bv[v], acc[u][v]);
+    }
+    if (kt + 1 < nkt) L1F_WRITE(buf ^ 1)
+    __syncthreads();
+  }
+#undef L1F_LOAD
+#undef L1F_WRITE
 }
 
 }  // namespace cmve

@@ -61,6 +61,17 @@ static inline int l2f_check_sets(const char* name, const cmve_rows_t* a, const c
   return CMVE_OK;
 }
 
+// the raw rows of both sides, the operands of every canonical score: what a filtered count (filter_count.h) and a
+// filtered top-k (topk_filter_tile.h) hand the launches that re-score on the canonical chain
+struct FltRows {
+  const void* A;
+  int32_t a_dtype;
+  int64_t lda, na;
+  const void* B;
+  int32_t b_dtype;
+  int64_t ldb, nb, d;
+};
+
 // The epilogues' side load of one tile row as l2f_interval takes it: the row's norm (from 1 / inv_norm) and its error
 // (err_h16 + theta); NaN for a row beyond the set (no interval: its pairs are never decided)
 __device__ __forceinline__ double l2f_side_norm(int64_t row, bool valid, const double* inv_norm) {

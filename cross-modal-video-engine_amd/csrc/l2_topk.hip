@@ -19,8 +19,10 @@
 // so out_idx / out_err are, word for word, cmve_pairwise_topk's.  A query whose list overflows, or that has no
 // threshold, gets out_idx[i, 0] = -2: the caller finishes it on the fp64 route.  Plain vector stores and integer
 // atomics only; the queries are taken L2T_QC at a time so that the workspace has no n_q x n_g term.
-// Launches A' and C, the sample, the layout and the parameter checks are topk_filter_tile.h's, shared with K23
-// (l1_topk.hip).
+// This file holds what is this filter's alone: the pass kernel's argument block, its interval and thread layout, and
+// the entry's checks of its own operands.  The tail of the epilogue, launches A' and C, the sample, the layout, the
+// parameter checks and the host body (l2t_topk_run: checks, workspace, the rounds of four launches) are
+// topk_filter_tile.h's, shared with K23 (l1_topk.hip).
 #include "topk_filter_tile.h"
 
 namespace cmve {
@@ -76,14 +78,7 @@ __global__ __launch_bounds__(256, 2) void l2t_pass_kernel(L2tArgs a) {
     const bool v = i < a.q_end;
     E.qn[tid] = l2f_side_norm(i, v, a.q_inv);
     E.qe[tid] = l2f_side_err(i, v, a.q_err, a.c.theta);
-    if (MODE == 1) {
-      E.thr[tid] = v ? a.thr[i - a.q0] : (double)NAN;
-      // An overflowed list is lost (launch C asks only whether the counter exceeds cap), so its row stops appending:
-      // rows clustered far from the origin -- every pair a candidate -- would otherwise serialise n_g atomics on
-      // one address per query.  Read once per tile, off the pairs' path; the counter only grows, so a tile that
-      // reads it early merely adds its own <= 128 candidates more.
-      E.full[tid] = v ? __hip_atomic_load(a.cnt + (i - a.q0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > a.cap : 1;
-    }
+    l2t_row_state<MODE>(a, E, tid, i, v);
   } else {
     const int t = tid - L2F_BM;
     const int64_t j = j0 + t;
@@ -112,34 +107,10 @@ __global__ __launch_bounds__(256, 2) void l2t_pass_kernel(L2tArgs a) {
         if (i >= a.q_end || j >= a.ng) continue;
         double dlo, dhi;
         l2f_interval(acc[m][n][r], qn, qe, E.gn[col], E.ge[col], a.c.gamma, a.c.kappa, dlo, dhi);
-        if (MODE == 0) {
-          // key = s D: its upper bound is dhi (alpha > 0) or -dlo (alpha < 0); NaN (no interval) becomes +inf
-          a.ub[(i - a.q0) * a.ub_ld + j] = l2t_f32_up(pos ? dhi : -dlo);
-        } else if (thr == thr) {
-          // excluded only on a positive test: D is provably beyond the threshold (a NaN interval fails it)
-          const bool out = pos ? dlo > thr : dhi < thr;
-          if (out) {
-            ++n_excl;
-          } else {
-            ++n_cand;
-            if (!full) {
-              const int64_t li = i - a.q0;
-              const int32_t p = gadd(a.cnt + li, (int32_t)1);
-              if (p < a.cap) a.list[li * a.cap + p] = (int32_t)j;
-            }
-          }
-        }
+        l2t_pair<MODE>(a, pos, i, j, dlo, dhi, thr, full, n_cand, n_excl);
       }
     }
-  if (MODE == 1) {
-    if (n_cand) atomicAdd(&E.n_cand, n_cand);
-    if (n_excl) atomicAdd(&E.n_excl, n_excl);
-    __syncthreads();
-    if (tid == 0) {
-      if (E.n_excl) gadd(a.stats + 0, (l2f_u64)E.n_excl);
-      if (E.n_cand) gadd(a.stats + 1, (l2f_u64)E.n_cand);
-    }
-  }
+  l2t_flush<MODE>(a, E, tid, n_cand, n_excl);
 }
 
 }  // namespace
@@ -161,59 +132,18 @@ extern "C" int cmve_l2_topk_workspace(const cmve_rows_t* q, const cmve_rows_t* g
 extern "C" int cmve_l2_topk(cmve_handle_t h, const cmve_rows_t* q, const cmve_rows_t* g, double alpha, double beta,
                             int32_t k, int64_t cand_cap, int64_t sample_rows, void* ws, int64_t ws_bytes,
                             int64_t* out_idx, double* out_err, int64_t* stats) {
-  CMVE_REQUIRE(h && q && g && stats, "cmve_l2_topk: NULL argument");
-  CMVE_REQUIRE(alpha != 0.0 && std::isfinite(alpha) && std::isfinite(beta),
-               "cmve_l2_topk: alpha must be finite and non-zero, beta finite (%g, %g)", alpha, beta);
-  if (int rc = l2t_check_params("cmve_l2_topk", k, cand_cap, sample_rows)) return rc;
-  if (int rc = l2f_check_sets("cmve_l2_topk", q, g)) return rc;
-  const int64_t n_q = q->n, n_g = g->n, d = q->d;
-  CMVE_REQUIRE(k <= n_g || n_q == 0, "cmve_l2_topk: k exceeds the gallery (%d > %lld): clamp it", k, (long long)n_g);
-  CMVE_REQUIRE((out_idx && out_err) || !n_q, "cmve_l2_topk: NULL output");
-  const L2tLayout l = l2t_layout(n_q, n_g, k, cand_cap, sample_rows);
-  CMVE_REQUIRE(n_q == 0 || (ws && ws_bytes >= l.bytes), "cmve_l2_topk: workspace too small (%lld < %lld bytes)",
-               (long long)ws_bytes, (long long)l.bytes);
-  CMVE_REQUIRE((((uintptr_t)ws) & 7) == 0, "cmve_l2_topk: workspace must be 8-byte aligned");
-  const hipStream_t st = h->stream;
-  CMVE_HIP(hipMemsetAsync(stats, 0, 4 * sizeof(int64_t), st));
-  if (n_q == 0) return CMVE_OK;
-  L2tArgs a;
-  a.q16 = q->h16;
-  a.g16 = g->h16;
-  a.q_inv = q->inv_norm;
-  a.g_inv = g->inv_norm;
-  a.q_err = q->err_h16;
-  a.g_err = g->err_h16;
-  a.d_pad = q->d_pad;
-  a.alpha = alpha;
-  a.c = l2f_consts(d, q->d_pad);
-  a.ub = (float*)((char*)ws + l.ub);
-  a.ub_ld = l.ub_ld;
-  double* thr = (double*)((char*)ws + l.thr);
-  a.thr = thr;
-  a.cnt = (int32_t*)((char*)ws + l.cnt);
-  a.list = (int32_t*)((char*)ws + l.list);
-  a.cap = cand_cap;
-  a.stats = (l2f_u64*)stats;
-  const int64_t tiles_s = (l.s + L2F_BN - 1) / L2F_BN, tiles_g = (n_g + L2F_BN - 1) / L2F_BN;
-  for (int64_t q0 = 0; q0 < n_q; q0 += l.qc) {
-    const int64_t nq = std::min(l.qc, n_q - q0);
-    a.q0 = q0;
-    a.q_end = q0 + nq;
-    a.tiles_a = (int)((nq + L2F_BM - 1) / L2F_BM);  // <= 8: tiles_a * tiles_g < 2^31
-    a.ng = l.s;
-    a.tiles_b = (int)tiles_s;
-    hipLaunchKernelGGL(l2t_pass_kernel<0>, dim3((unsigned)(a.tiles_a * tiles_s)), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(l2t_threshold_kernel<true>, dim3((unsigned)nq), dim3(256), 0, st, (const float*)a.ub, a.ub_ld, l.s,
-                       (int)k, alpha, beta, a.c.rho, thr, a.cnt);
-    a.ng = n_g;
-    a.tiles_b = (int)tiles_g;
-    hipLaunchKernelGGL(l2t_pass_kernel<1>, dim3((unsigned)(a.tiles_a * tiles_g)), dim3(256), 0, st, a);
-    PWR_TYPES(q->raw_dtype, g->raw_dtype, TA, TB, {
-      hipLaunchKernelGGL((l2t_finish_kernel<CMVE_PW_L2, TA, TB>), dim3((unsigned)nq), dim3(256), 0, st, (const TA*)q->raw,
-                         q->raw_ld, (const TB*)g->raw, g->raw_ld, d, alpha, beta, q0, (const double*)thr,
-                         (const int32_t*)a.cnt, (const int32_t*)a.list, cand_cap, (int)k, out_idx, out_err, a.stats);
-    })
-    if (int rc = check_launch("l2_topk")) return rc;
-  }
-  return CMVE_OK;
+  const char* name = "cmve_l2_topk";
+  CMVE_REQUIRE(h && q && g && stats, "%s: NULL argument", name);
+  const L2fConsts c = l2f_consts(q->d, q->d_pad);
+  auto own_checks = [&]() -> int { return l2f_check_sets(name, q, g); };
+  auto pass_launch = [&](int mode, hipStream_t st, const L2tRound& r, const L2tWs& w) {
+    const L2tArgs a{q->h16, g->h16, q->inv_norm, g->inv_norm, q->err_h16, g->err_h16, r.q0, r.q_end, r.ng, q->d_pad,
+                    alpha, c, w.ub, w.ub_ld, w.thr, w.cnt, w.list, w.cap, w.stats, r.tiles_a, r.tiles_b};
+    hipLaunchKernelGGL(mode == 0 ? l2t_pass_kernel<0> : l2t_pass_kernel<1>, dim3((unsigned)(r.tiles_a * r.tiles_b)),
+                       dim3(256), 0, st, a);
+  };
+  return l2t_topk_run<CMVE_PW_L2>(name, "l2_topk", h, FltRows{q->raw, q->raw_dtype, q->raw_ld, q->n, g->raw,
+                                                                g->raw_dtype, g->raw_ld, g->n, q->d},
+                                  alpha, beta, k, cand_cap, sample_rows, ws, ws_bytes, out_idx, out_err, stats, c.rho,
+                                  own_checks, pass_launch);
 }

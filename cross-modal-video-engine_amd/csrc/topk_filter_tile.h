@@ -1,8 +1,15 @@
 // What the two filtered top-k entries share (K20: l2_topk.hip, the MFMA filter of CMVE_PW_L2; K23: l1_topk.hip, the SAD
-// filter of CMVE_PW_L1), whatever brackets a pair's key: the stored upper bounds' rounding, launch A' (radix select of
-// the k-th smallest bound and its widening to a threshold that is strict on the canonical words), launch C (re-score,
-// sort, emit), the sample, the workspace layout and the checks of k / cand_cap / sample_rows.  A filter supplies its
-// own pass kernel (launches A and B).  The derivations are DESIGN s4, "K20" and "K23".
+// filter of CMVE_PW_L1), whatever brackets a pair's key:
+//   l2t_f32_up, l2t_row_state, l2t_pair, l2t_flush   the tail of a pass kernel's epilogue once it holds a pair's
+//                          interval: the stored upper bounds' rounding, the row's threshold and overflow flag, "launch
+//                          A stores the bound, launch B excludes or appends", the two counters
+//   l2t_threshold_kernel   launch A': radix select of the k-th smallest bound, widened to a threshold that is strict
+//                          on the canonical words
+//   l2t_finish_kernel      launch C: re-score, sort, emit
+//   l2t_sample, l2t_layout, l2t_check_params   the sample, the workspace and the checks of k / cand_cap / sample_rows
+//   l2t_topk_run           the host body: checks, memset, the rounds of four launches
+// A filter supplies its operands' checks, its pass kernel (tile, interval, thread layout) and the launch of it.  The
+// derivations are DESIGN s4, "K20" and "K23".
 #ifndef CMVE_TOPK_FILTER_TILE_H
 #define CMVE_TOPK_FILTER_TILE_H
 #include "l2_filter_tile.h"
@@ -21,6 +28,63 @@ __device__ __forceinline__ float l2t_f32_up(double x) {
     f = f > 0.f ? __uint_as_float(b + 1) : f < 0.f ? __uint_as_float(b - 1) : 1.17549435e-38f;
   }
   return f;
+}
+
+// ---- the common tail of the two pass kernels' epilogues.  MODE 0: launch A (the witnesses' bounds), MODE 1: launch B
+// (the candidates).  `Args` is the kernel's own flat argument block (L2tArgs, L1tArgs): it names q0, thr, cnt, cap, ub,
+// ub_ld, list and stats; `Epi` its epilogue LDS: it names thr[128] and full[128] by tile row, and n_cand and n_excl,
+// zeroed before the pairs.  (The helpers take a, E and the global row i whole: handed `double& thr`, `int& full` or
+// i - a.q0 instead, l2t_pass_kernel<1> compiles to another instruction stream; as they are, K20's two kernels keep
+// the streams they had with the statements written out.)
+
+// query row i (thread tid's row of the tile; `valid`: it exists) into the tile's LDS: its threshold, and whether its
+// list had overflowed when this tile began.  An overflowed list is lost (launch C asks only whether the counter exceeds cap), so
+// its row stops appending: rows clustered far from the origin -- every pair a candidate -- would otherwise serialise
+// n_g atomics on one address per query.  Read once per row and tile, off the pairs' path; the counter only grows, so a
+// tile that reads it early merely adds its own <= 128 candidates more.
+template <int MODE, typename Args, typename Epi>
+__device__ __forceinline__ void l2t_row_state(const Args& a, Epi& E, int tid, int64_t i, bool valid) {
+  if (MODE == 1) {
+    E.thr[tid] = valid ? a.thr[i - a.q0] : (double)NAN;
+    E.full[tid] = valid ? __hip_atomic_load(a.cnt + (i - a.q0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > a.cap : 1;
+  }
+}
+
+// one pair (query i, column j) whose distance lies in [dlo, dhi] (NaN, NaN: no interval); pos: alpha > 0
+template <int MODE, typename Args>
+__device__ __forceinline__ void l2t_pair(const Args& a, bool pos, int64_t i, int64_t j, double dlo, double dhi,
+                                         double thr, bool full, int& n_cand, int& n_excl) {
+  if (MODE == 0) {
+    // key = s D: its upper bound is dhi (alpha > 0) or -dlo (alpha < 0); NaN (no interval) becomes +inf
+    a.ub[(i - a.q0) * a.ub_ld + j] = l2t_f32_up(pos ? dhi : -dlo);
+  } else if (thr == thr) {
+    // excluded only on a positive test: D is provably beyond the threshold (a NaN interval fails it)
+    const bool out = pos ? dlo > thr : dhi < thr;
+    if (out) {
+      ++n_excl;
+    } else {
+      ++n_cand;
+      if (!full) {
+        const int64_t li = i - a.q0;
+        const int32_t p = gadd(a.cnt + li, (int32_t)1);
+        if (p < a.cap) a.list[li * a.cap + p] = (int32_t)j;
+      }
+    }
+  }
+}
+
+// the thread's counts through the block's LDS words into stats[0..1]: two integer atomics per tile
+template <int MODE, typename Args, typename Epi>
+__device__ __forceinline__ void l2t_flush(const Args& a, Epi& E, int tid, int n_cand, int n_excl) {
+  if (MODE == 1) {
+    if (n_cand) atomicAdd(&E.n_cand, n_cand);
+    if (n_excl) atomicAdd(&E.n_excl, n_excl);
+    __syncthreads();
+    if (tid == 0) {
+      if (E.n_excl) gadd(a.stats + 0, (l2f_u64)E.n_excl);
+      if (E.n_cand) gadd(a.stats + 1, (l2f_u64)E.n_cand);
+    }
+  }
 }
 
 // The witnesses' bound tau (key space: k distinct columns have s D <= tau) -> the distance-space threshold of launch
@@ -209,6 +273,70 @@ static inline int l2t_check_params(const char* name, int32_t k, int64_t cand_cap
                L2T_CAND_MAX, (long long)cand_cap, k);
   CMVE_REQUIRE(sample_rows >= 0 && sample_rows < (1ll << 31), "%s: bad sample_rows (%lld)", name,
                (long long)sample_rows);
+  return CMVE_OK;
+}
+
+// ---- the host body -------------------------------------------------------------------------------------------------------
+// what l2t_topk_run hands a filter's pass launch beside the filter's own operands: the workspace carved up (the same
+// for every round) and one pass of one round.  The pass kernels keep their flat argument blocks (L2tArgs, L1tArgs) and
+// are filled from these: an embedded struct moves a kernel's scalar loads (filter_count.h).
+struct L2tWs {
+  float* ub;       // [qc][ub_ld] upper key bounds
+  int64_t ub_ld;
+  double* thr;     // per query of the round: the distance-space threshold
+  int32_t* cnt;    // per query of the round: candidates found
+  int32_t* list;   // [qc][cap] column ids
+  int64_t cap;
+  l2f_u64* stats;  // {pairs excluded, candidates found, candidates re-scored, unresolved queries}
+};
+struct L2tRound {
+  int64_t q0, q_end;  // this round's queries; q0 is a multiple of 128
+  int64_t ng;         // columns of this pass: the sample (launch A) or the gallery (launch B)
+  int tiles_a, tiles_b;
+};
+
+// One filtered top-k on h's stream.  `name`: the entry (refusals), `label`: check_launch's; METRIC: CMVE_PW_L2 (the
+// keys are squared distances) or CMVE_PW_L1; r: the raw rows (q is A, the gallery B); rho: the canonical chain's
+// relative slack in distance space; own_checks(): the entry's checks of its own operands, run where they always ran
+// (after the scaling and the parameters, before k against the gallery); pass_launch(mode, st, round, ws): the
+// filter's pass kernel, MODE = mode, over round.tiles_a x round.tiles_b blocks of 256 threads.
+template <int METRIC, typename Own, typename Pass>
+static inline int l2t_topk_run(const char* name, const char* label, cmve_handle_t h, const FltRows& r, double alpha,
+                               double beta, int32_t k, int64_t cand_cap, int64_t sample_rows, void* ws,
+                               int64_t ws_bytes, int64_t* out_idx, double* out_err, int64_t* stats, double rho,
+                               Own own_checks, Pass pass_launch) {
+  CMVE_REQUIRE(alpha != 0.0 && std::isfinite(alpha) && std::isfinite(beta),
+               "%s: alpha must be finite and non-zero, beta finite (%g, %g)", name, alpha, beta);
+  if (int rc = l2t_check_params(name, k, cand_cap, sample_rows)) return rc;
+  if (int rc = own_checks()) return rc;
+  const int64_t n_q = r.na, n_g = r.nb;
+  CMVE_REQUIRE(k <= n_g || n_q == 0, "%s: k exceeds the gallery (%d > %lld): clamp it", name, k, (long long)n_g);
+  CMVE_REQUIRE((out_idx && out_err) || !n_q, "%s: NULL output", name);
+  const L2tLayout l = l2t_layout(n_q, n_g, k, cand_cap, sample_rows);
+  CMVE_REQUIRE(n_q == 0 || (ws && ws_bytes >= l.bytes), "%s: workspace too small (%lld < %lld bytes)", name,
+               (long long)ws_bytes, (long long)l.bytes);
+  CMVE_REQUIRE((((uintptr_t)ws) & 7) == 0, "%s: workspace must be 8-byte aligned", name);
+  const hipStream_t st = h->stream;
+  CMVE_HIP(hipMemsetAsync(stats, 0, 4 * sizeof(int64_t), st));
+  if (n_q == 0) return CMVE_OK;
+  char* base = (char*)ws;
+  const L2tWs w{(float*)(base + l.ub), l.ub_ld, (double*)(base + l.thr), (int32_t*)(base + l.cnt),
+                (int32_t*)(base + l.list), cand_cap, (l2f_u64*)stats};
+  const int tiles_s = (int)((l.s + L2F_BN - 1) / L2F_BN), tiles_g = (int)((n_g + L2F_BN - 1) / L2F_BN);
+  for (int64_t q0 = 0; q0 < n_q; q0 += l.qc) {
+    const int64_t nq = std::min(l.qc, n_q - q0);
+    const int tiles_a = (int)((nq + L2F_BM - 1) / L2F_BM);  // <= 8: tiles_a * tiles_g < 2^31
+    pass_launch(0, st, L2tRound{q0, q0 + nq, l.s, tiles_a, tiles_s}, w);
+    hipLaunchKernelGGL(l2t_threshold_kernel<METRIC == CMVE_PW_L2>, dim3((unsigned)nq), dim3(256), 0, st,
+                       (const float*)w.ub, w.ub_ld, l.s, (int)k, alpha, beta, rho, w.thr, w.cnt);
+    pass_launch(1, st, L2tRound{q0, q0 + nq, n_g, tiles_a, tiles_g}, w);
+    PWR_TYPES(r.a_dtype, r.b_dtype, TA, TB, {
+      hipLaunchKernelGGL((l2t_finish_kernel<METRIC, TA, TB>), dim3((unsigned)nq), dim3(256), 0, st, (const TA*)r.A,
+                         r.lda, (const TB*)r.B, r.ldb, r.d, alpha, beta, q0, (const double*)w.thr,
+                         (const int32_t*)w.cnt, (const int32_t*)w.list, w.cap, (int)k, out_idx, out_err, w.stats);
+    })
+    if (int rc = check_launch(label)) return rc;
+  }
   return CMVE_OK;
 }
 

@@ -165,6 +165,24 @@ def test_small_and_edge_shapes(adversarial):
             _same(_topk(q[rows], g, *ab, 10, filter=True), _topk(q[rows], g, *ab, 10, filter=False))
 
 
+def test_two_rounds():
+    """More than 1024 queries: the host body's second round of four launches (query 1024 is tile 8 of the packed
+    planes), which K23's route shares."""
+    rng = np.random.default_rng(26)
+    n_q, n_g, d = 1025, 130, 8
+    g = rng.standard_normal((n_g, d))
+    q = rng.standard_normal((n_q, d))
+    for ab in ((1.0, 0.0), (-1.0 / d, -1.0)):
+        got = _topk(q, g, *ab, 3, filter=True, return_stats=True)
+        _same(got[:2], _topk(q, g, *ab, 3, filter=False))
+        st = got[2]
+        print("two rounds, alpha %g: %s" % (ab[0], st))
+        # 130 columns are below cand_cap: no list overflows, every pair of a resolved query is excluded or a candidate
+        assert st["excluded"] + st["candidates"] == (n_q - st["unresolved"]) * n_g
+        one = _topk(q[77:78], g, *ab, 3, filter=True)
+        _same(one, (got[0][77:78], got[1][77:78]))
+
+
 # ---- 4. the fallback is exact and says so --------------------------------------------------------------------------------
 
 def test_fallback_is_exact_and_says_so(adversarial):
