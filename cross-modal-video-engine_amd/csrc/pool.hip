@@ -30,7 +30,8 @@ __global__ __launch_bounds__(256) void collate_kernel(const float* __restrict__ 
   if (blockIdx.x == 0)
     for (int t = threadIdx.x; t < t_max; t += 256) mask[b * t_max + t] = t < keep ? 1.f : 0.f;
   if (f0 >= F) return;
-  const bool vec = (f0 + 4 <= F) && ((ldf & 3) == 0) && ((F & 3) == 0);
+  // float4 loads need a 16-byte aligned base as well as a 4-multiple row stride
+  const bool vec = (f0 + 4 <= F) && ((ldf & 3) == 0) && ((F & 3) == 0) && (((uintptr_t)frames & 15) == 0);
   float acc[4] = {0.f, 0.f, 0.f, 0.f};
   for (int64_t t = 0; t < T; ++t) {
     const float* src = frames + (r0 + t) * ldf + f0;
@@ -70,7 +71,9 @@ __global__ __launch_bounds__(256) void pool_kernel(const float* __restrict__ x, 
   const int64_t f0 = (int64_t)blockIdx.x * 256 + lane * 4;
   const int64_t len = lengths ? (int64_t)lengths[b] : T;
   const int64_t tend = (MODE == 0) ? (len < T ? len : T) : T;  // MEAN_VALID stops at len
-  const bool vec = (f0 + 4 <= F) && ((st & 3) == 0) && ((sb & 3) == 0) && ((F & 3) == 0);
+  // float4 loads need a 16-byte aligned base as well as 4-multiple strides (a view may start mid-row)
+  const bool vec = (f0 + 4 <= F) && ((st & 3) == 0) && ((sb & 3) == 0) && ((F & 3) == 0) &&
+                   (((uintptr_t)x & 15) == 0);
   float acc[4];
   for (int e = 0; e < 4; ++e) acc[e] = (MODE >= 2) ? -INFINITY : 0.f;
   if (f0 < F) {
