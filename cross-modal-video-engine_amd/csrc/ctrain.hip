@@ -24,7 +24,7 @@ __global__ __launch_bounds__(256) void act_fwd_kernel(const float* __restrict__ 
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
     const float v = x[i];
     float r;
-    if (kind == 0) r = v > 0.f ? v : 0.f;
+    if (kind == 0) r = v <= 0.f ? 0.f : v;  // torch.relu: a NaN passes (NaN <= 0 is false)
     else if (kind == 1) r = sigm(v);
     else r = v * sigm(1.702f * v);
     y[i] = r;
@@ -37,7 +37,7 @@ __global__ __launch_bounds__(256) void act_bwd_kernel(const float* __restrict__ 
     const float v = x[i], g = dy[i];
     float r;
     if (kind == 0) {
-      r = v > 0.f ? g : 0.f;  // torch's threshold_backward: 0 at v == 0
+      r = v <= 0.f ? 0.f : g;  // torch's threshold_backward (x <= 0 ? 0 : grad): 0 at v == 0, grad at a NaN
     } else if (kind == 1) {
       const float s = sigm(v);
       r = g * (1.f - s) * s;  // sigmoid_backward: grad * (1 - y) * y
@@ -218,6 +218,10 @@ __global__ __launch_bounds__(256) void combine_fwd_kernel(const float* __restric
                                                           float* __restrict__ out) {
   const int64_t n = B * d;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    // every product and sum rounded on its own: the parenthesisation is the contract, as torch's eager ops and
+    // fuse_combine_kernel evaluate it (left to the default, the compiler contracted both products into fmas here
+    // and into neither there; HIP's __fmul_rn / __fadd_rn are plain operators and contract just the same)
+#pragma clang fp contract(off)
     const float s = ds[i / d];
     out[i] = ((y[i] + s * text[i]) + (1.f - s) * ref[i]) + based[i];
   }

@@ -429,6 +429,8 @@ __global__ __launch_bounds__(256) void fuse_combine_kernel(const float* __restri
   const float s1 = 1.f - s;
   double ss = 0.0;
   for (int64_t k = lane; k < d; k += 64) {
+    // each product and sum rounded on its own: the parenthesisation is the contract (never an fma)
+#pragma clang fp contract(off)
     const int64_t i = row * d + k;
     const float v = ((y[i] + s * text[i]) + s1 * ref[i]) + fmaxf(based[i], 0.f);  // based = relu(block out)
     out[i] = v;
@@ -621,6 +623,8 @@ extern "C" int cmve_mha_1q(cmve_handle_t h, const float* q, int64_t ldq, const f
   CMVE_REQUIRE(B > 0 && T > 0 && H > 0 && dh > 0 && ldq >= (int64_t)H * dh && ldo >= (int64_t)H * dh,
                "cmve_mha_1q: bad shape");
   const int64_t d = (int64_t)H * dh;
+  // as cmve_mha_1q_bwd: V lies after K in a row that holds both (a short ldkv would read across rows)
+  CMVE_REQUIRE(v_off >= d && ldkv >= v_off + d, "cmve_mha_1q: v_off >= H*dh and ldkv >= v_off + H*dh");
   const int E = (int)(d / 64);
   const int lph = (d % 64 == 0 && E > 0 && dh % E == 0) ? dh / E : 0;
   const size_t lds_rows = sizeof(float) * ((size_t)H * T + 4 * (size_t)d);
@@ -693,6 +697,7 @@ extern "C" int cmve_mha_absorbed(cmve_handle_t h, const float* y, int64_t ldy, i
 extern "C" int cmve_fuse_combine(cmve_handle_t h, const float* y, const float* ds, const float* text, const float* ref,
                                  const float* based, int64_t n, int64_t d, double eps, float* out) {
   CMVE_REQUIRE(h && y && ds && text && ref && based && out, "cmve_fuse_combine: NULL argument");
+  CMVE_REQUIRE(n >= 0 && d > 0, "cmve_fuse_combine: bad shape (n >= 0, d > 0)");
   if (n == 0) return CMVE_OK;
   hipLaunchKernelGGL(fuse_combine_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, h->stream, y, ds, text, ref,
                      based, n, d, eps, out);

@@ -184,7 +184,11 @@ int cmve_adaptive_avg_pool2d(cmve_handle_t h, const float* x, int64_t P, int64_t
  *   cmve_mha_1q: one query per batch element b (q [B, H*dh]) over T keys whose projected K/V rows
  *     are row t*B + b of kv (K at column 0, V at column v_off): the raw p_s_m.reshape(l*f, b, d)
  *     of combiner.py:164-165, which mixes batch rows -- reproduced, not fixed.  Scaled by dh^-0.5.
+ *     Requires B, T, H, dh > 0, ldq and ldo >= H*dh, v_off >= H*dh and ldkv >= v_off + H*dh (V after K
+ *     within one row; the same rule as cmve_mha_1q_bwd), else CMVE_E_INVALID.
  *   cmve_fuse_combine: out = normalize(((y + ds*text) + (1-ds)*ref) + relu(based), eps)  (combiner.py:166,178-180)
+ *     on contiguous [n, d] operands, ds [n]; the norm is clamped at eps (a zero row gives zeros).
+ *     Requires n >= 0 and d > 0, else CMVE_E_INVALID before any launch; n = 0 writes nothing.
  */
 int cmve_layernorm(cmve_handle_t h, const float* x, int64_t ldx, int64_t n, int64_t d,
                    const float* gamma, const float* beta, double eps, float* y, int64_t ldy);
