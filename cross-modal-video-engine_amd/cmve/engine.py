@@ -122,6 +122,7 @@ class RowSet:
         self.device = device
         self.raw = raw
         self.n, self.d, self.n_pad, self.d_pad = n, d, n_pad, d_pad
+        self.raw_ld = _pw_ld(raw)  # not stride(0): a one-row tensor may carry any, 0 for a [None, :] view
         self.eps = float(eps)
         self.hi = torch.empty((n_pad, d_pad), dtype=torch.int16, device=device)
         self.lo = torch.empty((n_pad, d_pad), dtype=torch.int16, device=device) if with_lo else None
@@ -134,7 +135,7 @@ class RowSet:
         self.desc = Rows(n=n, d=d, n_pad=n_pad, d_pad=d_pad, hi=self.hi.data_ptr(),
                          lo=self.lo.data_ptr() if self.lo is not None else None,
                          raw=raw.data_ptr() if n else None, raw_dtype=_dtype_code(raw), flags=_lib.PACK_RAW if raw_rows else 0,
-                         raw_ld=raw.stride(0) if n else d, inv_norm=self.inv_norm.data_ptr(),
+                         raw_ld=self.raw_ld, inv_norm=self.inv_norm.data_ptr(),
                          err_hi=self.err_hi.data_ptr(), err_hilo=self.err_hilo.data_ptr(),
                          err_max=self.err_max.data_ptr(), eps=self.eps,
                          h16=self.h16.data_ptr() if with_f16 else None,
@@ -163,7 +164,7 @@ class RowSet:
         """x / max(||x||, eps) on device (K1')."""
         out = torch.empty((self.n, self.d), dtype=dtype, device=self.device)
         if self.n:
-            check(lib.cmve_l2norm_rows(handle(self.device), _ptr(self.raw), _dtype_code(self.raw), self.raw.stride(0),
+            check(lib.cmve_l2norm_rows(handle(self.device), _ptr(self.raw), _dtype_code(self.raw), self.raw_ld,
                                        _ptr(out), _dtype_code(out), out.stride(0), self.n, self.d, self.eps),
                   "cmve_l2norm_rows")
         return out
@@ -328,7 +329,8 @@ def _pw_rows(x, name: str) -> torch.Tensor:
 
 
 def _pw_ld(t: torch.Tensor) -> int:
-    """Row stride of a pairwise operand (torch leaves the stride of a one-row tensor's row dimension arbitrary)."""
+    """Leading dimension of a [n, d] operand with contiguous rows (torch leaves the stride of a one-row tensor's row
+    dimension arbitrary): RowSet's raw rows, RankSession's bound rows and the pairwise operands."""
     return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
 
 
@@ -1283,7 +1285,7 @@ class RankSession:
             rs.raw.copy_(src_t, non_blocking=True)
             src = rs.raw
         rs.desc.raw = src.data_ptr()
-        rs.desc.raw_ld = src.stride(0)
+        rs.desc.raw_ld = _pw_ld(src)
         return src
 
     def enqueue(self, captions, videos, timing_slot: int = -1, out: Optional[torch.Tensor] = None,

@@ -566,7 +566,9 @@ int cmve_gt_positions_from_matrix(cmve_handle_t h, const void* errors, int32_t d
  * block per query selects T~_k among the candidates, keeps the band
  * s~ >= T~_k - 2E (at most 4096 columns), re-scores it in fp64 and sorts it
  * (score desc, index asc).  out_idx [q->n, k] int32, out_score [q->n, k] fp64
- * (the exact cosine).  *overflow (device int32) becomes non-zero if a query's
+ * (the exact cosine; -inf at a column whose cosine is NaN -- a zero row at eps = 0 --
+ * which sorts after every number, in index order; idx -1 / score NaN past the
+ * gallery when k > g->n).  *overflow (device int32) becomes non-zero if a query's
  * band kept more than 4096 columns (retry with CMVE_SIM_BF16X3, whose band is
  * ~10x narrower).  1 <= k <= 2048.
  * scores_ws: device workspace of at least cmve_topk_workspace() floats
@@ -587,8 +589,11 @@ int cmve_topk(cmve_handle_t h, const cmve_rows_t* q, const cmve_rows_t* g, int32
  *   3. per query: select T~_k among its entries, re-score the 2E band in fp64, sort
  *      (score desc, index asc).
  * A query whose entries exceed 512, whose band exceeds 256, or whose sample holds fewer than k
- * finite scores is left UNRESOLVED: out_idx[i, :] = -2, and *unresolved (device int32) counts
- * them; the caller re-runs those rows through cmve_topk (the host mirror does).  1 <= k <= 32
+ * finite scores (or its k-th score at -1: no finite threshold) is left UNRESOLVED, and so is every
+ * query of a 256-query tile (rows [256 t, 256 t + 256)) whose entries together exceed 256 * 512 =
+ * 131,072, the capacity of the tile's bucket: out_idx[i, :] = -2, out_score[i, :] = NaN, and
+ * *unresolved (device int32) counts them; the caller re-runs those rows through cmve_topk
+ * (the host mirror does).  1 <= k <= 32
  * (the sample is ~k/128 of the gallery; beyond a quarter the dense path is cheaper);
  * the gallery shard must hold < 2^24 rows.
  */

@@ -1,5 +1,6 @@
-"""Canary-buffer windows and the bound check shared by the C-ABI edge tests
-(test_gpu_head_edges.py, test_gpu_fusion_edges.py).  A plain module, not a test file."""
+"""Canary-buffer windows, the bound check and the restatements of score_error_bound and the directed fp32
+roundings shared by the C-ABI edge tests (test_gpu_head_edges.py, test_gpu_fusion_edges.py,
+test_gpu_pack_edges.py, test_gpu_topk_edges.py).  A plain module, not a test file."""
 import numpy as np
 import torch
 
@@ -51,3 +52,24 @@ def _within(got, want, bound, what):
     bad = ~(err <= b)
     assert not bad.any(), f"{what}: {int(bad.sum())} outside the bound, worst err {err[bad].max():.3e} " \
                           f"against {b[bad][np.argmax(err[bad])]:.3e}"
+
+
+def _f32_up(x):
+    with np.errstate(over="ignore"):
+        f = np.asarray(x, np.float64).astype(np.float32)
+    return np.where(f.astype(np.float64) < x, np.nextafter(f, np.float32(np.inf)), f).astype(np.float32)
+
+
+def _f32_down(x):
+    with np.errstate(over="ignore"):
+        f = np.asarray(x, np.float64).astype(np.float32)
+    return np.where(f.astype(np.float64) > x, np.nextafter(f, np.float32(-np.inf)), f).astype(np.float32)
+
+
+def _E(ea, eb, d_pad, mode):
+    """score_error_bound (cmve_internal.h:692) in fp64, operation for operation (mode 1 = CMVE_SIM_BF16X3)."""
+    ea, eb = np.asarray(ea, np.float64), np.asarray(eb, np.float64)
+    n = float(d_pad) * (33.0 / 32.0) * (3.0 if mode == 1 else 1.0)
+    u = 1.0 / 8388608.0
+    gamma = n * u / (1.0 - n * u)
+    return ea + (1.0 + ea) * eb + gamma * (1.0 + ea) * (1.0 + eb) + 1e-12

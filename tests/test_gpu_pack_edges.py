@@ -15,7 +15,7 @@ import numpy as np
 import pytest
 import torch
 
-from _windows import Pad, _within
+from _windows import Pad, _within, _E, _f32_up, _f32_down
 
 pytestmark = pytest.mark.gpu
 
@@ -85,27 +85,6 @@ def _f2bf(xf):
 
 def _bf2f(b):
     return (np.asarray(b, np.uint16).astype(np.uint32) << 16).view(np.float32)
-
-
-def _f32_up(x):
-    with np.errstate(over="ignore"):
-        f = np.asarray(x, np.float64).astype(np.float32)
-    return np.where(f.astype(np.float64) < x, np.nextafter(f, np.float32(INF)), f).astype(np.float32)
-
-
-def _f32_down(x):
-    with np.errstate(over="ignore"):
-        f = np.asarray(x, np.float64).astype(np.float32)
-    return np.where(f.astype(np.float64) > x, np.nextafter(f, np.float32(-INF)), f).astype(np.float32)
-
-
-def _E(ea, eb, d_pad, mode):
-    """score_error_bound (cmve_internal.h:692) in fp64, operation for operation."""
-    ea, eb = np.asarray(ea, np.float64), np.asarray(eb, np.float64)
-    n = float(d_pad) * (33.0 / 32.0) * (3.0 if mode == BF16X3 else 1.0)
-    u = 1.0 / 8388608.0
-    gamma = n * u / (1.0 - n * u)
-    return ea + (1.0 + ea) * eb + gamma * (1.0 + ea) * (1.0 + eb) + 1e-12
 
 
 def _norms(x):
