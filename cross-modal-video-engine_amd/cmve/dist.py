@@ -787,7 +787,8 @@ class MeasureShardedGallery(ShardedGallery):
     (``engine.pairwise_count(filter="l1")``: the same words, an overflow resolved on the device) and K23's top-k
     (``engine.pairwise_topk(filter="l1")``) over this shard, packed once as an ``engine.L1Set`` on its own grid by the
     first call that needs it; None -- the count from ``engine.L1_FILTER_MIN_PAIRS`` (d <= ``engine.L1_D_MAX``), the
-    top-k from ``engine.l1_topk_auto``.  ``band_cap`` / ``filter_stats`` as above.  jaccard has no filter."""
+    top-k from ``engine.l1_topk_auto``.  ``band_cap`` / ``filter_stats`` as above.  jaccard has no filter here: its
+    count filter (K24, ``engine.pairwise_count(filter="jaccard")``) serves an unsharded gallery."""
 
     # ---- shard-local arithmetic (HIP kernels) ----
     def _init_shard(self, local_embs, device, filter, band_cap, **_):

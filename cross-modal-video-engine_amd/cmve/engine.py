@@ -431,10 +431,27 @@ def _l1_applies(metric: int, score_dtype) -> bool:
     return metric == _lib.PW_L1 and score_dtype == torch.float64
 
 
+# ---- the SAD filter under jaccard (K24): the same codes, float32 words ----
+# Auto dispatch of the K24 filter (``filter=None``): the smallest na * nb at which it beats the K18 route by more than
+# the two routes' combined spread; None: never taken automatically, ``filter="jaccard"`` alone runs it.
+# tools/jaccard_filter_bench.py measures both routes at na = nb in {256 .. 16384}, D = 1024, non-negative float32 rows
+# (profiles/jaccard_filter.json, "crossover"; K18 / filter, one call each): up to 2048 x 2048 the filter's extra
+# launches cost it 0.4-0.8 ms (2.67 ms against 3.44 ms at 2048 x 2048); at 4096 x 4096 it takes 4.86 ms against
+# 6.15 ms, inside the K18 route's 1.86 ms of spread; at 8192 x 8192 8.25 ms against 17.36 ms with 0.86 ms of combined
+# spread, at 16384 x 16384 17.0 ms against 55.2 ms.  (At 16,384 x 131,072: 48.7 ms against 389.1 ms.)
+JACCARD_FILTER_MIN_PAIRS = 8192 * 8192
+
+
+def _jaccard_applies(metric: int, score_dtype) -> bool:
+    """The jaccard filter speaks for ``PW_JACCARD`` with float32 score words and for nothing else."""
+    return metric == _lib.PW_JACCARD and score_dtype == torch.float32
+
+
 def _filter_route(name: str, filter, metric: int, alpha: float, beta: float, score_dtype, l2_scaling: bool,
                   size=None) -> Optional[str]:
-    """THE route of a count: None (fp64), ``"l2"`` (the MFMA filter) or ``"l1"`` (the SAD filter), at two moments.
-    size None -- before any operand is touched: a forced value (True, ``"l1"``) gives its route, or ValueError where
+    """THE route of a count: None (the canonical chain), ``"l2"`` (the MFMA filter), ``"l1"`` (the SAD filter) or
+    ``"jaccard"`` (the SAD filter under jaccard, float32 words), at two moments.
+    size None -- before any operand is touched: a forced value (True, ``"l1"``, ``"jaccard"``) gives its route, or ValueError where
     that filter cannot speak for the call; ``filter=True`` judges alpha / beta here only with ``l2_scaling`` (else a
     bad scaling is the C entry's to refuse).  size = (na * nb, d, the sets are ones the Euclidean entries take) --
     the auto rule of ``filter=None``, which never hands an entry what it refuses."""
@@ -445,6 +462,11 @@ def _filter_route(name: str, filter, metric: int, alpha: float, beta: float, sco
                 raise ValueError(f'{name}: filter="l1" needs PW_L1 with float64 score words, alpha finite and '
                                  "non-zero, beta finite")
             return "l1"
+        if isinstance(filter, str) and filter == "jaccard":
+            if not (_jaccard_applies(metric, score_dtype) and scaling):
+                raise ValueError(f'{name}: filter="jaccard" needs PW_JACCARD with float32 score words, alpha finite '
+                                 "and non-zero, beta finite")
+            return "jaccard"
         if filter:
             if not (_l2_applies(metric, score_dtype) and (scaling or not l2_scaling)):
                 raise ValueError(f"{name}: filter=True needs PW_L2 with float64 score words"
@@ -456,6 +478,9 @@ def _filter_route(name: str, filter, metric: int, alpha: float, beta: float, sco
         return None
     if _l1_applies(metric, score_dtype):
         return "l1" if L1_FILTER_MIN_PAIRS is not None and pairs >= L1_FILTER_MIN_PAIRS and d <= L1_D_MAX else None
+    if _jaccard_applies(metric, score_dtype):
+        return ("jaccard" if JACCARD_FILTER_MIN_PAIRS is not None and pairs >= JACCARD_FILTER_MIN_PAIRS
+                and d <= L1_D_MAX else None)
     return "l2" if _l2_applies(metric, score_dtype) and pairs >= L2_FILTER_MIN_PAIRS and sets_ok else None
 
 
@@ -508,18 +533,41 @@ class L1Set:
                                _ptr(self.codes), self.n_pad, self.d_pad, _ptr(self.err)), "cmve_l1_pack")
 
 
-def _l1_sets(a, b, a_set: Optional["L1Set"], b_set: Optional["L1Set"]):
-    """Both sides as ``L1Set`` on ONE grid: a resident side's when there is one, else both sets' elements."""
+class JaccardSet(L1Set):
+    """Rows packed for the SAD filter under jaccard (K24): an ``L1Set`` -- the same codes, errors and grid, from the
+    same ``cmve_l1_pack`` -- plus the two per-row arrays of ``cmve_jaccard_rowsums``: ``qsum`` (int64, the exact sum of
+    the row's codes) and ``asum`` (float64, >= sum |x|; +inf where ``err`` is).  ``JaccardSet(x, grid=other.grid)``
+    works as ``L1Set`` does; a resident gallery is packed once.  It serves ``filter="l1"`` as well."""
+
+    def __init__(self, x, grid: Optional[torch.Tensor] = None, device: Optional[torch.device] = None):
+        super().__init__(x, grid=grid, device=device)
+        raw = self.raw
+        self.qsum = torch.empty(max(self.n, 1), dtype=torch.int64, device=raw.device)
+        self.asum = torch.empty(max(self.n, 1), dtype=torch.float64, device=raw.device)
+        check(lib.cmve_jaccard_rowsums(handle(raw.device), _ptr(raw), _dtype_code(raw), _pw_ld(raw), self.n, self.d,
+                                       _ptr(self.grid), self.n_pad, self.d_pad, _ptr(self.qsum), _ptr(self.asum)),
+              "cmve_jaccard_rowsums")
+
+
+def _l1_sets(a, b, a_set: Optional["L1Set"], b_set: Optional["L1Set"], cls=None):
+    """Both sides as ``L1Set`` (``cls``: as ``JaccardSet``) on ONE grid: a resident side's when there is one, else
+    both sets' elements."""
+    if cls is None:
+        cls = L1Set
+    else:
+        for given in (a_set, b_set):
+            if given is not None and not isinstance(given, cls):
+                raise TypeError(f'an L1Set holds no row sums: filter="jaccard" takes a {cls.__name__}')
     if a_set is not None and b_set is not None:
         if a_set.grid.data_ptr() != b_set.grid.data_ptr():
             raise ValueError("the two L1Set sides were packed on different grids: pack one with grid=other.grid")
         return a_set, b_set
     if a_set is not None:
-        return a_set, L1Set(b, grid=a_set.grid)
+        return a_set, cls(b, grid=a_set.grid)
     if b_set is not None:
-        return L1Set(a, grid=b_set.grid), b_set
+        return cls(a, grid=b_set.grid), b_set
     grid = l1_grid(b, l1_grid(a))
-    return L1Set(a, grid=grid), L1Set(b, grid=grid)
+    return cls(a, grid=grid), cls(b, grid=grid)
 
 
 def _l1_count_call(h, a_set: "L1Set", b_set: "L1Set", alpha, beta, row, col, ws, ws_bytes: int, stats):
@@ -529,6 +577,23 @@ def _l1_count_call(h, a_set: "L1Set", b_set: "L1Set", alpha, beta, row, col, ws,
                             _ptr(b), _dtype_code(b), _pw_ld(b), b_set.n, _ptr(b_set.codes), _ptr(b_set.err), a_set.d,
                             _ptr(a_set.grid), float(alpha), float(beta), *_count_tail(row, col, ws, ws_bytes, stats)),
           "cmve_l1_count")
+
+
+def jaccard_count_workspace(band_cap: int) -> int:
+    """Bytes of workspace ``cmve_jaccard_count`` needs for a band list of ``band_cap`` pairs (host only: no launch)."""
+    n = C.c_int64()
+    check(lib.cmve_jaccard_count_workspace(int(band_cap), C.byref(n)), "cmve_jaccard_count_workspace")
+    return n.value
+
+
+def _jaccard_count_call(h, a_set: "JaccardSet", b_set: "JaccardSet", alpha, beta, row, col, ws, ws_bytes: int, stats):
+    """``cmve_jaccard_count`` (row / col / ws / stats as ``_count_tail``; the items' words are float32 values)."""
+    a, b = a_set.raw, b_set.raw
+    check(lib.cmve_jaccard_count(h, _ptr(a), _dtype_code(a), _pw_ld(a), a_set.n, _ptr(a_set.codes), _ptr(a_set.err),
+                                 _ptr(a_set.qsum), _ptr(a_set.asum), _ptr(b), _dtype_code(b), _pw_ld(b), b_set.n,
+                                 _ptr(b_set.codes), _ptr(b_set.err), _ptr(b_set.qsum), _ptr(b_set.asum), a_set.d,
+                                 _ptr(a_set.grid), float(alpha), float(beta),
+                                 *_count_tail(row, col, ws, ws_bytes, stats)), "cmve_jaccard_count")
 
 
 class _PairwisePositions:
@@ -545,7 +610,12 @@ class _PairwisePositions:
     grid, the item scores from ``cmve_pairwise_item_scores``, the count from ONE ``cmve_l1_count`` (integer SAD filter
     + canonical re-score of the band, an overflowing list resolved on the device: the same words, no redo);
     None takes it too when it applies and na * nb reaches ``L1_FILTER_MIN_PAIRS``.  ``filter_stats`` then carries
-    the four counters, ``redone=False`` and ``fallback`` (the overflow word: the canonical count ran)."""
+    the four counters, ``redone=False`` and ``fallback`` (the overflow word: the canonical count ran).
+
+    ``filter="jaccard"`` -- the K24 route for ``PW_JACCARD`` with float32 score words: K22's codes plus the rows' code
+    sums, the item words (float32) from ``cmve_pairwise_item_scores``, the count from ONE ``cmve_jaccard_count`` (no
+    redo); None takes it too when it applies and na * nb reaches ``JACCARD_FILTER_MIN_PAIRS`` (never while that is
+    None).  ``filter_stats`` as for ``"l1"``."""
 
     def __init__(self, a, b, metric, alpha, beta, score_dtype, row_lists=None, col_lists=None, filter=None):
         self.filter_stats = None
@@ -571,7 +641,8 @@ class _PairwisePositions:
                                        (na * nb, a.shape[1], True))
         sc = None
         if route and na and nb and ritems + citems:
-            sc = (self._filtered_l1 if route == "l1" else self._filtered)(a, b, alpha, beta, sides)
+            run = {"l1": self._filtered_l1, "jaccard": self._filtered_jaccard, "l2": self._filtered}[route]
+            sc = run(a, b, alpha, beta, sides)
         if sc is None:
             nbytes = pairwise_positions_workspace(na, nb, ritems, citems, metric)
             ws = torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=dev)
@@ -583,14 +654,14 @@ class _PairwisePositions:
             sc = ws.cpu().numpy()
         self._collect(sides, sc)
 
-    def _filter_pass(self, a, b, metric, alpha, beta, sides):
-        """What the two filtered routes share.  The items' scores are computed into ONE device buffer with room for the
+    def _filter_pass(self, a, b, metric, alpha, beta, sides, score_dtype=torch.float64):
+        """What the filtered routes share.  The items' scores are computed into ONE device buffer with room for the
         counters; the run(call, nbytes) returned makes a workspace of nbytes, has call(row, col, ws, nbytes, stats)
         count into the sides' position buffers, and brings scores and counters to the host in one copy: (scores,
         {decided, band, rescored, overflow})."""
         (roff, _, ritems, rpos), (coff, _, citems, cpos) = sides
         na, nb, items = a.shape[0], b.shape[0], sides[0][2] + sides[1][2]
-        buf = self._item_scores(a, b, metric, alpha, beta, sides)
+        buf = self._item_scores(a, b, metric, alpha, beta, sides, score_dtype)
         row, col = (roff, buf[:ritems], ritems, nb, rpos), (coff, buf[ritems:items], citems, na, cpos)
 
         def run(call, nbytes):
@@ -620,9 +691,9 @@ class _PairwisePositions:
         return None
 
     @staticmethod
-    def _item_scores(a, b, metric, alpha, beta, sides):
-        """The items' fp64 scores, then room for a filter's four counters, in ONE device buffer: one copy to the host
-        brings both."""
+    def _item_scores(a, b, metric, alpha, beta, sides, score_dtype=torch.float64):
+        """The items' scores (fp64 slots; rounded to ``score_dtype``), then room for a filter's four counters, in ONE
+        device buffer: one copy to the host brings both."""
         (roff, ridx, ritems, _), (coff, cidx, citems, _) = sides
         na, nb = a.shape[0], b.shape[0]
         buf = torch.empty(ritems + citems + 4, dtype=torch.float64, device=a.device)
@@ -630,7 +701,7 @@ class _PairwisePositions:
         for off, idx, items, col_dir, n_other in ((roff, ridx, ritems, 0, nb), (coff, cidx, citems, 1, na)):
             if items:
                 out = buf[start:start + items]
-                _item_scores_into(out, a, b, metric, alpha, beta, torch.float64, off, idx, items, col_dir, 0)
+                _item_scores_into(out, a, b, metric, alpha, beta, score_dtype, off, idx, items, col_dir, 0)
                 # an index outside the other side scores NaN here (the sharded entry gives it the all-zero word)
                 out.masked_fill_((idx[:items] < 0) | (idx[:items] >= n_other), float("nan"))
             start += items
@@ -644,6 +715,17 @@ class _PairwisePositions:
         run = self._filter_pass(a, b, _lib.PW_L1, alpha, beta, sides)
         sc, st = run(lambda *tail: _l1_count_call(h, sa, sb, alpha, beta, *tail),
                      l1_count_workspace(l2_band_cap(a.shape[0] * b.shape[0])))
+        self.filter_stats = dict(st, redone=False, fallback=bool(st["overflow"]))
+        return sc
+
+    def _filtered_jaccard(self, a, b, alpha, beta, sides):
+        """The K24 route into the sides' position buffers; the items' words (host).  ONE ``cmve_jaccard_count`` call,
+        as ``_filtered_l1``: an overflowing band list is resolved on the device, never redone."""
+        h = handle(a.device)
+        sa, sb = _l1_sets(a, b, None, None, JaccardSet)
+        run = self._filter_pass(a, b, _lib.PW_JACCARD, alpha, beta, sides, torch.float32)
+        sc, st = run(lambda *tail: _jaccard_count_call(h, sa, sb, alpha, beta, *tail),
+                     jaccard_count_workspace(l2_band_cap(a.shape[0] * b.shape[0])))
         self.filter_stats = dict(st, redone=False, fallback=bool(st["overflow"]))
         return sc
 
@@ -760,7 +842,14 @@ def pairwise_count(a, b, metric: int, alpha: float, beta: float, score_dtype, ro
     with float64 score words, alpha finite and non-zero and beta finite; None also takes it when it applies and
     na * nb reaches ``L1_FILTER_MIN_PAIRS`` (never while that is None).  a / b may then be an ``L1Set`` (a resident
     side packed once; the other side is packed on its grid inside the call) -- plain rows on both sides share a
-    grid made from both.  ``band`` / ``return_stats`` as above."""
+    grid made from both.  ``band`` / ``return_stats`` as above.
+
+    ``filter="jaccard"`` -- ``cmve_jaccard_count`` (K24: the same SAD filter under ``PW_JACCARD`` with float32 score
+    words -- the item scores are float32 values in float64 slots --, the band re-scored on the canonical
+    two-accumulator chain, an overflowing list resolved on the device: the same words), ValueError unless the metric
+    is ``PW_JACCARD`` with float32 score words, alpha finite and non-zero and beta finite; None also takes it when it
+    applies and na * nb reaches ``JACCARD_FILTER_MIN_PAIRS`` (never while that is None).  a / b may then be a
+    ``JaccardSet`` (an ``L1Set`` plus the rows' code sums; a resident side packed once)."""
     route = _filter_route("pairwise_count", filter, metric, alpha, beta, score_dtype, True)
     a_l1, b_l1 = (a if isinstance(a, L1Set) else None), (b if isinstance(b, L1Set) else None)
     a_set = a if isinstance(a, RowSet) else None
@@ -783,6 +872,9 @@ def pairwise_count(a, b, metric: int, alpha: float, beta: float, score_dtype, ro
     # (auto never hands the entry what it refuses; filter=True does, and the entry says so)
     route = route or _filter_route("pairwise_count", filter, metric, alpha, beta, score_dtype, True,
                                    (na * nb, a.shape[1], _l2_set_ok(a_set) and _l2_set_ok(b_set)))
+    if filter is None and route == "jaccard" and any(s is not None and not isinstance(s, JaccardSet)
+                                                     for s in (a_l1, b_l1)):
+        route = None  # (a plain L1Set holds no row sums: the K18 route on its raw rows)
     stats = None
     if route:
         if band is None:
@@ -793,6 +885,9 @@ def pairwise_count(a, b, metric: int, alpha: float, beta: float, score_dtype, ro
     if route == "l1":
         a_l1, b_l1 = _l1_sets(a, b, a_l1, b_l1)
         _l1_count_call(handle(dev), a_l1, b_l1, alpha, beta, sides[0], sides[1], band, _nbytes(band), stats)
+    elif route == "jaccard":
+        a_l1, b_l1 = _l1_sets(a, b, a_l1, b_l1, JaccardSet)
+        _jaccard_count_call(handle(dev), a_l1, b_l1, alpha, beta, sides[0], sides[1], band, _nbytes(band), stats)
     elif route == "l2":
         if a_l1 is not None or b_l1 is not None:
             raise TypeError("pairwise_count: an L1Set is packed for filter=\"l1\"; the Euclidean filter takes a RowSet")

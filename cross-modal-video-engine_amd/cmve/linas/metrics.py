@@ -67,7 +67,9 @@ def measure_eval(caps, vids, measure, row_lists=None, col_lists=None, filter=Non
     ``filter``: None -- euclidean / l2 / l2_norm take the MFMA filter (K19) from ``engine.L2_FILTER_MIN_PAIRS``
     pairs on, the same words; True / False force it on (those three measures only) / off.  ``"l1"`` forces the
     integer SAD filter of l1 / l1_norm (K22: the same words; those two measures only), which None takes from
-    ``engine.L1_FILTER_MIN_PAIRS`` pairs on when that is set."""
+    ``engine.L1_FILTER_MIN_PAIRS`` pairs on when that is set.  ``"jaccard"`` forces the same SAD filter under jaccard
+    (K24: float32 words, the same words; that measure only), which None takes from
+    ``engine.JACCARD_FILTER_MIN_PAIRS`` pairs on when that is set."""
     from .evaluation import measure_spec
     metric, alpha, beta, _, sc_dt = measure_spec(measure, vids.shape[1])
     return engine.pairwise_gt_eval(caps, vids, metric, alpha, beta, sc_dt, row_lists, col_lists, filter)

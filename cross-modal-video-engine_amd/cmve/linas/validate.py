@@ -81,7 +81,8 @@ def cal_perf_embeddings(video_embs, cap_embs, video_ids, caption_ids, measure='c
     without materialising the N_c x N_v error matrix on host.  A non-cosine ``measure`` (the cdist branches and
     jaccard of evaluation.py:22-35) never forms the matrix at all, on the device or the host (K18); ``filter`` is
     ``metrics.measure_eval``'s (auto: the Euclidean measures count at the MFMA rate on large sets, K19;
-    ``filter="l1"``: l1 / l1_norm through the integer SAD filter, K22)."""
+    ``filter="l1"``: l1 / l1_norm through the integer SAD filter, K22; ``filter="jaccard"``: jaccard through the same
+    filter, K24)."""
     v2t_gt, t2v_gt = metrics.get_gt(video_ids, caption_ids)
     if measure != 'cosine':
         from .evaluation import measure_rows

@@ -1,5 +1,6 @@
 // What the host side of a filtered count shares, whatever the filter (K19 / K21: the MFMA filter of l2_filter.hip;
-// K22: the SAD filter of l1_filter.hip) -- every one of them promises cmve_pairwise_count's words:
+// K22: the SAD filter of l1_filter.hip; K24: the same filter under jaccard, jaccard_filter.hip) -- every one of them
+// promises cmve_pairwise_count's words:
 //   FltLists / FltBand   the caller's lists and band list, as every entry, launch and kernel argument carries them
 //   flt_check_lists      what every count entry asks of the lists (cmve_pairwise_count included)
 //   flt_count_run        the host body: checks, memsets, NaN items, the filter's main launch, fix-up, resolve
@@ -57,8 +58,8 @@ static inline int flt_check_lists(const char* name, FltLists& l) {
   return CMVE_OK;
 }
 
-// ---- the launches that do not depend on how the pairs were filtered (`metric` is CMVE_PW_L2 or CMVE_PW_L1; FltRows,
-// the raw rows of both sides, is l2_filter_tile.h's) ----
+// ---- the launches that do not depend on how the pairs were filtered (`metric` is CMVE_PW_L2 or CMVE_PW_L1 with fp64
+// words, or CMVE_PW_JACCARD with float32 words; FltRows, the raw rows of both sides, is l2_filter_tile.h's) ----
 // the NaN items' words of one direction (n_lists lists, the caller's n); l2_filter.hip
 void l2f_nan_launch(hipStream_t st, const int64_t* off, const double* sc, int64_t n_lists, int64_t n, int32_t* pos);
 // the band list's pairs on the canonical chain (returns at once on the device when the list overflowed); l2_filter.hip
@@ -68,7 +69,7 @@ void l2f_fixup_launch(hipStream_t st, int32_t metric, const FltRows& r, double a
 // l2_filter.hip
 void l2f_resolve_launch(hipStream_t st, int32_t metric, const FltRows& r, double alpha, double beta, const FltLists& l,
                         const l2f_u64* stats);
-// cmve_pairwise_count's counting tiles (pairwise_rank.hip) with fp64 score words, gated: a bounded grid whose blocks
+// cmve_pairwise_count's counting tiles (pairwise_rank.hip) with the metric's score words, gated: a bounded grid whose blocks
 // return at once when *gate is 0 and loop over the tiles otherwise.  pos must be zero where *gate is not.
 void pwr_count_gated_launch(hipStream_t st, int32_t metric, const FltRows& r, double alpha, double beta,
                             const FltLists& l, const l2f_u64* gate);

@@ -243,8 +243,8 @@ __global__ __launch_bounds__(256, 2) void l2f_main_kernel(L2fArgs a) {
 }
 
 // ---- the band pairs on the canonical chain -----------------------------------------------------------------------------
-// (METRIC: CMVE_PW_L2, or CMVE_PW_L1 for the SAD filter of l1_filter.hip -- the list, the lists' words and the
-// counters are the same, the chain is the metric's)
+// (METRIC: CMVE_PW_L2, CMVE_PW_L1 for the SAD filter of l1_filter.hip, or CMVE_PW_JACCARD for jaccard_filter.hip's --
+// the list, the lists' words and the counters are the same, the chain is the metric's; jaccard's words are float32)
 template <int METRIC, typename TA, typename TB>
 __global__ __launch_bounds__(256) void l2f_fixup_kernel(const TA* __restrict__ A, int64_t lda,
                                                         const TB* __restrict__ B, int64_t ldb, int64_t d, double alpha,
@@ -262,8 +262,10 @@ __global__ __launch_bounds__(256) void l2f_fixup_kernel(const TA* __restrict__ A
     const int64_t p = b0 + w * 64 + lane;
     const bool live = p < n;
     const int2 ij = band[live ? p : b0];  // an idle lane repeats a pair of the list: its loads stay in bounds
-    const double s = l2f_chain64<METRIC>(A, lda, B, ldb, d, ij.x, ij.y, sd[w], lane);
-    const double e = pw_score<METRIC>(s, 0.0, alpha, beta);
+    double s1 = 0.0;
+    const double s = l2f_chain64<METRIC>(A, lda, B, ldb, d, ij.x, ij.y, sd[w], lane, &s1);
+    // (jaccard's words are float32: K24)
+    const double e = pw_round(pw_score<METRIC>(s, s1, alpha, beta), METRIC == CMVE_PW_JACCARD);
     if (live) {
       if (row_pos) {
         const int64_t o = row_off[ij.x], m = row_off[ij.x + 1];
@@ -325,7 +327,9 @@ void l2f_fixup_launch(hipStream_t st, int32_t metric, const FltRows& r, double a
                        r.lda, (const TB*)r.B, r.ldb, r.d, alpha, beta, l.row_off, l.row_sc, l.row_pos, l.col_off,     \
                        l.col_sc, l.col_pos, (const int2*)b.band, b.cap, b.stats);                                     \
   })
-  if (metric == CMVE_PW_L1) { L2F_FIXUP(CMVE_PW_L1) } else { L2F_FIXUP(CMVE_PW_L2) }
+  if (metric == CMVE_PW_L1) { L2F_FIXUP(CMVE_PW_L1) }
+  else if (metric == CMVE_PW_JACCARD) { L2F_FIXUP(CMVE_PW_JACCARD) }
+  else { L2F_FIXUP(CMVE_PW_L2) }
 #undef L2F_FIXUP
 }
 

@@ -195,15 +195,38 @@ __device__ __forceinline__ void l2f_gemm_tile(const uint16_t* __restrict__ a16, 
 #undef L2F_WRITE
 }
 
-// The canonical sum (of squares: CMVE_PW_L2; of magnitudes: CMVE_PW_L1) of 64 listed pairs, one per lane of a wave: lane l's pair is (A row i, B row j) of ITS
+// The canonical sum (of squares: CMVE_PW_L2; of magnitudes: CMVE_PW_L1) of 64 listed pairs, one per lane of a wave:
+// lane l's pair is (A row i, B row j) of ITS
 // arguments.  The (a - b) chunks go through sd (this wave's [64][L2F_KC + 1] doubles of LDS) transposed, so the loads
 // are coalesced (16 lanes read 128 contiguous bytes of a row); each lane then runs its own pair's chain, pw_acc with
 // k ascending into one accumulator from zero.  Every lane must name rows that exist (an idle lane repeats a listed
 // pair).  The barriers are the block's: every wave of the block calls this the same number of times with the same d.
+// CMVE_PW_JACCARD (K24): the two sums of the pair -- the minima's is returned, the maxima's goes to *s1_out.  Its chain
+// takes both elements, so a chunk is L2F_KC / 2 deep: the A elements in sd's columns 0 .. 7, the B elements in 8 .. 15.
 template <int METRIC = CMVE_PW_L2, typename TA, typename TB>
 __device__ __forceinline__ double l2f_chain64(const TA* __restrict__ A, int64_t lda, const TB* __restrict__ B,
                                               int64_t ldb, int64_t d, int i, int j, double (&sd)[64][L2F_KC + 1],
-                                              int lane) {
+                                              int lane, double* s1_out = nullptr) {
+  if constexpr (METRIC == CMVE_PW_JACCARD) {
+    constexpr int KH = L2F_KC / 2;
+    double s0 = 0.0, s1 = 0.0;
+    for (int64_t k0 = 0; k0 < d; k0 += KH) {
+#pragma unroll 4
+      for (int it = 0; it < 16; ++it) {
+        const int q = it * 4 + (lane >> 4), k = lane & 7, side = (lane >> 3) & 1;
+        const int64_t qi = __shfl(i, q, 64), qj = __shfl(j, q, 64);
+        double x = 0.0;
+        if (k0 + k < d) x = side ? (double)B[qj * ldb + k0 + k] : (double)A[qi * lda + k0 + k];
+        sd[q][side * KH + k] = x;
+      }
+      __syncthreads();
+      const int kn = (int)min<int64_t>(KH, d - k0);
+      for (int k = 0; k < kn; ++k) pw_acc<METRIC>(sd[lane][k], sd[lane][KH + k], s0, s1);
+      __syncthreads();
+    }
+    *s1_out = s1;
+    return s0;
+  }
   double s = 0.0, unused = 0.0;
   for (int64_t k0 = 0; k0 < d; k0 += L2F_KC) {
 #pragma unroll 4

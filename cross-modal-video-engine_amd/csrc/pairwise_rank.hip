@@ -20,8 +20,6 @@
 
 namespace cmve {
 
-__device__ __forceinline__ double pw_round(double x, int f32) { return f32 ? (double)(float)x : x; }
-
 // ---- launch 1: the score of every listed item -------------------------------------------------------------
 // item p of list `owner` (off[owner] <= p < off[owner + 1]) names row idx[p] - idx_base of the other side; col_dir:
 // the lists belong to B rows and name A rows.  An index outside the other side (nothing is read) scores NaN, or --
@@ -57,7 +55,7 @@ __global__ __launch_bounds__(256) void pwr_item_kernel(const TA* __restrict__ A,
 // cmve_gt_positions_from_matrix's value for it instead, row_n - (NaN items of the list) + (its place among them)
 // (row_n == 0: its word stays 0 -- another shard of the gallery stores it).  The grid has at least one block row and
 // column, so the rule also runs when na or nb is 0.  pos must be zero on entry.
-// GATED (K21 / K22, cmve_l2_count_resolved and cmve_l1_count; gate / tiles_x / tiles are read by this instantiation alone): every thread reads
+// GATED (K21 / K22 / K24, cmve_l2_count_resolved, cmve_l1_count and cmve_jaccard_count; gate / tiles_x / tiles are read by this instantiation alone): every thread reads
 // *gate first and the block returns at once when it is 0; otherwise the blocks of a BOUNDED 1-d grid loop over the
 // tiles_x x tiles_y tiles, block b taking b, b + gridDim.x, ... in the plain grid's own order -- a call whose gate stays
 // shut dispatches a few thousand blocks, not one per tile.
@@ -333,13 +331,16 @@ void pwr_count_gated_launch(hipStream_t st, int32_t metric, const FltRows& r, do
   const int64_t tiles_x = std::max<int64_t>(1, (r.nb + PW_TB - 1) / PW_TB);
   const int64_t tiles = tiles_x * std::max<int64_t>(1, (r.na + PW_TA - 1) / PW_TA);
   const unsigned blocks = (unsigned)std::min<int64_t>(tiles, 64 * (int64_t)device_cus());
-#define PWR_GATED(M)                                                                                                  \
+#define PWR_GATED(M, F32)                                                                                             \
   PWR_TYPES(r.a_dtype, r.b_dtype, TA, TB, {                                                                           \
     hipLaunchKernelGGL((pwr_count_kernel<M, TA, TB, true>), dim3(blocks), dim3(256), 0, st, (const TA*)r.A, r.lda,    \
-                       r.na, (const TB*)r.B, r.ldb, r.nb, r.d, alpha, beta, 0, l.row_off, l.row_sc, l.row_n,          \
+                       r.na, (const TB*)r.B, r.ldb, r.nb, r.d, alpha, beta, F32, l.row_off, l.row_sc, l.row_n,        \
                        l.row_pos, l.col_off, l.col_sc, l.col_n, l.col_pos, gate, (unsigned)tiles_x, tiles);           \
   })
-  if (metric == CMVE_PW_L1) { PWR_GATED(CMVE_PW_L1) } else { PWR_GATED(CMVE_PW_L2) }
+  // (the filters' words: fp64 under CMVE_PW_L2 / CMVE_PW_L1, float32 under CMVE_PW_JACCARD -- K24)
+  if (metric == CMVE_PW_L1) { PWR_GATED(CMVE_PW_L1, 0) }
+  else if (metric == CMVE_PW_JACCARD) { PWR_GATED(CMVE_PW_JACCARD, 1) }
+  else { PWR_GATED(CMVE_PW_L2, 0) }
 #undef PWR_GATED
 }
 

@@ -42,6 +42,9 @@ __device__ __forceinline__ double pw_score(double s0, double s1, double alpha, d
   return alpha * pw_final<METRIC>(s0, s1) + beta;
 }
 
+// the one rounding to the score dtype (f32: float32 words, carried in a double)
+__device__ __forceinline__ double pw_round(double x, int f32) { return f32 ? (double)(float)x : x; }
+
 // the whole chain of one pair from its two rows (one thread: the listed items of K18, a handful per query)
 template <int METRIC, typename TA, typename TB>
 __device__ __forceinline__ double pw_pair_score(const TA* __restrict__ a, const TB* __restrict__ b, int64_t d,

@@ -822,6 +822,43 @@ int cmve_l1_count(cmve_handle_t h, const void* A, int32_t a_dtype, int64_t lda, 
                   const int64_t* col_off, const double* col_sc, int64_t col_items, int64_t col_n, int32_t* col_pos,
                   void* ws, int64_t ws_bytes, int64_t* stats);
 
+/* K24: cmve_pairwise_count for CMVE_PW_JACCARD with float32 score words from K22's integer SAD filter
+ * (csrc/jaccard_filter.hip).  Replaces, as its K18 twin does: LINAS-engine/evaluation.py:32-35 and :56-72 (cal_error
+ * and cal_error_batch under jaccard) + util/metrics.py:61-157 (t2v_map, v2t_map, eval_q2m's argsort loop).
+ *   The codes, the grid and the rows' errors are cmve_l1_grid's and cmve_l1_pack's, unchanged.  On the grid
+ *   sum_k min and sum_k max of the decoded rows are (P -+ s * SAD) / 2 with P = 2 d lo + s (sum qa + sum qb): integers;
+ *   the true sums lie within the two rows' quantisation errors of them, the canonical chains within
+ *   (d + 2) u (S_a + S_b) of the true sums.  Additive entries: the ABI version does not change.
+ *   cmve_jaccard_rowsums  (evaluation.py:32-35 + metrics.py:61-157: the packed form of cal_error's operands under
+ *                      jaccard) the two per-row arrays a jaccard side carries beside cmve_l1_pack's: qsum[i] = the
+ *                      exact sum of row i's codes (int64; the row is quantised again with the pack's own expression on
+ *                      the same grid, so the integers are the stored codes' bit for bit) and asum[i] >= sum_k |x_k|
+ *                      (fp64, rounded up; +inf where err is +inf).  n_pad / d_pad: cmve_l1_pack_size's, as
+ *                      cmve_l1_pack checks them.
+ *   cmve_jaccard_count_workspace  host only (evaluation.py:32-35 + metrics.py:61-157, as above): 8 * band_cap bytes,
+ *                      the band list and nothing else.
+ *   cmve_jaccard_count (evaluation.py:32-35, :56-72 + metrics.py:61-157, as above) cmve_l1_count's contract with
+ *                      CMVE_PW_JACCARD and float32 words: row_sc / col_sc hold float32 values carried in doubles
+ *                      (cmve_pairwise_item_scores with score_dtype = CMVE_F32).  On return row_pos / col_pos hold,
+ *                      word for word, what cmve_pairwise_count(metric = CMVE_PW_JACCARD, score_dtype = CMVE_F32)
+ *                      writes for the same lists (NaN items included, also when na or nb is 0; either direction may
+ *                      be NULL), WHETHER OR NOT the band list overflowed: the band is re-scored on the canonical
+ *                      two-accumulator chain with its one rounding to float32, an overflow is resolved on the device
+ *                      by cmve_l2_count_resolved's two gated launches.  ws / stats as cmve_l1_count's.  Enqueued on
+ *                      the handle's stream; allocates nothing, never synchronises; integer atomics only: two calls
+ *                      give the same words.  Refused: alpha 0 or non-finite, beta non-finite, d > 65,536, NULL codes /
+ *                      err / sums / grid, rows that are not F32 / F64. */
+int cmve_jaccard_rowsums(cmve_handle_t h, const void* X, int32_t dtype, int64_t ld, int64_t n, int64_t d,
+                         const double* grid, int64_t n_pad, int64_t d_pad, int64_t* qsum, double* asum);
+int cmve_jaccard_count_workspace(int64_t band_cap, int64_t* bytes);
+int cmve_jaccard_count(cmve_handle_t h, const void* A, int32_t a_dtype, int64_t lda, int64_t na, const void* a_codes,
+                       const double* a_err, const int64_t* a_qsum, const double* a_asum, const void* B,
+                       int32_t b_dtype, int64_t ldb, int64_t nb, const void* b_codes, const double* b_err,
+                       const int64_t* b_qsum, const double* b_asum, int64_t d, const double* grid, double alpha,
+                       double beta, const int64_t* row_off, const double* row_sc, int64_t row_items, int64_t row_n,
+                       int32_t* row_pos, const int64_t* col_off, const double* col_sc, int64_t col_items,
+                       int64_t col_n, int32_t* col_pos, void* ws, int64_t ws_bytes, int64_t* stats);
+
 /* K20: cmve_pairwise_topk for CMVE_PW_L2 with fp64 score words at the MFMA rate (csrc/l2_topk.hip).
  * Replaces, as its K18 twin does: LINAS-engine/inference.py:78-80 (cal_error(video_embs, cap_emb, measure) then
  * np.argsort(errors[0])[:topK]) under euclidean / l2 / l2_norm (LINAS-engine/evaluation.py:22-35).
