@@ -9,7 +9,8 @@ from __future__ import annotations
 import atexit
 import contextlib
 import ctypes as C
-from typing import Dict, Optional, Sequence, Tuple
+import functools
+from typing import Dict, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -426,11 +427,6 @@ L1_D_MAX = 65536  # cmve_l1_count's limit on d: the u32 SAD of uint16 codes is e
 L1_FILTER_MIN_PAIRS = 8192 * 8192
 
 
-def _l1_applies(metric: int, score_dtype) -> bool:
-    """The SAD filter speaks for ``PW_L1`` with float64 score words and for nothing else."""
-    return metric == _lib.PW_L1 and score_dtype == torch.float64
-
-
 # ---- the SAD filter under jaccard (K24): the same codes, float32 words ----
 # Auto dispatch of the K24 filter (``filter=None``): the smallest na * nb at which it beats the K18 route by more than
 # the two routes' combined spread; None: never taken automatically, ``filter="jaccard"`` alone runs it.
@@ -440,11 +436,6 @@ def _l1_applies(metric: int, score_dtype) -> bool:
 # 6.15 ms, inside the K18 route's 1.86 ms of spread; at 8192 x 8192 8.25 ms against 17.36 ms with 0.86 ms of combined
 # spread, at 16384 x 16384 17.0 ms against 55.2 ms.  (At 16,384 x 131,072: 48.7 ms against 389.1 ms.)
 JACCARD_FILTER_MIN_PAIRS = 8192 * 8192
-
-
-def _jaccard_applies(metric: int, score_dtype) -> bool:
-    """The jaccard filter speaks for ``PW_JACCARD`` with float32 score words and for nothing else."""
-    return metric == _lib.PW_JACCARD and score_dtype == torch.float32
 
 
 def _filter_route(name: str, filter, metric: int, alpha: float, beta: float, score_dtype, l2_scaling: bool,
@@ -457,16 +448,12 @@ def _filter_route(name: str, filter, metric: int, alpha: float, beta: float, sco
     the auto rule of ``filter=None``, which never hands an entry what it refuses."""
     scaling = _l2_scaling_ok(alpha, beta)
     if size is None:
-        if isinstance(filter, str) and filter == "l1":
-            if not (_l1_applies(metric, score_dtype) and scaling):
-                raise ValueError(f'{name}: filter="l1" needs PW_L1 with float64 score words, alpha finite and '
-                                 "non-zero, beta finite")
-            return "l1"
-        if isinstance(filter, str) and filter == "jaccard":
-            if not (_jaccard_applies(metric, score_dtype) and scaling):
-                raise ValueError(f'{name}: filter="jaccard" needs PW_JACCARD with float32 score words, alpha finite '
+        if isinstance(filter, str) and filter in _SAD_FILTERS:
+            f = _SAD_FILTERS[filter]
+            if not (f.applies(metric, score_dtype) and scaling):
+                raise ValueError(f'{name}: filter="{filter}" needs {f.metric} with {f.words} score words, alpha finite '
                                  "and non-zero, beta finite")
-            return "jaccard"
+            return filter
         if filter:
             if not (_l2_applies(metric, score_dtype) and (scaling or not l2_scaling)):
                 raise ValueError(f"{name}: filter=True needs PW_L2 with float64 score words"
@@ -476,11 +463,10 @@ def _filter_route(name: str, filter, metric: int, alpha: float, beta: float, sco
     pairs, d, sets_ok = size
     if filter is not None or not scaling:
         return None
-    if _l1_applies(metric, score_dtype):
-        return "l1" if L1_FILTER_MIN_PAIRS is not None and pairs >= L1_FILTER_MIN_PAIRS and d <= L1_D_MAX else None
-    if _jaccard_applies(metric, score_dtype):
-        return ("jaccard" if JACCARD_FILTER_MIN_PAIRS is not None and pairs >= JACCARD_FILTER_MIN_PAIRS
-                and d <= L1_D_MAX else None)
+    for route, f in _SAD_FILTERS.items():
+        if f.applies(metric, score_dtype):
+            min_pairs = globals()[f.min_pairs]  # (read at call time; None: never automatically)
+            return route if min_pairs is not None and pairs >= min_pairs and d <= L1_D_MAX else None
     return "l2" if _l2_applies(metric, score_dtype) and pairs >= L2_FILTER_MIN_PAIRS and sets_ok else None
 
 
@@ -491,11 +477,22 @@ def l1_pack_size(n: int, d: int) -> Tuple[int, int]:
     return n_pad.value, d_pad.value
 
 
+def _sad_count_workspace(route: str, band_cap: int) -> int:
+    """Bytes of workspace the route's count entry needs for a band list of ``band_cap`` pairs (host only: no launch)."""
+    entry = _SAD_FILTERS[route].entry + "_workspace"
+    n = C.c_int64()
+    check(getattr(lib, entry)(int(band_cap), C.byref(n)), entry)
+    return n.value
+
+
 def l1_count_workspace(band_cap: int) -> int:
     """Bytes of workspace ``cmve_l1_count`` needs for a band list of ``band_cap`` pairs (host only: no launch)."""
-    n = C.c_int64()
-    check(lib.cmve_l1_count_workspace(int(band_cap), C.byref(n)), "cmve_l1_count_workspace")
-    return n.value
+    return _sad_count_workspace("l1", band_cap)
+
+
+def jaccard_count_workspace(band_cap: int) -> int:
+    """Bytes of workspace ``cmve_jaccard_count`` needs for a band list of ``band_cap`` pairs (host only: no launch)."""
+    return _sad_count_workspace("jaccard", band_cap)
 
 
 def l1_grid(x: torch.Tensor, grid: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -570,30 +567,42 @@ def _l1_sets(a, b, a_set: Optional["L1Set"], b_set: Optional["L1Set"], cls=None)
     return cls(a, grid=grid), cls(b, grid=grid)
 
 
-def _l1_count_call(h, a_set: "L1Set", b_set: "L1Set", alpha, beta, row, col, ws, ws_bytes: int, stats):
-    """``cmve_l1_count`` (row / col / ws / stats as ``_count_tail``)."""
-    a, b = a_set.raw, b_set.raw
-    check(lib.cmve_l1_count(h, _ptr(a), _dtype_code(a), _pw_ld(a), a_set.n, _ptr(a_set.codes), _ptr(a_set.err),
-                            _ptr(b), _dtype_code(b), _pw_ld(b), b_set.n, _ptr(b_set.codes), _ptr(b_set.err), a_set.d,
-                            _ptr(a_set.grid), float(alpha), float(beta), *_count_tail(row, col, ws, ws_bytes, stats)),
-          "cmve_l1_count")
+class _SadFilter(NamedTuple):
+    """A SAD filter as every entry sees it: what it speaks for, what it packs and what it calls."""
+    metric: str  # the ``_lib`` name of the one metric it speaks for ...
+    score_dtype: torch.dtype  # ... with these score words, and with nothing else
+    set_cls: type  # a packed side
+    min_pairs: str  # the module-level auto threshold, by name: read at call time (the tests patch it)
+    entry: str  # the C count entry; its workspace entry is ``entry + "_workspace"``
+    extras: Tuple[str, ...]  # the per-set arrays the count entry takes after the codes and the errors
+
+    words = property(lambda self: str(self.score_dtype).split(".")[-1])  # as the refusals name the score words
+
+    def applies(self, metric: int, score_dtype) -> bool:
+        return metric == getattr(_lib, self.metric) and score_dtype == self.score_dtype
 
 
-def jaccard_count_workspace(band_cap: int) -> int:
-    """Bytes of workspace ``cmve_jaccard_count`` needs for a band list of ``band_cap`` pairs (host only: no launch)."""
-    n = C.c_int64()
-    check(lib.cmve_jaccard_count_workspace(int(band_cap), C.byref(n)), "cmve_jaccard_count_workspace")
-    return n.value
+# the routes of ``_filter_route`` that are SAD filters (K22, K24), in the order the auto rule asks them
+_SAD_FILTERS = {
+    "l1": _SadFilter("PW_L1", torch.float64, L1Set, "L1_FILTER_MIN_PAIRS", "cmve_l1_count", ()),
+    "jaccard": _SadFilter("PW_JACCARD", torch.float32, JaccardSet, "JACCARD_FILTER_MIN_PAIRS",
+                          "cmve_jaccard_count", ("qsum", "asum")),
+}
 
 
-def _jaccard_count_call(h, a_set: "JaccardSet", b_set: "JaccardSet", alpha, beta, row, col, ws, ws_bytes: int, stats):
-    """``cmve_jaccard_count`` (row / col / ws / stats as ``_count_tail``; the items' words are float32 values)."""
-    a, b = a_set.raw, b_set.raw
-    check(lib.cmve_jaccard_count(h, _ptr(a), _dtype_code(a), _pw_ld(a), a_set.n, _ptr(a_set.codes), _ptr(a_set.err),
-                                 _ptr(a_set.qsum), _ptr(a_set.asum), _ptr(b), _dtype_code(b), _pw_ld(b), b_set.n,
-                                 _ptr(b_set.codes), _ptr(b_set.err), _ptr(b_set.qsum), _ptr(b_set.asum), a_set.d,
-                                 _ptr(a_set.grid), float(alpha), float(beta),
-                                 *_count_tail(row, col, ws, ws_bytes, stats)), "cmve_jaccard_count")
+def _sad_count_call(route: str, h, a_set: "L1Set", b_set: "L1Set", alpha, beta, row, col, ws, ws_bytes: int, stats):
+    """The route's count entry (row / col / ws / stats as ``_count_tail``; jaccard's item words are float32 values)."""
+    f = _SAD_FILTERS[route]
+
+    def side(s):
+        return (_ptr(s.raw), _dtype_code(s.raw), _pw_ld(s.raw), s.n, _ptr(s.codes), _ptr(s.err),
+                *(_ptr(getattr(s, x)) for x in f.extras))
+    check(getattr(lib, f.entry)(h, *side(a_set), *side(b_set), a_set.d, _ptr(a_set.grid), float(alpha), float(beta),
+                                *_count_tail(row, col, ws, ws_bytes, stats)), f.entry)
+
+
+_l1_count_call = functools.partial(_sad_count_call, "l1")            # (the names the bench tools call)
+_jaccard_count_call = functools.partial(_sad_count_call, "jaccard")
 
 
 class _PairwisePositions:
@@ -641,8 +650,8 @@ class _PairwisePositions:
                                        (na * nb, a.shape[1], True))
         sc = None
         if route and na and nb and ritems + citems:
-            run = {"l1": self._filtered_l1, "jaccard": self._filtered_jaccard, "l2": self._filtered}[route]
-            sc = run(a, b, alpha, beta, sides)
+            sc = (self._filtered(a, b, alpha, beta, sides) if route == "l2"
+                  else self._filtered_sad(route, a, b, alpha, beta, sides))
         if sc is None:
             nbytes = pairwise_positions_workspace(na, nb, ritems, citems, metric)
             ws = torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=dev)
@@ -707,25 +716,14 @@ class _PairwisePositions:
             start += items
         return buf
 
-    def _filtered_l1(self, a, b, alpha, beta, sides):
-        """The K22 route into the sides' position buffers; the items' scores (host).  ONE ``cmve_l1_count`` call:
-        a band list that overflows is resolved on the device (``fallback``: the canonical count ran), never redone."""
-        h = handle(a.device)
-        sa, sb = _l1_sets(a, b, None, None)
-        run = self._filter_pass(a, b, _lib.PW_L1, alpha, beta, sides)
-        sc, st = run(lambda *tail: _l1_count_call(h, sa, sb, alpha, beta, *tail),
-                     l1_count_workspace(l2_band_cap(a.shape[0] * b.shape[0])))
-        self.filter_stats = dict(st, redone=False, fallback=bool(st["overflow"]))
-        return sc
-
-    def _filtered_jaccard(self, a, b, alpha, beta, sides):
-        """The K24 route into the sides' position buffers; the items' words (host).  ONE ``cmve_jaccard_count`` call,
-        as ``_filtered_l1``: an overflowing band list is resolved on the device, never redone."""
-        h = handle(a.device)
-        sa, sb = _l1_sets(a, b, None, None, JaccardSet)
-        run = self._filter_pass(a, b, _lib.PW_JACCARD, alpha, beta, sides, torch.float32)
-        sc, st = run(lambda *tail: _jaccard_count_call(h, sa, sb, alpha, beta, *tail),
-                     jaccard_count_workspace(l2_band_cap(a.shape[0] * b.shape[0])))
+    def _filtered_sad(self, route, a, b, alpha, beta, sides):
+        """The K22 / K24 route into the sides' position buffers; the items' scores (host).  ONE count call: a band
+        list that overflows is resolved on the device (``fallback``: the canonical count ran), never redone."""
+        f, h = _SAD_FILTERS[route], handle(a.device)
+        sa, sb = _l1_sets(a, b, None, None, f.set_cls)
+        run = self._filter_pass(a, b, getattr(_lib, f.metric), alpha, beta, sides, f.score_dtype)
+        sc, st = run(lambda *tail: _sad_count_call(route, h, sa, sb, alpha, beta, *tail),
+                     _sad_count_workspace(route, l2_band_cap(a.shape[0] * b.shape[0])))
         self.filter_stats = dict(st, redone=False, fallback=bool(st["overflow"]))
         return sc
 
@@ -882,12 +880,9 @@ def pairwise_count(a, b, metric: int, alpha: float, beta: float, score_dtype, ro
         elif band.dtype != torch.int64 or not band.is_contiguous() or band.device != dev:
             raise TypeError("pairwise_count: band is a contiguous int64 tensor on the rows' device")
         stats = torch.empty(4, dtype=torch.int64, device=dev)
-    if route == "l1":
-        a_l1, b_l1 = _l1_sets(a, b, a_l1, b_l1)
-        _l1_count_call(handle(dev), a_l1, b_l1, alpha, beta, sides[0], sides[1], band, _nbytes(band), stats)
-    elif route == "jaccard":
-        a_l1, b_l1 = _l1_sets(a, b, a_l1, b_l1, JaccardSet)
-        _jaccard_count_call(handle(dev), a_l1, b_l1, alpha, beta, sides[0], sides[1], band, _nbytes(band), stats)
+    if route in _SAD_FILTERS:
+        a_l1, b_l1 = _l1_sets(a, b, a_l1, b_l1, _SAD_FILTERS[route].set_cls)
+        _sad_count_call(route, handle(dev), a_l1, b_l1, alpha, beta, sides[0], sides[1], band, _nbytes(band), stats)
     elif route == "l2":
         if a_l1 is not None or b_l1 is not None:
             raise TypeError("pairwise_count: an L1Set is packed for filter=\"l1\"; the Euclidean filter takes a RowSet")
@@ -1118,7 +1113,7 @@ def pairwise_topk(q, g, metric: int, alpha: float, beta: float, score_dtype, k: 
         if _l2_applies(metric, score_dtype):
             if l2_topk_auto(n_q, n_g, g_set is not None) and _l2_set_ok(q_set) and _l2_set_ok(g_set):
                 route = "l2"
-        elif _l1_applies(metric, score_dtype):
+        elif _SAD_FILTERS["l1"].applies(metric, score_dtype):
             if l1_topk_auto(n_q, n_g, g_l1 is not None) and q.shape[1] <= L1_D_MAX:
                 route = "l1"
     topk_stats = None

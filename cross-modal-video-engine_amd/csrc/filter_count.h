@@ -4,8 +4,10 @@
 //   FltLists / FltBand   the caller's lists and band list, as every entry, launch and kernel argument carries them
 //   flt_check_lists      what every count entry asks of the lists (cmve_pairwise_count included)
 //   flt_count_run        the host body: checks, memsets, NaN items, the filter's main launch, fix-up, resolve
-// A filter supplies its own operands' checks and a main launch.  The two main kernels keep an epilogue each (the same
-// algorithm on two thread layouts): written once as a force-inlined template it cost l2f_main_kernel 6% (DESIGN s4).
+// A filter supplies its own operands' checks and a main launch.  The two SAD filters share one kernel body and one
+// epilogue (sad_count.h: the same tile, thread layout and occupancy under a small policy); l2f_main_kernel keeps an
+// epilogue of its own (the same algorithm on another thread layout, at 256 VGPRs): written once as a force-inlined
+// template it cost that kernel 6% (DESIGN s4).
 #ifndef CMVE_FILTER_COUNT_H
 #define CMVE_FILTER_COUNT_H
 #include "l2_filter_tile.h"
@@ -33,7 +35,7 @@ struct FltBand {
 };
 
 // what flt_count_run hands a filter's main launch beside the filter's own operands (l2f_main_kernel takes it as it
-// is; l1f_main_kernel keeps the flat argument block it is tuned on and is filled from it)
+// is; the SAD count kernels keep a flat argument block whose common prefix sad_count_args fills from it)
 struct FltArgs {
   int64_t na, nb;
   double alpha, beta;

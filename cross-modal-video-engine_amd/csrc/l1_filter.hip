@@ -13,12 +13,11 @@
 //   l1f_grid_kernel  min / max of the eligible elements into the two grid words (integer atomics on the words' bits:
 //                    order-independent), accumulating so that two sets can share one grid
 //   l1f_pack_kernel  rows -> codes in the tiled order of l1_filter_tile.h, and the rows' errors
-//   l1f_main_kernel  128 x 128 tile, 256 threads of 8 x 8 u32 accumulators: the SADs are l1f_sad_tile's
-//                    (l1_filter_tile.h; the one K loop, shared with K23's l1t_pass_kernel); fp64 epilogue as
-//                    l2f_main_kernel's: interval test against each item, band append, counts (shuffle / LDS partial
-//                    sums, one integer atomic per (item, tile): bit-reproducible)
-#include "filter_count.h"
-#include "l1_filter_tile.h"
+//   l1f_main_kernel  sad_count.h's kernel body (128 x 128 tile, 256 threads of 8 x 8 u32 accumulators from
+//                    l1f_sad_tile, the one K loop shared with K23's l1t_pass_kernel; fp64 epilogue: interval test
+//                    against each item, band append, counts, bit-reproducible) under the policy L1fCount: a row's
+//                    error, l2f_thresholds, l1f_interval and its two-bound comparisons
+#include "sad_count.h"
 
 namespace cmve {
 namespace {
@@ -124,240 +123,39 @@ __global__ __launch_bounds__(256) void l1f_pack_kernel(const T* __restrict__ X, 
   }
 }
 
-// ---- the count -----------------------------------------------------------------------------------------------------------
-struct L1fArgs {
-  const uint32_t* a_codes;  // tiled (l1_filter_tile.h)
-  const uint32_t* b_codes;
-  const double* a_err;
-  const double* b_err;
-  const double* grid;
-  int64_t na, nb;
-  int nkt;  // K tiles
-  double alpha, beta, rho, lim;
-  const int64_t* row_off;
-  const double* row_sc;
-  int32_t* row_pos;
-  const int64_t* col_off;
-  const double* col_sc;
-  int32_t* col_pos;
-  int2* band;
-  int64_t cap;
-  l2f_u64* stats;  // {decided, band found, band re-scored, overflow}
-  int tiles_a, tiles_b;
+// ---- the count: sad_count.h's kernel under the L1 policy ----------------------------------------------------------------
+struct L1fCount {
+  struct Args : SadArgs {
+    double rho, lim;
+  };
+  static constexpr int NS = 1;  // a side carries its row error
+  struct Iv {
+    double dlo, dhi;
+  };
+  template <bool B>
+  static __device__ __forceinline__ void side(const Args& a, bool v, int64_t i, double, double, double (&t)[NS]) {
+    t[0] = v ? (B ? a.b_err : a.a_err)[i] : (double)NAN;  // a row beyond the set: no interval
+  }
+  // (below / not-below thresholds)
+  static __device__ __forceinline__ void thresholds(const Args& a, double w, double& tb, double& tn) {
+    l2f_thresholds<false>(w, a.alpha, a.beta, a.rho, tb, tn);
+  }
+  static __device__ __forceinline__ Iv interval(const Args& a, uint32_t sad, double s, const double (&ea)[NS],
+                                                const double (&eb)[NS]) {
+    Iv iv;
+    l1f_interval(sad, s, ea[0], eb[0], a.lim, iv.dlo, iv.dhi);
+    return iv;
+  }
+  static __device__ __forceinline__ bool has(const Iv& iv) { return iv.dlo == iv.dlo; }
+  static __device__ __forceinline__ bool below(const Iv& iv, bool pos, double tb, double) {
+    return pos ? iv.dhi < tb : iv.dlo > tb;
+  }
+  static __device__ __forceinline__ bool not_below(const Iv& iv, bool pos, double, double tn) {
+    return pos ? iv.dlo > tn : iv.dhi < tn;
+  }
 };
 
-// the epilogue's LDS, laid over the staging buffers once the K loop is done
-struct L1fEpi {
-  double ae[L1F_BM], be[L1F_BN];                              // row errors of the tile's rows / columns
-  double rtb[L1F_BM], rtn[L1F_BM], ctb[L1F_BN], ctn[L1F_BN];  // one round's thresholds (below / not-below)
-  int64_t ro[L1F_BM], co[L1F_BN];
-  int mr[L1F_BM], mc[L1F_BN];
-  int rc[L1F_BM], cc[L1F_BN];
-  int s_m[2];
-  int band_cnt;
-  long long band_base;
-  double s;  // the grid's step, re-read per row of a round (see the epilogue)
-};
-static_assert(sizeof(L1fEpi) <= L1F_SMEM, "the epilogue's LDS fits the staging buffers");
-
-__global__ __launch_bounds__(256, 4) void l1f_main_kernel(L1fArgs a) {
-  __shared__ __attribute__((aligned(16))) char smem[L1F_SMEM];
-  const int tid = threadIdx.x, lane = tid & 63, tx = tid & 15, ty = tid >> 4;
-  int ta, tb_;
-  l2f_tile_of_block(blockIdx.x, a.tiles_a, a.tiles_b, ta, tb_);
-  const int64_t i0 = (int64_t)ta * L1F_BM, j0 = (int64_t)tb_ * L1F_BN;
-
-  // ---- the SADs: acc[u][v] of the pair (A row i0 + l1f_row(ty, u), B row j0 + l1f_row(tx, v)); the tiles' blocks lie
-  // below the sets' n_pad (a multiple of 128) and d_pad: in bounds
-  uint32_t acc[8][8];
-  l1f_sad_tile(a.a_codes + (int64_t)ta * a.nkt * L1F_TILE_DW, a.b_codes + (int64_t)tb_ * a.nkt * L1F_TILE_DW, a.nkt,
-               smem, acc);
-
-  // ---- epilogue (every wave has passed the loop's last barrier: smem is free) ------------------------------------------
-  L1fEpi& E = *(L1fEpi*)smem;
-  if (tid < 2) E.s_m[tid] = 0;
-  if (tid == 2) E.band_cnt = 0;
-  if (tid == 3) {
-    double lo_unused, s;
-    l1f_grid_of(a.grid, lo_unused, s);
-    E.s = s;
-  }
-  __syncthreads();
-  if (tid < L1F_BM) {
-    const int64_t i = i0 + tid;
-    const bool v = i < a.na;
-    E.ae[tid] = v ? a.a_err[i] : (double)NAN;  // a row beyond the set: no interval
-    const int64_t o = (v && a.row_pos) ? a.row_off[i] : 0;
-    const int m = (v && a.row_pos) ? (int)(a.row_off[i + 1] - o) : 0;
-    E.ro[tid] = o;
-    E.mr[tid] = m;
-    E.rc[tid] = 0;
-    if (m) atomicMax(&E.s_m[0], m);
-  } else {
-    const int t = tid - L1F_BM;
-    const int64_t j = j0 + t;
-    const bool v = j < a.nb;
-    E.be[t] = v ? a.b_err[j] : (double)NAN;
-    const int64_t o = (v && a.col_pos) ? a.col_off[j] : 0;
-    const int m = (v && a.col_pos) ? (int)(a.col_off[j + 1] - o) : 0;
-    E.co[t] = o;
-    E.mc[t] = m;
-    E.cc[t] = 0;
-    if (m) atomicMax(&E.s_m[1], m);
-  }
-  __syncthreads();
-  const int rounds = max(E.s_m[0], E.s_m[1]);  // block-uniform
-  // bit u * 8 + v of `valid`: the pair exists
-  uint64_t valid = 0, band = 0;
-#pragma unroll
-  for (int u = 0; u < 8; ++u)
-#pragma unroll
-    for (int v = 0; v < 8; ++v)
-      if (i0 + l1f_row(ty, u) < a.na && j0 + l1f_row(tx, v) < a.nb) valid |= 1ull << (u * 8 + v);
-
-  // one round: item `it` of every row and column list.  PASS 0 marks the pairs some item cannot decide, PASS 1
-  // counts the decided ones.
-  for (int pass = 0; pass < 2; ++pass) {
-    for (int it = 0; it < rounds; ++it) {
-      if (tid < L1F_BM) {
-        double tb = (double)NAN, tn = (double)NAN;
-        const bool has = it < E.mr[tid];
-        if (has) l2f_thresholds<false>(a.row_sc[E.ro[tid] + it], a.alpha, a.beta, a.rho, tb, tn);
-        E.rtb[tid] = tb;
-        E.rtn[tid] = tn;
-      } else {
-        const int t = tid - L1F_BM;
-        double tb = (double)NAN, tn = (double)NAN;
-        const bool has = it < E.mc[t];
-        if (has) l2f_thresholds<false>(a.col_sc[E.co[t] + it], a.alpha, a.beta, a.rho, tb, tn);
-        E.ctb[t] = tb;
-        E.ctn[t] = tn;
-      }
-      __syncthreads();
-      const bool pos = a.alpha > 0.0;
-      int ccnt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-      int rpack[2] = {0, 0};  // four rows' counts each, a byte a row (<= 8 per thread, <= 128 over the row's 16 lanes)
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        const int row = l1f_row(ty, u);
-        // a volatile read: the 64 intervals are formed again in every round, eight at a time, instead of being
-        // hoisted out of the rounds as 128 live doubles per thread
-        const double s = *(const volatile double*)&E.s;
-        const double ae = E.ae[row], rtb = E.rtb[row], rtn = E.rtn[row];
-        const bool rhas = it < E.mr[row];
-        int rcnt = 0;
-#pragma unroll
-        for (int v = 0; v < 8; ++v) {
-          const int col = l1f_row(tx, v);
-          const int bit = u * 8 + v;
-          double dlo, dhi;
-          l1f_interval(acc[u][v], s, ae, E.be[col], a.lim, dlo, dhi);
-          const bool chas = it < E.mc[col];
-          const double ctb = E.ctb[col], ctn = E.ctn[col];
-          const bool rb = pos ? dhi < rtb : dlo > rtb, rn = pos ? dlo > rtn : dhi < rtn;
-          const bool cb = pos ? dhi < ctb : dlo > ctb, cn = pos ? dlo > ctn : dhi < ctn;
-          if (pass == 0) {
-            // also a pair with no item to compare against must have an interval, so that decided + band = pairs
-            const bool okr = rhas ? (rb || rn) : (dlo == dlo);
-            const bool okc = chas ? (cb || cn) : (dlo == dlo);
-            if (!(okr && okc)) band |= 1ull << bit;
-          } else {
-            const bool live = ((valid & ~band) >> bit) & 1;
-            rcnt += (live && rhas && rb) ? 1 : 0;
-            ccnt[v] += (live && chas && cb) ? 1 : 0;
-          }
-        }
-        rpack[u >> 2] += rcnt << (8 * (u & 3));
-      }
-      if (pass == 1) {
-        // rows: the 16 lanes tx = 0..15 of this wave share them
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          int p = rpack[h];
-          p += __shfl_xor(p, 1, 64);
-          p += __shfl_xor(p, 2, 64);
-          p += __shfl_xor(p, 4, 64);
-          p += __shfl_xor(p, 8, 64);
-          if (tx == 0 && p) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              const int c = (p >> (8 * r)) & 255;
-              if (c) atomicAdd(&E.rc[l1f_row(ty, 4 * h + r)], c);
-            }
-          }
-        }
-        // columns: the 4 lane groups of each of the 4 waves share them (<= 8 per thread, <= 32 per wave)
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          int p = ccnt[4 * h] | (ccnt[4 * h + 1] << 8) | (ccnt[4 * h + 2] << 16) | (ccnt[4 * h + 3] << 24);
-          p += __shfl_xor(p, 16, 64);
-          p += __shfl_xor(p, 32, 64);
-          if ((lane >> 4) == 0 && p) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              const int c = (p >> (8 * r)) & 255;
-              if (c) atomicAdd(&E.cc[l1f_row(tx, 4 * h + r)], c);
-            }
-          }
-        }
-      }
-      __syncthreads();
-      if (pass == 1) {  // one integer atomic per (item, tile)
-        if (tid < L1F_BM) {
-          const int c = E.rc[tid];
-          if (c && it < E.mr[tid]) gadd(a.row_pos + E.ro[tid] + it, (int32_t)c);
-          E.rc[tid] = 0;
-        } else {
-          const int t = tid - L1F_BM;
-          const int c = E.cc[t];
-          if (c && it < E.mc[t]) gadd(a.col_pos + E.co[t] + it, (int32_t)c);
-          E.cc[t] = 0;
-        }
-        // (the next round's threshold writes and this read touch different words; its barrier orders the counters)
-      }
-    }
-    if (pass == 0) {
-      if (rounds == 0) {  // no list in this tile: nothing to decide, but the pairs without an interval are band
-#pragma unroll
-        for (int u = 0; u < 8; ++u)
-#pragma unroll
-          for (int v = 0; v < 8; ++v) {
-            double dlo, dhi;
-            l1f_interval(acc[u][v], E.s, E.ae[l1f_row(ty, u)], E.be[l1f_row(tx, v)], a.lim, dlo, dhi);
-            if (!(dlo == dlo)) band |= 1ull << (u * 8 + v);
-          }
-      }
-      // the band pairs, once each, into the caller's list
-      band &= valid;
-      const int nband = __popcll(band);
-      int my = 0;
-      if (nband) my = atomicAdd(&E.band_cnt, nband);
-      __syncthreads();
-      if (tid == 0) {
-        const int total = E.band_cnt;
-        const int nv = (int)(min<int64_t>(L1F_BM, a.na - i0) * min<int64_t>(L1F_BN, a.nb - j0));
-        long long base = 0;
-        if (total) {
-          base = (long long)gadd(a.stats + 1, (l2f_u64)total);
-          if (base + total > a.cap) gmax(a.stats + 3, (l2f_u64)1);
-        }
-        if (nv - total) gadd(a.stats + 0, (l2f_u64)(nv - total));
-        E.band_base = base;
-      }
-      __syncthreads();
-      if (nband) {
-        long long p = E.band_base + my;
-        uint64_t b = band;
-        while (b) {
-          const int bit = __ffsll((long long)b) - 1;
-          b &= b - 1;
-          if (p < a.cap) a.band[p] = make_int2((int)(i0 + l1f_row(ty, bit >> 3)), (int)(j0 + l1f_row(tx, bit & 7)));
-          ++p;
-        }
-      }
-    }
-  }
-}
+__global__ __launch_bounds__(256, 4) void l1f_main_kernel(L1fCount::Args a) { sad_count_body<L1fCount>(a); }
 
 }  // namespace
 }  // namespace cmve
@@ -413,11 +211,7 @@ extern "C" int cmve_l1_pack(cmve_handle_t h, const void* X, int32_t dtype, int64
 }
 
 extern "C" int cmve_l1_count_workspace(int64_t band_cap, int64_t* bytes) {
-  CMVE_REQUIRE(bytes, "cmve_l1_count_workspace: NULL argument");
-  CMVE_REQUIRE(band_cap >= 0 && band_cap <= INT64_MAX / 8, "cmve_l1_count_workspace: bad band capacity (%lld)",
-               (long long)band_cap);
-  *bytes = band_cap * (int64_t)sizeof(int2);  // the band list and nothing else: (i, j) per slot
-  return CMVE_OK;
+  return sad_count_workspace("cmve_l1_count_workspace", band_cap, bytes);
 }
 
 extern "C" int cmve_l1_count(cmve_handle_t h, const void* A, int32_t a_dtype, int64_t lda, int64_t na,
@@ -429,32 +223,19 @@ extern "C" int cmve_l1_count(cmve_handle_t h, const void* A, int32_t a_dtype, in
                              int64_t ws_bytes, int64_t* stats) {
   const char* name = "cmve_l1_count";
   CMVE_REQUIRE(h && stats && (A || !na) && (B || !nb), "%s: NULL argument", name);
+  const FltRows rows{A, a_dtype, lda, na, B, b_dtype, ldb, nb, d};
   auto own_checks = [&]() -> int {
-    CMVE_REQUIRE(d > 0 && d <= L1F_D_MAX, "%s: d must be in [1, %lld] (%lld): the u32 SAD is exact up to there", name,
-                 (long long)L1F_D_MAX, (long long)d);
-    CMVE_REQUIRE(na >= 0 && nb >= 0 && na < (1ll << 31) && nb < (1ll << 31) && lda >= d && ldb >= d, "%s: bad shape",
-                 name);
-    CMVE_REQUIRE(l1f_dtype_ok(a_dtype) && l1f_dtype_ok(b_dtype), "%s: rows must be CMVE_F32/CMVE_F64", name);
-    CMVE_REQUIRE(grid && ((a_codes && a_err) || !na) && ((b_codes && b_err) || !nb),
-                 "%s: the codes, the row errors or the grid are missing (cmve_l1_grid, cmve_l1_pack)", name);
-    CMVE_REQUIRE(((((uintptr_t)a_codes) | ((uintptr_t)b_codes)) & 15) == 0, "%s: codes must be 16-byte aligned", name);
-    return CMVE_OK;
+    return sad_count_checks(name, d, rows, a_codes, b_codes, grid, a_codes && a_err, b_codes && b_err,
+                            "the codes, the row errors or the grid are missing (cmve_l1_grid, cmve_l1_pack)");
   };
   auto main_launch = [&](hipStream_t st, const FltArgs& f) {
-    int64_t n_pad = 0, d_pad = 0;
-    l1f_pads(na, d, n_pad, d_pad);
-    // (the kernel's own flat argument block: embedding FltArgs moved its scalar loads and cost the kernel 1.2%)
-    const FltLists& l = f.lists;
-    const L1fArgs g{(const uint32_t*)a_codes, (const uint32_t*)b_codes, a_err, b_err, grid, f.na, f.nb,
-                    (int)(d_pad / L1F_BK), f.alpha, f.beta,
-                    2.0 * ((double)d + 16.0) * L2F_U,    // rho: DESIGN s4 (K22)
-                    (1e300 - fabs(beta)) / fabs(alpha),  // lim: below it alpha * S + beta cannot overflow
-                    l.row_off, l.row_sc, l.row_pos, l.col_off, l.col_sc, l.col_pos, f.band.band, f.band.cap,
-                    f.band.stats, f.tiles_a, f.tiles_b};
+    const L1fCount::Args g{sad_count_args(f, a_codes, a_err, b_codes, b_err, grid, d),
+                           2.0 * ((double)d + 16.0) * L2F_U,     // rho: DESIGN s4 (K22)
+                           (1e300 - fabs(beta)) / fabs(alpha)};  // lim: below it alpha * S + beta cannot overflow
     hipLaunchKernelGGL(l1f_main_kernel, dim3((unsigned)(f.tiles_a * f.tiles_b)), dim3(256), 0, st, g);
   };
   // (resolve: an overflowing list is resolved on the device, from the start -- no entry leaves it to the host)
-  return flt_count_run(name, "l1_count", h, CMVE_PW_L1, FltRows{A, a_dtype, lda, na, B, b_dtype, ldb, nb, d}, alpha, beta,
+  return flt_count_run(name, "l1_count", h, CMVE_PW_L1, rows, alpha, beta,
                        {row_off, row_sc, row_items, row_n, row_pos, col_off, col_sc, col_items, col_n, col_pos}, ws,
                        ws_bytes, stats, true, own_checks, main_launch);
 }

@@ -441,6 +441,46 @@ def test_a_tile_with_no_list_in_it():
     assert st["rescored"] == st["band"] and st["overflow"] == 0
 
 
+# ---- 7b. the seams of the one count body (sad_count.h) ---------------------------------------------------------------------
+
+def _seams():
+    """129 x 257 x 33: 2 x 3 tiles whose last row tile and last column tile hold ONE row, d no multiple of the
+    32-element K tile (two K tiles).  Row lists of 0, 1, 3 and 5 items side by side in a tile (the tile's rounds exceed
+    most lists' lengths); the only column list is that of row 256, the one row of the last column tile, and names row
+    128, the one row of the last row tile.  Ten exact duplicates and a NaN row put pairs into the band."""
+    na, nb, d = 129, 257, 33
+    rng = np.random.default_rng(na * nb)
+    b = rng.standard_normal((nb, d))
+    pick = rng.integers(0, nb, na)
+    a = b[pick] + 0.5 * rng.standard_normal((na, d))
+    a, b = np.abs(a), np.abs(b)
+    b[130:140] = b[0:10]
+    a[5, 3] = np.nan
+    rows = [([int(pick[i])] + list(map(int, rng.integers(0, nb, 4))))[:(0, 1, 3, 5)[i % 4]] for i in range(na)]
+    rows[128] = [int(pick[128]), 256, 0, 130, 256]
+    cols = [[] for _ in range(nb)]
+    cols[256] = [128, 3, 128, 7, 0]
+    return a, b, rows, cols
+
+
+@pytest.fixture(scope="module")
+def seams():
+    return _seams()
+
+
+@pytest.mark.parametrize("alpha", [1.0, -1.0], ids=["a1", "a-1"])
+@pytest.mark.parametrize("lists", ["both", "no_rows", "no_cols"])
+def test_seams_of_the_one_count_body(seams, lists, alpha):
+    a, b, rows, cols = seams
+    pairs = a.shape[0] * b.shape[0]
+    f, e = _both(a, b, alpha, 0.0, None if lists == "no_rows" else rows, None if lists == "no_cols" else cols)
+    _assert_same_words(f, e)
+    st = f.filter_stats
+    print("%s: decided %d, band %d (%.2f%%)" % (lists, st["decided"], st["band"], 100.0 * st["band"] / pairs))
+    _assert_accounted(st, pairs)                    # decided + band == 129 * 257, rescored == band, overflow == 0
+    assert pairs == 129 * 257 and 0 < st["band"] < pairs // 8
+
+
 # ---- 8. dispatch -------------------------------------------------------------------------------------------------------------
 
 def test_dispatch(adversarial, monkeypatch):

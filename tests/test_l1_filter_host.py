@@ -83,6 +83,47 @@ def test_filter_l1_refuses_before_any_device_call():
     assert engine._l2_count_stats(np.array([7, 5, 3, 1], np.int64)) == dict(decided=7, band=5, rescored=3, overflow=1)
 
 
+def test_every_sad_filter_record_routes_with_the_words_it_had(monkeypatch):
+    """The routes ``_filter_route`` gives for the SAD filters, record by record: the texts and results are literals."""
+    import torch
+    from cmve import _lib, engine
+    want = {"l1": (_lib.PW_L1, torch.float64, torch.float32, "L1_FILTER_MIN_PAIRS", 8192 * 8192,
+                   'x: filter="l1" needs PW_L1 with float64 score words, alpha finite and non-zero, beta finite'),
+            "jaccard": (_lib.PW_JACCARD, torch.float32, torch.float64, "JACCARD_FILTER_MIN_PAIRS", 8192 * 8192,
+                        'x: filter="jaccard" needs PW_JACCARD with float32 score words, alpha finite and non-zero, '
+                        "beta finite")}
+    assert list(engine._SAD_FILTERS) == list(want)
+    for route in engine._SAD_FILTERS:
+        metric, dt, other_dt, min_name, min_pairs, text = want[route]
+        assert getattr(engine, min_name) == min_pairs
+        for l2_scaling in (False, True):
+            assert engine._filter_route("x", route, metric, -1.0, 0.25, dt, l2_scaling) == route
+            for m, t, alpha, beta in ((_lib.PW_L2, dt, 1.0, 0.0), (_lib.PW_SQ_L2, dt, 1.0, 0.0), (metric, other_dt, 1.0, 0.0),
+                                      (metric, dt, 0.0, 0.0), (metric, dt, float("nan"), 0.0),
+                                      (metric, dt, float("inf"), 0.0), (metric, dt, 1.0, float("inf"))):
+                with pytest.raises(ValueError) as ei:
+                    engine._filter_route("x", route, m, alpha, beta, t, l2_scaling)
+                assert str(ei.value) == text
+            # a forced route is settled before the sizes are known; False and True never become this route later
+            for flt in (route, False, True):
+                assert engine._filter_route("x", flt, metric, 1.0, 0.0, dt, l2_scaling, (1 << 40, 64, True)) is None
+
+        def auto(pairs, d=64, m=metric, t=dt, alpha=1.0, beta=0.0):
+            return engine._filter_route("x", None, m, alpha, beta, t, False, (pairs, d, True))
+        assert auto(min_pairs - 1) is None and auto(min_pairs) == route and auto(1 << 40) == route
+        assert auto(min_pairs, d=65536) == route and auto(1 << 40, d=65537) is None
+        assert auto(1 << 40, t=other_dt) is None and auto(1 << 40, alpha=0.0) is None
+        assert auto(1 << 40, beta=float("nan")) is None
+        monkeypatch.setattr(engine, min_name, 1)       # the name is read at call time
+        assert auto(0) is None and auto(1) == route
+        monkeypatch.setattr(engine, min_name, None)    # None: never automatically; the forced route stays
+        assert auto(1 << 62) is None
+        assert engine._filter_route("x", route, metric, 1.0, 0.0, dt, False) == route
+        monkeypatch.undo()
+    # before the sizes are known nothing is automatic
+    assert engine._filter_route("x", None, _lib.PW_L1, 1.0, 0.0, torch.float64, False) is None
+
+
 # ---- the bound of DESIGN s4 (K22), restated in numpy ---------------------------------------------------------------------
 
 U = 2.0 ** -53
