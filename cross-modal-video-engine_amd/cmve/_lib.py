@@ -169,6 +169,9 @@ SIGNATURES = {
     "cmve_l1_topk_workspace": (C.c_int, [_i64, _i64, _i32, _i64, _i64, _P(_i64)]),
     "cmve_l1_topk": (C.c_int, [_vp, _vp, _i32, _i64, _i64, _vp, _vp, _vp, _i32, _i64, _i64, _vp, _vp, _i64, _vp, _f64,
                                _f64, _i32, _i64, _i64, _vp, _i64, _vp, _vp, _vp]),
+    "cmve_jaccard_topk_workspace": (C.c_int, [_i64, _i64, _i32, _i64, _i64, _P(_i64)]),
+    "cmve_jaccard_topk": (C.c_int, [_vp, _vp, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _vp, _vp,
+                                    _vp, _vp, _i64, _vp, _f64, _f64, _i32, _i64, _i64, _vp, _i64, _vp, _vp, _vp]),
     "cmve_pairwise_topk_workspace": (C.c_int, [_i64, _i64, _i32, _i32, _P(_i64), _P(_i64)]),
     "cmve_pairwise_topk": (C.c_int, [_vp, _vp, _i32, _i64, _i64, _vp, _i32, _i64, _i64, _i64, _i32, _f64, _f64, _i32,
                                      _i32, _i32, _vp, _i64, _vp, _vp]),

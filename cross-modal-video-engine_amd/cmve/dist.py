@@ -479,6 +479,7 @@ def ap_from_positions(positions) -> float:
 
 _L2_MEASURES = ('euclidean', 'l2', 'l2_norm')  # CMVE_PW_L2 with fp64 score words: what K19 - K21 filter
 _L1_MEASURES = ('l1', 'l1_norm')  # CMVE_PW_L1 with fp64 score words: what K22 / K23 filter (filter="l1")
+_JACCARD_MEASURES = ('jaccard',)  # CMVE_PW_JACCARD with float32 score words: what K24 / K25 filter (filter="jaccard")
 
 
 class ShardedGallery:
@@ -491,7 +492,7 @@ class ShardedGallery:
 
     ``comm``: a communicator (default: TorchComm over torch.distributed's process group).
     ``filter=True`` needs a Euclidean measure: ValueError under any other, cosine included; ``filter="l1"`` needs
-    l1 / l1_norm: ValueError under any other."""
+    l1 / l1_norm, ``filter="jaccard"`` needs jaccard: ValueError under any other."""
 
     def __new__(cls, *args, **kw):
         if cls is ShardedGallery:  # measure: __init__'s 10th argument
@@ -504,6 +505,9 @@ class ShardedGallery:
         if isinstance(filter, str) and filter == "l1":
             if measure not in _L1_MEASURES:
                 raise ValueError(f'ShardedGallery: filter="l1" needs an L1 measure {_L1_MEASURES}, not {measure!r}')
+        elif isinstance(filter, str) and filter == "jaccard":
+            if measure not in _JACCARD_MEASURES:
+                raise ValueError(f'ShardedGallery: filter="jaccard" needs the jaccard measure, not {measure!r}')
         elif filter and measure not in _L2_MEASURES:
             raise ValueError(f"ShardedGallery: filter=True needs a Euclidean measure {_L2_MEASURES}, not {measure!r}")
         if not isinstance(self, _family(measure)):  # a family built directly, or a subclass of this base alone
@@ -787,8 +791,11 @@ class MeasureShardedGallery(ShardedGallery):
     (``engine.pairwise_count(filter="l1")``: the same words, an overflow resolved on the device) and K23's top-k
     (``engine.pairwise_topk(filter="l1")``) over this shard, packed once as an ``engine.L1Set`` on its own grid by the
     first call that needs it; None -- the count from ``engine.L1_FILTER_MIN_PAIRS`` (d <= ``engine.L1_D_MAX``), the
-    top-k from ``engine.l1_topk_auto``.  ``band_cap`` / ``filter_stats`` as above.  jaccard has no filter here: its
-    count filter (K24, ``engine.pairwise_count(filter="jaccard")``) serves an unsharded gallery."""
+    top-k from ``engine.l1_topk_auto``.  ``band_cap`` / ``filter_stats`` as above.
+    ``filter`` (jaccard): the same with ``"jaccard"`` -- K24's count (``engine.pairwise_count(filter="jaccard")``) and
+    K25's top-k (``engine.pairwise_topk(filter="jaccard")``) over this shard, packed once as an ``engine.JaccardSet``
+    on its own grid; None -- the count from ``engine.JACCARD_FILTER_MIN_PAIRS`` (d <= ``engine.L1_D_MAX``), the top-k
+    from ``engine.jaccard_topk_auto``."""
 
     # ---- shard-local arithmetic (HIP kernels) ----
     def _init_shard(self, local_embs, device, filter, band_cap, **_):
@@ -801,8 +808,10 @@ class MeasureShardedGallery(ShardedGallery):
         self.shard = self._pw_rows(local_embs)  # resident, unnormalised, in the measure's input dtype
         self.device = self.shard.device
         self.n = int(self.shard.shape[0])
-        # the filter family that speaks for the measure: "l2" (K19 - K21, a RowSet), "l1" (K22 / K23, an L1Set) or None
-        self._pw_family = "l2" if self.measure in _L2_MEASURES else "l1" if self.measure in _L1_MEASURES else None
+        # the filter family that speaks for the measure: "l2" (K19 - K21, a RowSet), "l1" (K22 / K23, an L1Set),
+        # "jaccard" (K24 / K25, a JaccardSet) or None; the last two are the SAD families: ``filter`` names them
+        self._pw_family = ("l2" if self.measure in _L2_MEASURES else "l1" if self.measure in _L1_MEASURES
+                           else "jaccard" if self.measure in _JACCARD_MEASURES else None)
         self._pw_packed = None  # the shard's pack for its family's filters, made by the first call that needs it
         self._pw_filter_off = False  # latched by a top-k the filter handed back whole, or a count whose band
         #                              exceeds 1/8 of the pairs: this shard stays on fp64
@@ -829,26 +838,33 @@ class MeasureShardedGallery(ShardedGallery):
         is given, so there is no second copy of the shard."""
         if self._pw_packed is None:
             self._pw_packed = (engine.L1Set(self.shard) if self._pw_family == "l1"  # (on the shard's own grid)
+                               else engine.JaccardSet(self.shard) if self._pw_family == "jaccard"
                                else engine.RowSet(self.shard, eps=0.0, with_lo=False, device=self.device))
         return self._pw_packed
 
+    def _pw_sad(self) -> bool:
+        """The measure's filters are the SAD ones (K22 - K25): ``filter`` names the family, the pack is on a grid."""
+        return self._pw_family in ("l1", "jaccard")
+
     def _pw_forced(self) -> bool:
-        """The constructor's filter names this family's filter (True: Euclidean, "l1": L1)."""
+        """The constructor's filter names this family's filter (True: Euclidean, "l1": L1, "jaccard": jaccard)."""
         f = self._pw_filter
-        return (isinstance(f, str) and f == "l1") if self._pw_family == "l1" else bool(f)
+        return (isinstance(f, str) and f == self._pw_family) if self._pw_sad() else bool(f)
 
     def _pw_count_auto(self, pairs: int) -> bool:
         """filter=None: the family's count filter pays from its measured number of pairs (None there: never)."""
-        if self._pw_family == "l1":
-            lo = engine.L1_FILTER_MIN_PAIRS if self.shard.shape[1] <= engine.L1_D_MAX else None
+        if self._pw_sad():
+            lo = engine.L1_FILTER_MIN_PAIRS if self._pw_family == "l1" else engine.JACCARD_FILTER_MIN_PAIRS
+            lo = lo if self.shard.shape[1] <= engine.L1_D_MAX else None
         else:
             lo = engine.L2_FILTER_MIN_PAIRS
         return lo is not None and pairs >= lo
 
     def _pw_count(self, q, row, col):
         """ONE pass over (all captions) x (this shard): (row positions | None, column positions | None), int32.
-        With the family's filter due the count is ``cmve_l2_count_resolved``'s (K21, Euclidean) or ``cmve_l1_count``'s
-        (K22, l1 / l1_norm): the same words whatever the band list does -- an overflow is resolved on the device --
+        With the family's filter due the count is ``cmve_l2_count_resolved``'s (K21, Euclidean), ``cmve_l1_count``'s
+        (K22, l1 / l1_norm) or ``cmve_jaccard_count``'s (K24): the same words whatever the band list does -- an
+        overflow is resolved on the device --
         its counters kept on the device as this pass's ``filter_stats``."""
         self._pw_stats = None
         pairs = int(q.shape[0]) * self.n
@@ -860,7 +876,7 @@ class MeasureShardedGallery(ShardedGallery):
             cap = engine.l2_band_cap(pairs) if self._pw_band_cap is None else int(self._pw_band_cap)
             self._pw_band = torch.empty(cap, dtype=torch.int64, device=self.device)
         rpos, cpos, self._pw_stats = engine.pairwise_count(q, self._pw_pack(), *self._pw_spec(), row=row, col=col,
-                                                           filter="l1" if self._pw_family == "l1" else True,
+                                                           filter=self._pw_family if self._pw_sad() else True,
                                                            band=self._pw_band, return_stats=True)
         self._pw_pairs = pairs
         return rpos, cpos
@@ -894,20 +910,22 @@ class MeasureShardedGallery(ShardedGallery):
     def _pw_topk(self, q, k: int):
         """This shard's (local ids int64, errors fp64) [n_q, k] on the device, (error asc, id asc), NaN last.
         Under a Euclidean measure engine.pairwise_topk may take the K20 filter (auto), under l1 / l1_norm the K23
-        filter (auto, or forced by ``filter="l1"``; never under ``filter=False``); what it leaves unresolved is
-        finished on the fp64 route here, on this shard alone: the words are the same and no flag rides a collective."""
-        l1 = self._pw_family == "l1"
-        if self._pw_filter_off or (l1 and self._pw_filter is False):
+        filter and under jaccard the K25 filter (auto, or forced by ``filter="l1"`` / ``filter="jaccard"``; never under
+        ``filter=False``); what it leaves unresolved is finished on the K18 route here, on this shard alone: the words
+        are the same and no flag rides a collective."""
+        sad = self._pw_sad()
+        if self._pw_filter_off or (sad and self._pw_filter is False):
             return engine.pairwise_topk(q, self.shard, *self._pw_spec(), k, to_host=False, filter=False)
-        forced = l1 and self._pw_forced()
-        auto = engine.l1_topk_auto if l1 else engine.l2_topk_auto
-        fits = not l1 or self.shard.shape[1] <= engine.L1_D_MAX  # (beyond it auto stays on fp64; forced: ValueError)
+        forced = sad and self._pw_forced()
+        auto = {"l1": engine.l1_topk_auto, "jaccard": engine.jaccard_topk_auto}.get(self._pw_family,
+                                                                                    engine.l2_topk_auto)
+        fits = not sad or self.shard.shape[1] <= engine.L1_D_MAX  # (beyond it auto stays on K18; forced: ValueError)
         if (self._pw_packed is None and self._pw_family is not None
                 and (forced or (fits and auto(q.shape[0], self.n, packed=True)))):
             self._pw_pack()  # ONCE, by the first call large enough for a filter
         g = self.shard if self._pw_packed is None else self._pw_packed
         idx, err, st = engine.pairwise_topk(q, g, *self._pw_spec(), k, to_host=False, return_stats=True,
-                                            filter="l1" if forced else None)
+                                            filter=self._pw_family if forced else None)
         self._pw_filter_off = st is not None and st["fallback"]
         return idx, err
 

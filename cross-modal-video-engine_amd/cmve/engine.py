@@ -1042,11 +1042,75 @@ def l1_topk(q: "L1Set", g: "L1Set", alpha: float, beta: float, k: int, cand_cap:
                                l1_topk_workspace(q, g, k, cap, sample_rows), ws, g.device)
 
 
-def _topk_filtered(metric: int, filtered, q, g, alpha, beta, k):
-    """A filtered route of ``pairwise_topk`` (K20: ``metric`` PW_L2, K23: PW_L1): ``filtered()`` is the filter's call
-    and returns (idx, err, stats) as ``l2_topk`` / ``l1_topk`` do; q / g are the raw rows.  Returns (idx, err) on the
-    device with the same words as the fp64 route, and the ``topk_stats`` record; idx is None when the whole call has
-    to take the fp64 route."""
+JACCARD_TOPK_CAND_MAX = L2_TOPK_CAND_MAX  # cmve_jaccard_topk's limit on cand_cap: the same last launch, the same LDS
+# Auto dispatch of the K25 filter (``filter=None`` under PW_JACCARD with float32 words): a rule of its own with
+# ``l1_topk_auto``'s clauses (None in a constant switches its clause off: "never taken automatically",
+# ``filter="jaccard"`` alone runs it).  From tools/jaccard_topk_bench.py -> profiles/jaccard_topk.json (top-10, D = 1024,
+# non-negative float32 rows, alpha = -1, medians of 5 alternating repeats, K18 route / filter in ms; "wins" = by more
+# than the two spreads together; the constants were None while it ran).  Against a gallery that is already packed (a
+# JaccardSet: GalleryScorer, the sharded gallery) the filter won at 64 x 131,072 (2.45 / 1.62, spreads 0.07 + 0.01),
+# 1000 x 131,072 (28.9 / 4.52), 16,384 x 131,072 (502.6 / 70.2) and over 1,048,576 rows at every n_q: 1 (3.32 / 3.05,
+# spreads 0.01 + 0.05), 64 (17.1 / 3.76), 1000 (232.0 / 20.8); it lost at 1 x 131,072 (0.83 / 1.11: both are launch
+# gaps).  A packed gallery takes it from MIN_GALLERY rows or MIN_PAIRS pairs, the smallest sizes measured to win.  A
+# gallery given as plain rows pays the grid, both packs and the row sums inside the call (0.92 ms at 131,072 rows,
+# 5.7 ms at 1,048,576): it won at 64 x 1,048,576 (17.3 / 9.51), 1000 x 131,072 (29.0 / 5.53), 1000 x 1,048,576
+# (232.0 / 26.4) and 16,384 x 131,072 (502.8 / 71.4), lost at 64 x 131,072 (2.45 / 2.56) and at one query (0.83 / 1.97
+# and 3.30 / 8.67): plain rows take it from MIN_Q queries AND MIN_PLAIN_PAIRS pairs.  Between the measured sizes the
+# pair rules are an interpolation.
+JACCARD_TOPK_FILTER_MIN_GALLERY = 1 << 20      # packed: 1 x 1,048,576
+JACCARD_TOPK_FILTER_MIN_PAIRS = 1 << 23        # packed: 64 x 131,072
+JACCARD_TOPK_FILTER_MIN_Q = 64                 # plain rows
+JACCARD_TOPK_FILTER_MIN_PLAIN_PAIRS = 1 << 26  # plain rows: 64 x 1,048,576
+
+
+def jaccard_topk_auto(n_q: int, n_g: int, packed: bool = False) -> bool:
+    """Whether ``pairwise_topk(filter=None)`` takes the K25 filter at this size (given PW_JACCARD with float32 words);
+    ``packed``: the gallery is a JaccardSet already.  A constant left None switches its clause off."""
+    if n_q < 1 or n_g < 1:
+        return False
+    if packed:
+        return ((JACCARD_TOPK_FILTER_MIN_GALLERY is not None and n_g >= JACCARD_TOPK_FILTER_MIN_GALLERY)
+                or (JACCARD_TOPK_FILTER_MIN_PAIRS is not None and n_q * n_g >= JACCARD_TOPK_FILTER_MIN_PAIRS))
+    return (JACCARD_TOPK_FILTER_MIN_Q is not None and JACCARD_TOPK_FILTER_MIN_PLAIN_PAIRS is not None
+            and n_q >= JACCARD_TOPK_FILTER_MIN_Q and n_q * n_g >= JACCARD_TOPK_FILTER_MIN_PLAIN_PAIRS)
+
+
+def jaccard_topk_workspace(q, g, k: int, cand_cap: Optional[int] = None, sample_rows: Optional[int] = None) -> int:
+    """Bytes of workspace ``cmve_jaccard_topk`` needs (host only: no launch).  q / g: a ``JaccardSet`` or a row
+    count."""
+    n = C.c_int64()
+    check(lib.cmve_jaccard_topk_workspace(_n_rows(q), _n_rows(g), int(k),
+                                          JACCARD_TOPK_CAND_MAX if cand_cap is None else int(cand_cap),
+                                          int(sample_rows or 0), C.byref(n)), "cmve_jaccard_topk_workspace")
+    return n.value
+
+
+def jaccard_topk(q: "JaccardSet", g: "JaccardSet", alpha: float, beta: float, k: int, cand_cap: Optional[int] = None,
+                 sample_rows: Optional[int] = None, ws: Optional[torch.Tensor] = None):
+    """``cmve_jaccard_topk`` (K25): (idx int64 [n_q, k], err fp64 [n_q, k] holding float32 words) on the device and the
+    stats dict {excluded, candidates, rescored, unresolved} (one small copy to the host), as ``l1_topk``.  Both sets
+    are ``JaccardSet`` packed on ONE grid (TypeError / ValueError otherwise).  An unresolved query has
+    idx[i, 0] == -2 and the rest of its row unwritten.  k must not exceed the gallery.  ws: a caller-held device
+    workspace, used when it holds ``jaccard_topk_workspace`` bytes (a fresh one otherwise)."""
+    q, g = _l1_sets(None, None, q, g, cls=JaccardSet)
+    if q.d != g.d:
+        raise ValueError(f"jaccard_topk: dimensions differ ({q.d}, {g.d})")
+    cap = JACCARD_TOPK_CAND_MAX if cand_cap is None else int(cand_cap)
+
+    def side(s):
+        return (_ptr(s.raw), _dtype_code(s.raw), _pw_ld(s.raw), s.n, _ptr(s.codes), _ptr(s.err), _ptr(s.qsum),
+                _ptr(s.asum))
+    head = (*side(q), *side(g), g.d, _ptr(g.grid), float(alpha), float(beta), int(k), cap, int(sample_rows or 0))
+    return _filtered_topk_call(lib.cmve_jaccard_topk, "cmve_jaccard_topk", head, q.n, k,
+                               jaccard_topk_workspace(q, g, k, cap, sample_rows), ws, g.device)
+
+
+def _topk_filtered(metric: int, filtered, q, g, alpha, beta, k, score_dtype=torch.float64):
+    """A filtered route of ``pairwise_topk`` (K20: ``metric`` PW_L2, K23: PW_L1, K25: PW_JACCARD with float32 words):
+    ``filtered()`` is the filter's call and returns (idx, err, stats) as ``l2_topk`` / ``l1_topk`` do; q / g are the
+    raw rows, ``score_dtype`` the call's own (unresolved rows are re-run with it).  Returns (idx, err) on the device
+    with the same words as the K18 route, and the ``topk_stats`` record; idx is None when the whole call has to take
+    the K18 route."""
     idx, err, stats = filtered()
     n_q = q.shape[0]
     stats.update(fallback_rows=0, fallback=False)
@@ -1055,7 +1119,7 @@ def _topk_filtered(metric: int, filtered, q, g, alpha, beta, k):
             stats.update(fallback_rows=n_q, fallback=True)
             return None, None, stats
         rows = (idx[:, 0] == -2).nonzero().flatten()
-        sub_i, sub_e = pairwise_topk(q[rows], g, metric, alpha, beta, torch.float64, k, to_host=False, filter=False)
+        sub_i, sub_e = pairwise_topk(q[rows], g, metric, alpha, beta, score_dtype, k, to_host=False, filter=False)
         idx[rows], err[rows] = sub_i, sub_e
         stats["fallback_rows"] = int(rows.numel())
     return idx, err, stats
@@ -1089,7 +1153,15 @@ def pairwise_topk(q, g, metric: int, alpha: float, beta: float, score_dtype, k: 
     ``l1_topk_auto`` says it pays (never while its ``L1_TOPK_FILTER_MIN_*`` are None).  g (and q) may then be an
     ``L1Set``: a resident gallery is packed once on its own grid and the queries are packed on ``g.grid`` inside the
     call; plain rows on both sides share a grid made from both; two ``L1Set`` on different grids are a ValueError.
-    Unresolved queries, the whole-call fallback, ``cand_cap`` / ``sample_rows`` and ``topk_stats``: as above."""
+    Unresolved queries, the whole-call fallback, ``cand_cap`` / ``sample_rows`` and ``topk_stats``: as above.
+
+    ``filter="jaccard"`` -- the K25 route for ``PW_JACCARD`` with float32 score words (``cmve_jaccard_topk``: the same
+    SAD filter under K24's interval of the two sums, canonical re-score of the candidates with the one rounding to
+    float32: the same words), ValueError unless the metric is ``PW_JACCARD`` with float32 score words, alpha finite
+    and non-zero and beta finite; None also takes it when it applies and ``jaccard_topk_auto`` says it pays (never
+    while its ``JACCARD_TOPK_FILTER_MIN_*`` are None; the L1 and L2 constants are not consulted).  g (and q) may then
+    be a ``JaccardSet``, as an ``L1Set`` above; a ``RowSet`` or a bare ``L1Set`` is a TypeError.  Unresolved queries
+    are re-run with float32 words; the rest as above."""
     route = _filter_route("pairwise_topk", filter, metric, alpha, beta, score_dtype, False)
     g_set = g if isinstance(g, RowSet) else None
     q_set = q if isinstance(q, RowSet) else None
@@ -1116,6 +1188,9 @@ def pairwise_topk(q, g, metric: int, alpha: float, beta: float, score_dtype, k: 
         elif _SAD_FILTERS["l1"].applies(metric, score_dtype):
             if l1_topk_auto(n_q, n_g, g_l1 is not None) and q.shape[1] <= L1_D_MAX:
                 route = "l1"
+        elif _SAD_FILTERS["jaccard"].applies(metric, score_dtype):
+            if jaccard_topk_auto(n_q, n_g, isinstance(g_l1, JaccardSet)) and q.shape[1] <= L1_D_MAX:
+                route = "jaccard"
     topk_stats = None
     if route and n_q > 0 and k <= L2_TOPK_CAND_MAX:
         if route == "l1":
@@ -1123,7 +1198,13 @@ def pairwise_topk(q, g, metric: int, alpha: float, beta: float, score_dtype, k: 
                 raise TypeError('pairwise_topk: a RowSet is packed for the Euclidean filter; filter="l1" takes an L1Set')
             q_l1, g_l1 = _l1_sets(q, g, q_l1, g_l1)
             filtered = lambda: l1_topk(q_l1, g_l1, alpha, beta, k, cand_cap, sample_rows, ws)  # noqa: E731
-        else:
+        elif route == "jaccard":
+            if q_set is not None or g_set is not None:
+                raise TypeError('pairwise_topk: a RowSet is packed for the Euclidean filter; filter="jaccard" takes a '
+                                "JaccardSet")
+            q_l1, g_l1 = _l1_sets(q, g, q_l1, g_l1, cls=JaccardSet)
+            filtered = lambda: jaccard_topk(q_l1, g_l1, alpha, beta, k, cand_cap, sample_rows, ws)  # noqa: E731
+        elif route == "l2":
             if q_l1 is not None or g_l1 is not None:
                 raise TypeError('pairwise_topk: an L1Set is packed for filter="l1"; the Euclidean filter takes a RowSet')
             if g_set is None:
@@ -1131,7 +1212,9 @@ def pairwise_topk(q, g, metric: int, alpha: float, beta: float, score_dtype, k: 
             if q_set is None:
                 q_set = RowSet(q, with_lo=False, device=g.device)
             filtered = lambda: l2_topk(q_set, g_set, alpha, beta, k, cand_cap, sample_rows, ws)  # noqa: E731
-        idx, err, topk_stats = _topk_filtered(metric, filtered, q, g, alpha, beta, k)
+        else:
+            raise AssertionError(f"pairwise_topk: no top-k behind the route {route!r}")
+        idx, err, topk_stats = _topk_filtered(metric, filtered, q, g, alpha, beta, k, score_dtype)
         if idx is not None:
             return result(idx, err, topk_stats)
     lo, rec = pairwise_topk_workspace(n_q, n_g, k, metric)

@@ -31,6 +31,7 @@ overrides the checkpoint's opt.measure (with both bypasses no checkpoint is read
 from __future__ import annotations
 
 import argparse
+import collections
 import os
 import sys
 
@@ -38,6 +39,11 @@ import numpy as np
 
 from .. import engine
 from .._lib import SIM_F16
+
+
+# the SAD-filtered top-k that serves a measure (K23, K25): the ``filter`` word, the packed gallery's class, the auto
+# rule and the workspace size
+_SadRoute = collections.namedtuple("_SadRoute", "word set_cls auto workspace")
 
 
 class GalleryScorer:
@@ -63,7 +69,13 @@ class GalleryScorer:
     measures alone and is ignored here (no pack).  The gallery is then packed once as an ``engine.L1Set`` on its own
     grid -- uint16 codes, 2 bytes per element beside the fp64 rows, plus 8 bytes per row; the rows are not copied --
     and each call packs its queries on that grid.  One workspace stays resident, sized for the route taken, and a
-    call handed back whole turns the automatic filter off, as above.  'jaccard' has no such form and stays on K18."""
+    call handed back whole turns the automatic filter off, as above.
+
+    Under 'jaccard' the SAD-filtered top-k of K25 serves in the same way (``engine.pairwise_topk(filter="jaccard")``:
+    float32 words, the same ids): ``filter="jaccard"`` forces it, None takes it when
+    ``engine.jaccard_topk_auto(n_q, n_g, packed=True)`` says it pays, False skips the pack, True is ignored.  The
+    gallery is packed once as an ``engine.JaccardSet`` over the gallery rows themselves (the codes and 24 bytes per
+    row; no second copy).  ``filter="jaccard"`` under any other measure is a ValueError."""
 
     def __init__(self, video_embs, video_ids=None, with_lo=True, measure='cosine', filter=None):
         self.measure = measure
@@ -72,6 +84,8 @@ class GalleryScorer:
         self._ws = None
         self._packed = None
         self._filter_off = False  # latched by a call the filter handed back whole
+        if isinstance(filter, str) and filter == "jaccard" and measure != 'jaccard':
+            raise ValueError(f'GalleryScorer: filter="jaccard" speaks for the jaccard measure, not {measure!r}')
         if measure != 'cosine':
             from .evaluation import measure_rows
             self.gallery = measure_rows(video_embs, measure)
@@ -80,11 +94,13 @@ class GalleryScorer:
                 self.gallery = self._packed.raw  # the pack keeps the rows it was given: no second copy
             # l1 / l1_norm (K23): packed when forced, or when the auto rule could take some call over this gallery
             # (never while its constants are None); filter=True speaks for the Euclidean measures alone
+            # jaccard (K25): the same, as a JaccardSet under filter="jaccard" and its own rule
             n_g = self.gallery.shape[0]
-            if measure in ('l1', 'l1_norm') and n_g and 1 <= self.gallery.shape[1] <= engine.L1_D_MAX and (
-                    (isinstance(filter, str) and filter == "l1")
-                    or (filter is None and engine.l1_topk_auto(1 << 30, n_g, packed=True))):
-                self._packed = engine.L1Set(self.gallery)
+            sad = self._sad_route()
+            if sad is not None and n_g and 1 <= self.gallery.shape[1] <= engine.L1_D_MAX and (
+                    (isinstance(filter, str) and filter == sad.word)
+                    or (filter is None and sad.auto(1 << 30, n_g, packed=True))):
+                self._packed = sad.set_cls(self.gallery)
                 self.gallery = self._packed.raw
             return
         emb = video_embs if hasattr(video_embs, "data_ptr") else np.asarray(video_embs)
@@ -92,6 +108,15 @@ class GalleryScorer:
         self._ws = None
         self._q = {}    # resident query sets by (rows, dim, dtype): re-packed in place per call
         self._out = {}  # resident top-k outputs by (rows, k)
+
+    def _sad_route(self):
+        """The SAD-filtered top-k that serves this measure, or None.  (Looked up per call: the tests patch the engine's
+        names.)"""
+        if self.measure in ('l1', 'l1_norm'):
+            return _SadRoute("l1", engine.L1Set, engine.l1_topk_auto, engine.l1_topk_workspace)
+        if self.measure == 'jaccard':
+            return _SadRoute("jaccard", engine.JaccardSet, engine.jaccard_topk_auto, engine.jaccard_topk_workspace)
+        return None
 
     def topk_indices(self, cap_embs, topK=10):
         """[N_q, topK] gallery indices, best first (== np.argsort(cal_error(...)[i])[:topK])."""
@@ -132,16 +157,16 @@ class GalleryScorer:
         # the route this call will take, as engine.pairwise_topk decides it; a gallery whose calls fell back to the
         # fp64 route as a whole (rows clustered far from the origin) is not asked again under filter=None
         flt = False
-        l1 = isinstance(self._packed, engine.L1Set)
+        sad = self._sad_route() if isinstance(self._packed, engine.L1Set) else None
         if self._packed is not None and q.shape[0] and 1 <= k <= engine.L2_TOPK_CAND_MAX:
-            forced = (isinstance(self.filter, str) and self.filter == "l1") if l1 else self.filter is True
-            auto = engine.l1_topk_auto if l1 else engine.l2_topk_auto
+            forced = (isinstance(self.filter, str) and self.filter == sad.word) if sad else self.filter is True
+            auto = sad.auto if sad else engine.l2_topk_auto
             flt = forced or (self.filter is None and not self._filter_off
                              and auto(q.shape[0], g.shape[0], packed=True))
         # ONE workspace stays resident between calls, sized for that route only and grown when a call needs more
         need = 0
-        if flt and l1:
-            need = engine.l1_topk_workspace(q.shape[0], g.shape[0], k)  # (the queries are packed on the gallery's grid)
+        if flt and sad:
+            need = sad.workspace(q.shape[0], g.shape[0], k)  # (the queries are packed on the gallery's grid)
         elif flt:
             q = engine.RowSet(q, eps=0.0, with_lo=False, device=g.device)
             need = engine.l2_topk_workspace(q, self._packed, k)
@@ -150,7 +175,7 @@ class GalleryScorer:
         if need and (self._ws is None or self._ws.numel() < need):
             self._ws = torch.empty(need, dtype=torch.uint8, device=g.device)
         idx, _, st = engine.pairwise_topk(q, self._packed if flt else g, metric, alpha, beta, sc_dt, k, ws=self._ws,
-                                          filter=("l1" if l1 else True) if flt else False, return_stats=True)
+                                          filter=(sad.word if sad else True) if flt else False, return_stats=True)
         if st is not None and st["fallback"]:
             self._filter_off = True
         return idx

@@ -1,15 +1,18 @@
-// What the two filtered top-k entries share (K20: l2_topk.hip, the MFMA filter of CMVE_PW_L2; K23: l1_topk.hip, the SAD
-// filter of CMVE_PW_L1), whatever brackets a pair's key:
-//   l2t_f32_up, l2t_row_state, l2t_pair, l2t_flush   the tail of a pass kernel's epilogue once it holds a pair's
-//                          interval: the stored upper bounds' rounding, the row's threshold and overflow flag, "launch
-//                          A stores the bound, launch B excludes or appends", the two counters
-//   l2t_threshold_kernel   launch A': radix select of the k-th smallest bound, widened to a threshold that is strict
-//                          on the canonical words
+// What the filtered top-k entries share (K20: l2_topk.hip, the MFMA filter of CMVE_PW_L2; K23: l1_topk.hip, the SAD
+// filter of CMVE_PW_L1; K25: jaccard_topk.hip, the SAD filter of CMVE_PW_JACCARD with float32 words), whatever brackets
+// a pair's key:
+//   l2t_f32_up, l2t_row_state, l2t_pair, l2t_decide, l2t_flush   the tail of a pass kernel's epilogue once it holds a
+//                          pair's interval: the stored upper bounds' rounding, the row's threshold and overflow flag,
+//                          "launch A stores the bound, launch B excludes or appends", the two counters (K25 brackets
+//                          two sums, not a distance: its pair step is its own and ends in l2t_decide)
+//   l2t_kth_bound, l2t_threshold_kernel   launch A': radix select of the k-th smallest bound, widened to a threshold
+//                          that is strict on the canonical words (K25 maps the bound through float32 words: a
+//                          threshold kernel of its own around the same select)
 //   l2t_finish_kernel      launch C: re-score, sort, emit
 //   l2t_sample, l2t_layout, l2t_check_params   the sample, the workspace and the checks of k / cand_cap / sample_rows
 //   l2t_topk_run           the host body: checks, memset, the rounds of four launches
 // A filter supplies its operands' checks, its pass kernel (tile, interval, thread layout) and the launch of it.  The
-// derivations are DESIGN s4, "K20" and "K23".
+// derivations are DESIGN s4, "K20", "K23" and "K25".
 #ifndef CMVE_TOPK_FILTER_TILE_H
 #define CMVE_TOPK_FILTER_TILE_H
 #include "l2_filter_tile.h"
@@ -50,6 +53,23 @@ __device__ __forceinline__ void l2t_row_state(const Args& a, Epi& E, int tid, in
   }
 }
 
+// launch B's verdict on the pair (query i, column j) of a query that has a threshold: `out` -- its key is provably
+// beyond it -- counts it excluded; anything else is a candidate, appended unless the row's list was already full
+template <typename Args>
+__device__ __forceinline__ void l2t_decide(const Args& a, bool out, int64_t i, int64_t j, bool full, int& n_cand,
+                                           int& n_excl) {
+  if (out) {
+    ++n_excl;
+  } else {
+    ++n_cand;
+    if (!full) {
+      const int64_t li = i - a.q0;
+      const int32_t p = gadd(a.cnt + li, (int32_t)1);
+      if (p < a.cap) a.list[li * a.cap + p] = (int32_t)j;
+    }
+  }
+}
+
 // one pair (query i, column j) whose distance lies in [dlo, dhi] (NaN, NaN: no interval); pos: alpha > 0
 template <int MODE, typename Args>
 __device__ __forceinline__ void l2t_pair(const Args& a, bool pos, int64_t i, int64_t j, double dlo, double dhi,
@@ -59,17 +79,7 @@ __device__ __forceinline__ void l2t_pair(const Args& a, bool pos, int64_t i, int
     a.ub[(i - a.q0) * a.ub_ld + j] = l2t_f32_up(pos ? dhi : -dlo);
   } else if (thr == thr) {
     // excluded only on a positive test: D is provably beyond the threshold (a NaN interval fails it)
-    const bool out = pos ? dlo > thr : dhi < thr;
-    if (out) {
-      ++n_excl;
-    } else {
-      ++n_cand;
-      if (!full) {
-        const int64_t li = i - a.q0;
-        const int32_t p = gadd(a.cnt + li, (int32_t)1);
-        if (p < a.cap) a.list[li * a.cap + p] = (int32_t)j;
-      }
-    }
+    l2t_decide(a, pos ? dlo > thr : dhi < thr, i, j, full, n_cand, n_excl);
   }
 }
 
@@ -122,19 +132,15 @@ __device__ __forceinline__ uint32_t l2t_key32(float f) {
   return (b >> 31) ? ~b : (b | 0x80000000u);
 }
 
-// launch A': one block per query.  The k-th smallest of its ns stored bounds by a 4 x 8-bit radix select, then the
-// threshold; the query's candidate counter starts at zero here.
-template <bool SQUARED>
-__global__ __launch_bounds__(256) void l2t_threshold_kernel(const float* __restrict__ ub, int64_t ub_ld, int64_t ns,
-                                                            int k, double alpha, double beta, double rho,
-                                                            double* __restrict__ thr, int32_t* __restrict__ cnt) {
+// The k-th smallest of the ns bounds at p by a 4 x 8-bit radix select, on the block's 256 threads (ns >= k: it
+// exists); every thread returns it.
+__device__ __forceinline__ float l2t_kth_bound(const float* __restrict__ p, int64_t ns, int k) {
   __shared__ int hist[256];
   __shared__ uint32_t s_prefix;
   __shared__ int s_k;
   const int tid = threadIdx.x;
-  const float* p = ub + (int64_t)blockIdx.x * ub_ld;
   uint32_t prefix = 0, mask = 0;
-  int kk = k;  // the rank looked for among the values that match the prefix (ns >= k: it exists)
+  int kk = k;  // the rank looked for among the values that match the prefix
   for (int shift = 24; shift >= 0; shift -= 8) {
     hist[tid] = 0;
     __syncthreads();
@@ -154,9 +160,18 @@ __global__ __launch_bounds__(256) void l2t_threshold_kernel(const float* __restr
     kk = s_k;
     mask |= 255u << shift;
   }
-  if (tid == 0) {
-    const uint32_t b = (prefix >> 31) ? (prefix & 0x7fffffffu) : ~prefix;
-    thr[blockIdx.x] = l2t_widen<SQUARED>((double)__uint_as_float(b), alpha, beta, rho);
+  return __uint_as_float((prefix >> 31) ? (prefix & 0x7fffffffu) : ~prefix);
+}
+
+// launch A': one block per query.  The k-th smallest of its ns stored bounds, then the threshold; the query's
+// candidate counter starts at zero here.
+template <bool SQUARED>
+__global__ __launch_bounds__(256) void l2t_threshold_kernel(const float* __restrict__ ub, int64_t ub_ld, int64_t ns,
+                                                            int k, double alpha, double beta, double rho,
+                                                            double* __restrict__ thr, int32_t* __restrict__ cnt) {
+  const float tau = l2t_kth_bound(ub + (int64_t)blockIdx.x * ub_ld, ns, k);
+  if (threadIdx.x == 0) {
+    thr[blockIdx.x] = l2t_widen<SQUARED>((double)tau, alpha, beta, rho);
     cnt[blockIdx.x] = 0;
   }
 }
@@ -199,9 +214,12 @@ __global__ __launch_bounds__(256) void l2t_finish_kernel(const TA* __restrict__ 
     const int p = b0 + tid;
     const bool live = p < n;
     const int j = mine[live ? p : b0];  // an idle lane repeats a candidate: its loads stay in bounds
-    const double s = l2f_chain64<METRIC>(Q, ldq, G, ldg, d, (int)gi, j, sd[w], lane);
+    // (jaccard, K25: both sums, and the one rounding to the float32 word)
+    constexpr bool JAC = METRIC == CMVE_PW_JACCARD;
+    double s1 = 0.0;
+    const double s = l2f_chain64<METRIC>(Q, ldq, G, ldg, d, (int)gi, j, sd[w], lane, JAC ? &s1 : nullptr);
     if (live) {
-      sw[p] = pw_score<METRIC>(s, 0.0, alpha, beta);
+      sw[p] = pw_round(pw_score<METRIC>(s, s1, alpha, beta), JAC);
       sid[p] = j;
     }
   }
@@ -296,15 +314,16 @@ struct L2tRound {
 };
 
 // One filtered top-k on h's stream.  `name`: the entry (refusals), `label`: check_launch's; METRIC: CMVE_PW_L2 (the
-// keys are squared distances) or CMVE_PW_L1; r: the raw rows (q is A, the gallery B); rho: the canonical chain's
-// relative slack in distance space; own_checks(): the entry's checks of its own operands, run where they always ran
-// (after the scaling and the parameters, before k against the gallery); pass_launch(mode, st, round, ws): the
-// filter's pass kernel, MODE = mode, over round.tiles_a x round.tiles_b blocks of 256 threads.
-template <int METRIC, typename Own, typename Pass>
+// keys are squared distances), CMVE_PW_L1 or CMVE_PW_JACCARD (float32 words); r: the raw rows (q is A, the gallery
+// B); own_checks(): the entry's checks of its own operands, run where they always ran (after the scaling and the
+// parameters, before k against the gallery); pass_launch(mode, st, round, ws): the filter's pass kernel, MODE = mode,
+// over round.tiles_a x round.tiles_b blocks of 256 threads; thr_launch(st, nq, ns, ws): launch A' -- nq blocks of 256
+// threads that leave the round's ws.thr from the ns stored bounds per query and zero ws.cnt.
+template <int METRIC, typename Own, typename Pass, typename Thr>
 static inline int l2t_topk_run(const char* name, const char* label, cmve_handle_t h, const FltRows& r, double alpha,
                                double beta, int32_t k, int64_t cand_cap, int64_t sample_rows, void* ws,
-                               int64_t ws_bytes, int64_t* out_idx, double* out_err, int64_t* stats, double rho,
-                               Own own_checks, Pass pass_launch) {
+                               int64_t ws_bytes, int64_t* out_idx, double* out_err, int64_t* stats,
+                               Own own_checks, Pass pass_launch, Thr thr_launch) {
   CMVE_REQUIRE(alpha != 0.0 && std::isfinite(alpha) && std::isfinite(beta),
                "%s: alpha must be finite and non-zero, beta finite (%g, %g)", name, alpha, beta);
   if (int rc = l2t_check_params(name, k, cand_cap, sample_rows)) return rc;
@@ -327,8 +346,7 @@ static inline int l2t_topk_run(const char* name, const char* label, cmve_handle_
     const int64_t nq = std::min(l.qc, n_q - q0);
     const int tiles_a = (int)((nq + L2F_BM - 1) / L2F_BM);  // <= 8: tiles_a * tiles_g < 2^31
     pass_launch(0, st, L2tRound{q0, q0 + nq, l.s, tiles_a, tiles_s}, w);
-    hipLaunchKernelGGL(l2t_threshold_kernel<METRIC == CMVE_PW_L2>, dim3((unsigned)nq), dim3(256), 0, st,
-                       (const float*)w.ub, w.ub_ld, l.s, (int)k, alpha, beta, rho, w.thr, w.cnt);
+    thr_launch(st, nq, l.s, w);
     pass_launch(1, st, L2tRound{q0, q0 + nq, n_g, tiles_a, tiles_g}, w);
     PWR_TYPES(r.a_dtype, r.b_dtype, TA, TB, {
       hipLaunchKernelGGL((l2t_finish_kernel<METRIC, TA, TB>), dim3((unsigned)nq), dim3(256), 0, st, (const TA*)r.A,
@@ -338,6 +356,20 @@ static inline int l2t_topk_run(const char* name, const char* label, cmve_handle_
     if (int rc = check_launch(label)) return rc;
   }
   return CMVE_OK;
+}
+
+// ... with l2t_threshold_kernel as launch A' (K20, K23); rho: the canonical chain's relative slack in distance space
+template <int METRIC, typename Own, typename Pass>
+static inline int l2t_topk_run(const char* name, const char* label, cmve_handle_t h, const FltRows& r, double alpha,
+                               double beta, int32_t k, int64_t cand_cap, int64_t sample_rows, void* ws,
+                               int64_t ws_bytes, int64_t* out_idx, double* out_err, int64_t* stats, double rho,
+                               Own own_checks, Pass pass_launch) {
+  auto thr_launch = [&](hipStream_t st, int64_t nq, int64_t ns, const L2tWs& w) {
+    hipLaunchKernelGGL(l2t_threshold_kernel<METRIC == CMVE_PW_L2>, dim3((unsigned)nq), dim3(256), 0, st,
+                       (const float*)w.ub, w.ub_ld, ns, (int)k, alpha, beta, rho, w.thr, w.cnt);
+  };
+  return l2t_topk_run<METRIC>(name, label, h, r, alpha, beta, k, cand_cap, sample_rows, ws, ws_bytes, out_idx, out_err,
+                              stats, own_checks, pass_launch, thr_launch);
 }
 
 }  // namespace cmve

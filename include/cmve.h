@@ -931,6 +931,42 @@ int cmve_l1_topk(cmve_handle_t h, const void* Q, int32_t q_dtype, int64_t ldq, i
                  int64_t cand_cap, int64_t sample_rows, void* ws, int64_t ws_bytes, int64_t* out_idx, double* out_err,
                  int64_t* stats);
 
+/* K25: cmve_pairwise_topk for CMVE_PW_JACCARD with float32 score words at the integer SAD rate
+ * (csrc/jaccard_topk.hip).  Replaces, as its K18 twin does: LINAS-engine/inference.py:78-80 (cal_error(video_embs,
+ * cap_emb, measure) then np.argsort(errors[0])[:topK]) under jaccard (LINAS-engine/evaluation.py:32-35).  Additive
+ * entries: the ABI version does not change.
+ *   cmve_l1_topk's operands plus, per side, qsum (int64) and asum (fp64) of cmve_jaccard_rowsums: a side exactly as
+ *   cmve_jaccard_count takes it, both sets on ONE grid.  out_idx int64 [n_q, k] / out_err fp64 [n_q, k] hold, word for
+ *   word, what cmve_pairwise_topk(metric = CMVE_PW_JACCARD, score_dtype = CMVE_F32) writes for the raw rows, alpha,
+ *   beta and k: float32 words carried in doubles, (error asc, index asc) on the canonical float32 word, NaN last in
+ *   index order, -0.0 == +0.0, ids of G's rows.  1 <= k <= n_g (the caller clamps k to the gallery).
+ *   cmve_l1_topk's four launches per round of 1,024 queries, in the space of the quotient
+ *   q = sum min / sum max: K22's SAD tile over the first sample_rows gallery rows stores every pair's upper bound on
+ *   sign(alpha) * q (the far end of K24's interval of the two sums: the one division per pair, on the sample only);
+ *   the k-th smallest per query becomes one quotient-space threshold beyond which a row's FLOAT32 word is strictly
+ *   worse than k rows' (checked on the device against K24's map of a float32 word to quotient space); the SAD tile
+ *   over the whole gallery excludes a row only when its whole interval lies beyond it (one fp64 product, no division)
+ *   and appends every other row (or one without an interval: a NaN, infinite or huge row, a sum of maxima that may
+ *   not be positive) to the query's candidate list; a block per query re-scores its candidates on the canonical
+ *   two-accumulator chain with its one rounding to float32, sorts them and emits k.
+ *   cand_cap, sample_rows, ws (cmve_jaccard_topk_workspace bytes: host only, no launch; the same layout formula as
+ *   cmve_l1_topk_workspace), the trailing candidate counters, the UNRESOLVED mark out_idx[i, 0] = -2 (a list that
+ *   overflows -- a query whose words all tie keeps every row --, fewer than k bounded rows in the sample, or no
+ *   usable threshold) and stats = {pairs excluded, candidates found, candidates re-scored, unresolved queries}: as
+ *   cmve_l2_topk's.
+ *   Enqueued on the handle's stream; allocates nothing, never synchronises; integer atomics only.  Refused, before
+ *   any launch: NULL arguments, alpha 0 or non-finite, beta non-finite, d outside [1, 65,536], n >= 2^31, k < 1,
+ *   k > n_g, cand_cap outside [k, 2048], a bad sample_rows, a short or misaligned workspace, NULL outputs with
+ *   n_q > 0, missing codes / row errors / row sums / grid (cmve_jaccard_rowsums). */
+int cmve_jaccard_topk_workspace(int64_t n_q, int64_t n_g, int32_t k, int64_t cand_cap, int64_t sample_rows,
+                                int64_t* bytes);
+int cmve_jaccard_topk(cmve_handle_t h, const void* Q, int32_t q_dtype, int64_t ldq, int64_t n_q, const void* q_codes,
+                      const double* q_err, const int64_t* q_qsum, const double* q_asum, const void* G,
+                      int32_t g_dtype, int64_t ldg, int64_t n_g, const void* g_codes, const double* g_err,
+                      const int64_t* g_qsum, const double* g_asum, int64_t d, const double* grid, double alpha,
+                      double beta, int32_t k, int64_t cand_cap, int64_t sample_rows, void* ws, int64_t ws_bytes,
+                      int64_t* out_idx, double* out_err, int64_t* stats);
+
 /* ---- training step of the projection heads ---------------
  * K11: what LINAS-engine/model.py:984-1004 (train_emb, style 'GT') runs around the GEMMs (K3 forward,
  * cmve_gemm_f32 backward) and the losses (K6/K7).  Device pointers, fp32 rows; statistics in fp64.
