@@ -438,6 +438,19 @@ L1_FILTER_MIN_PAIRS = 8192 * 8192
 JACCARD_FILTER_MIN_PAIRS = 8192 * 8192
 
 
+# ---- the cosine filter (K26): every listed item's position, both directions, from one MFMA pass ----
+# Auto dispatch of the K26 route (``filter=None`` of cmve.linas: taken only where today's route would run a second or
+# third rank pass, i.e. some list holds more than one item): the smallest n_c * n_v at which it beats today's passes
+# by more than the two routes' combined spread; None: never taken automatically, ``filter="cosine"`` alone runs it.
+# tools/cos_positions_bench.py measures cal_perf_embeddings on both routes at D = 1024 with 20 captions per video, host
+# embeddings in, tuples out, 10 alternating repeats (profiles/cos_positions.json; today's passes / one pass, medians):
+# 49.0 ms against 11.2 ms at 20,000 x 1,000 -- 4.4x on the medians, but single repeats of either route stray by
+# 30-36 ms on the host (combined spread 69.8 ms), so it does not count as a win by the rule; 153.1 ms against 72.1 ms at
+# 59,800 x 2,990 with 61.2 ms of combined spread; 1.113 s against 0.397 s at 327,680 x 16,384 with 0.296 s.  The count
+# itself (MFMA pass and band re-score) takes 0.48 / 2.13 / 54.7 ms there, the item words 0.08 / 0.26 / 1.39 ms.
+COS_FILTER_MIN_PAIRS = 59800 * 2990
+
+
 def _filter_route(name: str, filter, metric: int, alpha: float, beta: float, score_dtype, l2_scaling: bool,
                   size=None) -> Optional[str]:
     """THE route of a count: None (the canonical chain), ``"l2"`` (the MFMA filter), ``"l1"`` (the SAD filter) or
@@ -1876,3 +1889,150 @@ def gt_positions_fused(a: RowSet, b: RowSet, lists, mode: int = _lib.SIM_F16):
         p += len(l)
     return out
 
+
+
+# ---- K26: exact positions of every listed item under cosine from ONE MFMA pass (csrc/cos_filter.hip) ----
+def _cos_sets(a, b, name: str):
+    if not (isinstance(a, RowSet) and isinstance(b, RowSet)):
+        raise TypeError(f"{name}: both sides are RowSets (eps = 0, with their fp16 plane)")
+    if a.d != b.d:
+        raise ValueError(f"{name}: dimensions {a.d} and {b.d} do not match")
+    if a.device != b.device:
+        raise ValueError(f"{name}: the two sets live on different devices")
+
+
+def cos_item_scores(a: RowSet, b: RowSet, off: torch.Tensor, idx: torch.Tensor, n_items: int, col_dir: bool = False,
+                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fp64 [n_items] on the device: cos64 of every listed item of one CSR side (``cmve_cos_item_scores``) -- the word
+    ``gt_thresholds`` and the rank fix-up compute.  (off, idx): ``csr`` of the lists of a's rows naming b's rows
+    (col_dir: of b's rows naming a's rows).  An index outside the other set scores NaN.  No host copy, no
+    synchronisation."""
+    _cos_sets(a, b, "cos_item_scores")
+    n_items = int(n_items)
+    if idx.numel() < n_items or idx.dtype != torch.int32 or off.dtype != torch.int64:
+        raise ValueError(f"cos_item_scores: {n_items} items need int64 offsets and as many int32 indices")
+    if out is None:
+        out = torch.empty(max(n_items, 1), dtype=torch.float64, device=a.device)
+    elif out.dtype != torch.float64 or not out.is_contiguous() or out.numel() < n_items:
+        raise TypeError("cos_item_scores: out is a contiguous float64 tensor of at least n_items words")
+    check(lib.cmve_cos_item_scores(handle(a.device), C.byref(a.desc), C.byref(b.desc), _ptr(off), _ptr(idx),
+                                   off.numel() - 1, n_items, 1 if col_dir else 0, _ptr(out)), "cmve_cos_item_scores")
+    return out[:n_items]
+
+
+def cos_count_workspace(a: RowSet, b: RowSet, band_cap: int) -> int:
+    """Bytes of workspace ``cmve_cos_count`` needs for a band list of ``band_cap`` pairs (host only: no launch)."""
+    n = C.c_int64()
+    check(lib.cmve_cos_count_workspace(C.byref(a.desc), C.byref(b.desc), int(band_cap), C.byref(n)),
+          "cmve_cos_count_workspace")
+    return n.value
+
+
+def cos_count(a: RowSet, b: RowSet, row=None, col=None, band: Optional[torch.Tensor] = None,
+              stats: Optional[torch.Tensor] = None, row_pos: Optional[torch.Tensor] = None,
+              col_pos: Optional[torch.Tensor] = None):
+    """(row_pos, col_pos, stats): ``cmve_cos_count`` on device tensors, no host copy, no synchronisation.
+    row = (off [na + 1], item words fp64 [items], n): a non-NaN item's word is #{ j : cos64(i, j) > word }, a NaN item's
+    n - (NaN items of its list) + (its place among them); col: the mirror; a direction left None gives None.
+    ``band``: a caller-owned contiguous int64 device tensor, one slot per element (None: ``l2_band_cap(na * nb)``
+    slots).  ``stats``: int64 [4] on the device, {decided, band found, band re-scored, overflow}: when the overflow
+    word is 1 the positions are NOT valid and ``stats[1]`` is the capacity a redo needs (``cos_gt_eval`` does that)."""
+    _cos_sets(a, b, "cos_count")
+    dev = a.device
+    sides = []
+    for side, n_lists, pos in ((row, a.n, row_pos), (col, b.n, col_pos)):
+        if side is None:
+            sides.append((None, None, 0, 0, None))
+            continue
+        off, sc, n = side
+        if off.numel() != n_lists + 1:
+            raise ValueError(f"cos_count: {off.numel() - 1} lists for {n_lists} rows")
+        if sc.dtype != torch.float64 or not sc.is_contiguous():
+            raise TypeError("cos_count: item words are contiguous float64")
+        if pos is None:
+            pos = torch.empty(max(sc.numel(), 1), dtype=torch.int32, device=dev)
+        elif pos.dtype != torch.int32 or not pos.is_contiguous() or pos.numel() < sc.numel():
+            raise TypeError("cos_count: positions are contiguous int32, one per item")
+        sides.append((off, sc, sc.numel(), int(n), pos))
+    if band is None:
+        band = torch.empty(l2_band_cap(a.n * b.n), dtype=torch.int64, device=dev)
+    elif band.dtype != torch.int64 or not band.is_contiguous() or band.device != dev:
+        raise TypeError("cos_count: band is a contiguous int64 tensor on the sets' device")
+    if stats is None:
+        stats = torch.empty(4, dtype=torch.int64, device=dev)
+    check(lib.cmve_cos_count(handle(dev), C.byref(a.desc), C.byref(b.desc),
+                             *_count_tail(sides[0], sides[1], band, _nbytes(band), stats)), "cmve_cos_count")
+    (_, _, ritems, _, rpos), (_, _, citems, _, cpos) = sides
+    return (None if rpos is None else rpos[:ritems]), (None if cpos is None else cpos[:citems]), stats
+
+
+def cos_gt_eval_flat(caps: RowSet, vids: RowSet, row_lists=None, col_lists=None, band_cap: Optional[int] = None):
+    """``cos_gt_eval`` without the per-list arrays: per direction (offsets int64 [n + 1], 1-based positions int64
+    [items] in list order, ranks int64 [n]) on the host, or None for a direction without lists."""
+    _cos_sets(caps, vids, "cos_gt_eval")
+    na, nb, dev = caps.n, vids.n, caps.device
+    if row_lists is not None and len(row_lists) != na:
+        raise ValueError(f"cos_gt_eval: {len(row_lists)} row lists for {na} rows")
+    if col_lists is not None and len(col_lists) != nb:
+        raise ValueError(f"cos_gt_eval: {len(col_lists)} column lists for {nb} rows")
+    sides, total = [], 0
+    for lists in (row_lists, col_lists):
+        if lists is None:
+            sides.append(None)
+            continue
+        off, idx = csr(lists, dev)
+        items = sum(len(l) for l in lists)
+        sides.append((off, idx, items, total))
+        total += items
+    buf = torch.empty(total + 4, dtype=torch.float64, device=dev)  # the items' words, then the four counters
+    stats = buf[total:].view(torch.int64)
+    args = []
+    for side, col_dir, n_m in ((sides[0], False, nb), (sides[1], True, na)):
+        if side is None:
+            args.append(None)
+            continue
+        off, idx, items, start = side
+        sc = buf[start:start + items]
+        if items:
+            cos_item_scores(caps, vids, off, idx, items, col_dir, out=sc)
+        args.append((off, sc, n_m))
+    cap = max(1, int(band_cap) if band_cap is not None else l2_band_cap(na * nb))
+    for attempt in range(2):
+        band = torch.empty(cap, dtype=torch.int64, device=dev)
+        rpos, cpos, _ = cos_count(caps, vids, args[0], args[1], band, stats)
+        st = _l2_count_stats(stats.cpu().numpy())
+        cos_gt_eval.stats = dict(st, redone=attempt > 0)
+        if not st["overflow"]:
+            break
+        cap = st["band"]
+    else:
+        raise _lib.CmveError("cos_gt_eval: the band list overflowed at the capacity the count itself reported")
+    out = []
+    for side, arg, pos in ((sides[0], args[0], rpos), (sides[1], args[1], cpos)):
+        if side is None:
+            out.append(None)
+            continue
+        ranks = pairwise_list_ranks(side[0], arg[1], pos, arg[2]).cpu().numpy()
+        out.append((side[0].cpu().numpy(), pos.cpu().numpy().astype(np.int64) + 1, ranks))
+    return out[0], out[1]
+
+
+def cos_gt_eval(caps: RowSet, vids: RowSet, row_lists=None, col_lists=None, band_cap: Optional[int] = None):
+    """((t2v positions, t2v ranks), (v2t positions, v2t ranks)) under cosine from ONE pass over the caps x vids pairs
+    (K26), in ``pairwise_gt_eval``'s shapes: per direction the 1-based position of every listed item (a list of int64
+    arrays aligned with the lists) and the 1-based best-GT rank of every list (``cmve_pairwise_list_ranks``); a
+    direction without lists gives (None, None).  The words are ``gt_positions_fused``'s and ``gt_rank_counts``'s.
+    row_lists[i]: rows of vids listed for caption i; col_lists[j]: rows of caps listed for video j.  A band list that
+    overflows (``band_cap`` slots; None: ``l2_band_cap``) is redone once with the reported need.  The counters of the
+    last count are left in ``cos_gt_eval.stats`` ({decided, band, rescored, overflow, redone})."""
+    out = []
+    for side in cos_gt_eval_flat(caps, vids, row_lists, col_lists, band_cap):
+        if side is None:
+            out.append((None, None))
+            continue
+        offs, p, ranks = side
+        out.append(([p[offs[i]:offs[i + 1]] for i in range(offs.size - 1)], ranks))
+    return out[0], out[1]
+
+
+cos_gt_eval.stats = None

@@ -75,12 +75,60 @@ def measure_eval(caps, vids, measure, row_lists=None, col_lists=None, filter=Non
     return engine.pairwise_gt_eval(caps, vids, metric, alpha, beta, sc_dt, row_lists, col_lists, filter)
 
 
+def cosine_sets(errors, filter=None):
+    """(captions RowSet, videos RowSet) of errors = -cos that carry their packed sets, else None.  ``filter="cosine"``
+    asks for the one-pass route (K26), which speaks for those errors alone: anything else is a ValueError."""
+    meta = _fused_sets(errors)
+    if meta is not None and meta[2] < 0:
+        return meta[0], meta[1]
+    if filter == "cosine":
+        raise ValueError('filter="cosine" needs errors that carry their packed cosine sets (cal_error under cosine), '
+                         "or measure='cosine'")
+    return None
+
+
+def cosine_one_pass(filter, n_c, n_v, *lists) -> bool:
+    """Whether a cosine evaluation takes the one-pass route (K26, ``engine.cos_gt_eval``): ``filter="cosine"`` forces
+    it; None takes it where today's route would run a second or third rank pass -- some list holds more than one item
+    -- and n_c * n_v reaches ``engine.COS_FILTER_MIN_PAIRS`` (never while that is None)."""
+    if filter == "cosine":
+        return True
+    min_pairs = engine.COS_FILTER_MIN_PAIRS  # (read at call time)
+    return (filter is None and min_pairs is not None and n_c * n_v >= min_pairs
+            and any(len(l) > 1 for ls in lists for l in ls))
+
+
 def maps_from_positions(t2v_pos, v2t_pos):
     """(t2v_map, v2t_map) of metrics.py:61-102 from every GT item's position: the t2v AP scores the FIRST GT video
     of each caption alone (1 / its position), the v2t AP all GT captions of each video."""
     t2v = float(np.mean([ap_from_positions(p[:1]) for p in t2v_pos]))
     v2t = float(np.mean([ap_from_positions(p) for p in v2t_pos]))
     return t2v, v2t
+
+
+def ap_flat(offs, pos, first_only=False):
+    """``ap_from_positions`` of every list of a CSR side at once (offs int64 [n + 1], 1-based positions in list
+    order), the same floats: lists of one length are sorted and summed as the rows of one matrix.  ``first_only``:
+    each list's FIRST item alone (the t2v AP of metrics.py:61-79)."""
+    offs, pos = np.asarray(offs, np.int64), np.asarray(pos)
+    lens = np.diff(offs)
+    out = np.zeros(lens.size, np.float64)
+    if first_only:
+        has = lens > 0
+        out[has] = 1.0 / pos[offs[:-1][has]].astype(np.float64)
+        return out
+    for m in np.unique(lens):
+        if m == 0:
+            continue
+        which = np.flatnonzero(lens == m)
+        p = np.sort(pos[offs[which][:, None] + np.arange(m)[None, :]].astype(np.float64), axis=1)
+        out[which] = np.sum(np.arange(1, m + 1) / p, axis=1) / m
+    return out
+
+
+def maps_from_flat(t2v, v2t):
+    """``maps_from_positions`` from ``engine.cos_gt_eval_flat``'s sides."""
+    return float(np.mean(ap_flat(t2v[0], t2v[1], first_only=True))), float(np.mean(ap_flat(v2t[0], v2t[1])))
 
 
 def gt_ranks(scores, q2m_gts):
@@ -128,13 +176,17 @@ def ap_from_positions(positions):
     return float(np.sum(np.arange(1, p.size + 1) / p) / p.size)
 
 
-def t2v_map(c2i, t2v_gts):
-    """metrics.py:61-79: AP of the FIRST GT video of each caption (= 1 / its position)."""
+def t2v_map(c2i, t2v_gts, filter=None):
+    """metrics.py:61-79: AP of the FIRST GT video of each caption (= 1 / its position).  ``filter="cosine"``: the
+    positions from the one-pass count (K26) -- errors = -cos with their packed sets only."""
     n_q = c2i.shape[0]
     firsts = [[_lists(t2v_gts, n_q)[i][0]] for i in range(n_q)]
-    meta = _fused_sets(c2i)
-    if meta is not None and meta[2] < 0:
-        caps, vids, _ = meta
+    cos = cosine_sets(c2i, filter)
+    if cos is not None:
+        caps, vids = cos
+        if cosine_one_pass(filter, n_q, c2i.shape[1]):
+            offs, pos, _ = engine.cos_gt_eval_flat(caps, vids, row_lists=firsts)[0]
+            return float(np.mean(ap_flat(offs, pos)))
         r, _, _ = engine.gt_rank_counts(caps, vids, row_gts=firsts)
         return float(np.mean(1.0 / r))
     pw = _measure_sets(c2i)
@@ -145,13 +197,17 @@ def t2v_map(c2i, t2v_gts):
     return float(np.mean([ap_from_positions(p) for p in pos]))
 
 
-def v2t_map(c2i, v2t_gts):
-    """metrics.py:83-102: AP over all GT captions of each video (columns of c2i)."""
+def v2t_map(c2i, v2t_gts, filter=None):
+    """metrics.py:83-102: AP over all GT captions of each video (columns of c2i).  ``filter``: ``t2v_map``'s; None
+    also takes the one-pass count where today's route expands the captions (``cosine_one_pass``)."""
     n_v = c2i.shape[1]
     lists = _lists(v2t_gts, n_v)
-    meta = _fused_sets(c2i)
-    if meta is not None and meta[2] < 0:
-        caps, vids, _ = meta
+    cos = cosine_sets(c2i, filter)
+    if cos is not None:
+        caps, vids = cos
+        if cosine_one_pass(filter, c2i.shape[0], n_v, lists):
+            offs, pos, _ = engine.cos_gt_eval_flat(caps, vids, col_lists=lists)[1]
+            return float(np.mean(ap_flat(offs, pos)))
         if all(len(l) <= 1 for l in lists):
             _, c, _ = engine.gt_rank_counts(caps, vids, col_gts=lists)
             return float(np.mean([1.0 / c[j] if lists[j] else 0.0 for j in range(n_v)]))

@@ -33,13 +33,24 @@ def _log(tag, r1, r5, r10, medr, meanr, m):
     logging.info(" * " + '-' * 10)
 
 
-def cal_perf(t2v_all_errors, v2t_gt, t2v_gt, tb_logger=None, model=None):
+def _cosine_one_pass(caps, vids, t2v_lists, v2t_lists):
+    """Both directions' ranks and both mAPs under cosine from ONE ``engine.cos_gt_eval_flat`` call (K26)."""
+    t2v, v2t = engine.cos_gt_eval_flat(caps, vids, t2v_lists, v2t_lists)
+    return (t2v[2], v2t[2]) + metrics.maps_from_flat(t2v, v2t)
+
+
+def cal_perf(t2v_all_errors, v2t_gt, t2v_gt, tb_logger=None, model=None, filter=None):
+    """``filter="cosine"`` (errors = -cos with their packed sets only, else ValueError): every rank and mAP position
+    from one MFMA pass over the pairs (K26); None takes it where today's route would run a second or third pass and
+    ``engine.COS_FILTER_MIN_PAIRS`` is set and reached."""
     n_c, n_v = t2v_all_errors.shape
     t2v_lists = metrics._lists(t2v_gt, n_c)
     v2t_lists = metrics._lists(v2t_gt, n_v)
-    meta = getattr(t2v_all_errors, '_cmve', None) if isinstance(t2v_all_errors, ErrorMatrix) else None
-    if meta is not None and meta[2] < 0:
-        caps, vids, _ = meta
+    cos = metrics.cosine_sets(t2v_all_errors, filter)
+    if cos is not None and metrics.cosine_one_pass(filter, n_c, n_v, t2v_lists, v2t_lists):
+        t2v_ranks, v2t_ranks, t2v_map_score, v2t_map_score = _cosine_one_pass(*cos, t2v_lists, v2t_lists)
+    elif cos is not None:
+        caps, vids = cos
         t2v_ranks, v2t_ranks, _ = engine.gt_rank_counts(caps, vids, row_gts=t2v_lists, col_gts=v2t_lists)
         if all(len(l) == 1 for l in t2v_lists):
             t2v_map_score = float(np.mean(1.0 / t2v_ranks))
@@ -82,9 +93,12 @@ def cal_perf_embeddings(video_embs, cap_embs, video_ids, caption_ids, measure='c
     jaccard of evaluation.py:22-35) never forms the matrix at all, on the device or the host (K18); ``filter`` is
     ``metrics.measure_eval``'s (auto: the Euclidean measures count at the MFMA rate on large sets, K19;
     ``filter="l1"``: l1 / l1_norm through the integer SAD filter, K22; ``filter="jaccard"``: jaccard through the same
-    filter, K24)."""
+    filter, K24).  Under cosine ``filter="cosine"`` takes every rank and mAP position from ONE MFMA pass (K26,
+    ``cal_perf``'s rule for None); with any other measure it is a ValueError."""
     v2t_gt, t2v_gt = metrics.get_gt(video_ids, caption_ids)
     if measure != 'cosine':
+        if filter == "cosine":
+            raise ValueError(f'filter="cosine" needs measure=\'cosine\', got {measure!r}')
         from .evaluation import measure_rows
         caps, vids = measure_rows(cap_embs, measure), measure_rows(video_embs, measure)
         t2v_lists = metrics._lists(t2v_gt, caps.shape[0])
@@ -96,6 +110,9 @@ def cal_perf_embeddings(video_embs, cap_embs, video_ids, caption_ids, measure='c
     vids = engine.RowSet(np.asarray(video_embs), eps=0.0, with_lo=False)
     n_c, n_v = caps.n, vids.n
     t2v_lists = metrics._lists(t2v_gt, n_c)
+    if metrics.cosine_one_pass(filter, n_c, n_v, t2v_lists, v2t_gt):
+        t2v_ranks, v2t_ranks, t2v_map, v2t_map = _cosine_one_pass(caps, vids, t2v_lists, v2t_gt)
+        return (metrics.metrics_from_ranks(v2t_ranks) + (v2t_map,), metrics.metrics_from_ranks(t2v_ranks) + (t2v_map,))
     t2v_ranks, v2t_ranks, _ = engine.gt_rank_counts(caps, vids, row_gts=t2v_lists, col_gts=v2t_gt)
     t2v = metrics.metrics_from_ranks(t2v_ranks)
     v2t = metrics.metrics_from_ranks(v2t_ranks)

@@ -4,7 +4,8 @@
 //   FltLists / FltBand   the caller's lists and band list, as every entry, launch and kernel argument carries them
 //   flt_check_lists      what every count entry asks of the lists (cmve_pairwise_count included)
 //   flt_count_run        the host body: checks, memsets, NaN items, the filter's main launch, fix-up, resolve
-// A filter supplies its own operands' checks and a main launch.  The two SAD filters share one kernel body and one
+// A filter supplies its own operands' checks and a main launch (K26, the cosine filter of cos_filter.hip, also its
+// fix-up launch: its canonical word is cos64, not a chain of pairwise_tile.h).  The two SAD filters share one kernel body and one
 // epilogue (sad_count.h: the same tile, thread layout and occupancy under a small policy); l2f_main_kernel keeps an
 // epilogue of its own (the same algorithm on another thread layout, at 256 VGPRs): written once as a force-inlined
 // template it cost that kernel 6% (DESIGN s4).
@@ -80,11 +81,13 @@ void pwr_count_gated_launch(hipStream_t st, int32_t metric, const FltRows& r, do
 // One filtered count on h's stream.  `name`: the entry (refusals), `label`: check_launch's; own_checks(): the
 // entry's checks of its own operands, run where they always ran (after the scaling, before the lists);
 // main_launch(st, args): the filter's main kernel over args.tiles_a x args.tiles_b blocks.  `resolve`: an
-// overflowing list is resolved on the device.
-template <typename Own, typename Main>
+// overflowing list is resolved on the device.  fixup_launch(st, lists, band): the re-score of the band list on the
+// entry's canonical chain -- l2f_fixup_launch with `metric` for the measures of pairwise_tile.h (the overload below),
+// K26's own under cosine (cos_filter.hip, whose words are cos64's).
+template <typename Own, typename Main, typename Fix>
 static inline int flt_count_run(const char* name, const char* label, cmve_handle_t h, int32_t metric,
                                 const FltRows& r, double alpha, double beta, FltLists l, void* ws, int64_t ws_bytes,
-                                int64_t* stats, bool resolve, Own own_checks, Main main_launch) {
+                                int64_t* stats, bool resolve, Own own_checks, Main main_launch, Fix fixup_launch) {
   CMVE_REQUIRE(alpha != 0.0 && std::isfinite(alpha) && std::isfinite(beta),
                "%s: alpha must be finite and non-zero, beta finite (%g, %g)", name, alpha, beta);
   if (int rc = own_checks()) return rc;
@@ -105,9 +108,19 @@ static inline int flt_count_run(const char* name, const char* label, cmve_handle
   if (r.na == 0 || r.nb == 0) return check_launch(label);
   const FltBand band{(int2*)ws, ws_bytes / (int64_t)sizeof(int2), (l2f_u64*)stats};
   main_launch(st, FltArgs{r.na, r.nb, alpha, beta, l, band, (int)tiles_a, (int)tiles_b});
-  if (band.cap > 0) l2f_fixup_launch(st, metric, r, alpha, beta, l, band);
+  if (band.cap > 0) fixup_launch(st, l, band);
   if (resolve) l2f_resolve_launch(st, metric, r, alpha, beta, l, band.stats);
   return check_launch(label);
+}
+
+template <typename Own, typename Main>
+static inline int flt_count_run(const char* name, const char* label, cmve_handle_t h, int32_t metric,
+                                const FltRows& r, double alpha, double beta, FltLists l, void* ws, int64_t ws_bytes,
+                                int64_t* stats, bool resolve, Own own_checks, Main main_launch) {
+  return flt_count_run(name, label, h, metric, r, alpha, beta, l, ws, ws_bytes, stats, resolve, own_checks, main_launch,
+                       [&](hipStream_t st, const FltLists& fl, const FltBand& fb) {
+                         l2f_fixup_launch(st, metric, r, alpha, beta, fl, fb);
+                       });
 }
 
 }  // namespace cmve

@@ -859,6 +859,42 @@ int cmve_jaccard_count(cmve_handle_t h, const void* A, int32_t a_dtype, int64_t 
                        int32_t* row_pos, const int64_t* col_off, const double* col_sc, int64_t col_items,
                        int64_t col_n, int32_t* col_pos, void* ws, int64_t ws_bytes, int64_t* stats);
 
+/* K26: the exact position of EVERY listed item under cosine, both directions, from one pass at the MFMA rate
+ * (csrc/cos_filter.hip).  Replaces LINAS-engine/evaluation.py:17-21 (cal_error under cosine) +
+ * util/metrics.py:61-102,124-157 (t2v_map, v2t_map, eval_q2m's argsort loop), i.e. validate.py:15-54 (cal_perf).
+ * Additive entries: the ABI version does not change.
+ *   a, b: ordinary packed sets (cmve_pack_rows with eps = 0 and the fp16 plane, not CMVE_PACK_RAW, raw rows F32 / F64)
+ *   of the captions [na, d] and the videos [nb, d].  The canonical word of a pair is
+ *   cos64(i, j) = dot64(raw_a_i, raw_b_j) * (inv_norm_a_i * inv_norm_b_j), the word cmve_gt_thresholds and
+ *   cmve_rank_fixup compute (one device function), symmetric in its two rows.
+ *   cmve_cos_item_scores  (evaluation.py:17-21 + metrics.py:61-102,124-157 = validate.py:15-54) out[p] = cos64 of
+ *                      item p of one CSR side: list `owner` (off[owner] <= p < off[owner + 1]) names row idx[p] of
+ *                      the other set; col_dir = 0: the lists are a's rows' and name b's rows, n_lists = na;
+ *                      col_dir = 1: the mirror, n_lists = nb.  An index outside the other set scores NaN.
+ *   cmve_cos_count_workspace  (evaluation.py:17-21 + metrics.py:61-102,124-157 = validate.py:15-54) host only, no
+ *                      launch: 8 * band_cap bytes, the band list and nothing else.
+ *   cmve_cos_count     (evaluation.py:17-21 + metrics.py:61-102,124-157 = validate.py:15-54)
+ *                      row_pos[p] = #{ j < nb : cos64(i, j) > row_sc[p] } for every item p of every row i of a,
+ *                      col_pos[p] = #{ i < na : cos64(i, j) > col_sc[p] } for every item p of every row j of b; a NaN
+ *                      item gets n - (NaN items of its list) + (its place among them) with the caller's row_n / col_n
+ *                      (0: its word stays 0); either direction may be NULL.  An fp16 MFMA cosine decides every
+ *                      comparison whose sides lie further apart than its rigorous error; every
+ *                      other pair -- the band -- is appended once to the list in ws and re-scored with cos64.
+ *                      ws: 8-byte aligned, need not be zeroed, the capacity is ws_bytes / 8.  stats: device int64[4] =
+ *                      {pairs decided by the filter, band pairs found, band pairs re-scored, overflow flag};
+ *                      decided + band = na * nb.  When the band outgrows the list the re-score returns at once on
+ *                      the device, the flag is 1, the positions are NOT valid and stats[1] is the whole need: one redo
+ *                      with that capacity suffices.  Enqueued on the handle's stream; allocates nothing, never
+ *                      synchronises; integer atomics only: two calls give the same words.  Refused before any
+ *                      launch: a set without h16, eps != 0, CMVE_PACK_RAW, mismatched d, bad lists. */
+int cmve_cos_item_scores(cmve_handle_t h, const cmve_rows_t* a, const cmve_rows_t* b, const int64_t* off,
+                         const int32_t* idx, int64_t n_lists, int64_t n_items, int32_t col_dir, double* out);
+int cmve_cos_count_workspace(const cmve_rows_t* a, const cmve_rows_t* b, int64_t band_cap, int64_t* bytes);
+int cmve_cos_count(cmve_handle_t h, const cmve_rows_t* a, const cmve_rows_t* b, const int64_t* row_off,
+                   const double* row_sc, int64_t row_items, int64_t row_n, int32_t* row_pos, const int64_t* col_off,
+                   const double* col_sc, int64_t col_items, int64_t col_n, int32_t* col_pos, void* ws,
+                   int64_t ws_bytes, int64_t* stats);
+
 /* K20: cmve_pairwise_topk for CMVE_PW_L2 with fp64 score words at the MFMA rate (csrc/l2_topk.hip).
  * Replaces, as its K18 twin does: LINAS-engine/inference.py:78-80 (cal_error(video_embs, cap_emb, measure) then
  * np.argsort(errors[0])[:topK]) under euclidean / l2 / l2_norm (LINAS-engine/evaluation.py:22-35).
