@@ -45,6 +45,7 @@ subclass replaces.  The coordination above them is the same for every communicat
 """
 from __future__ import annotations
 
+import functools
 import threading
 from typing import Callable, List, Optional, Sequence
 
@@ -810,8 +811,8 @@ class MeasureShardedGallery(ShardedGallery):
         self.n = int(self.shard.shape[0])
         # the filter family that speaks for the measure: "l2" (K19 - K21, a RowSet), "l1" (K22 / K23, an L1Set),
         # "jaccard" (K24 / K25, a JaccardSet) or None; the last two are the SAD families: ``filter`` names them
-        self._pw_family = ("l2" if self.measure in _L2_MEASURES else "l1" if self.measure in _L1_MEASURES
-                           else "jaccard" if self.measure in _JACCARD_MEASURES else None)
+        metric, _, _, sc_dt = self._pw_spec()
+        self._pw_family = "l2" if self.measure in _L2_MEASURES else engine.sad_route_of(metric, sc_dt)
         self._pw_packed = None  # the shard's pack for its family's filters, made by the first call that needs it
         self._pw_filter_off = False  # latched by a top-k the filter handed back whole, or a count whose band
         #                              exceeds 1/8 of the pairs: this shard stays on fp64
@@ -837,14 +838,13 @@ class MeasureShardedGallery(ShardedGallery):
         """The shard's pack for the filters, made ONCE and shared by the top-k and the count; it keeps the rows it
         is given, so there is no second copy of the shard."""
         if self._pw_packed is None:
-            self._pw_packed = (engine.L1Set(self.shard) if self._pw_family == "l1"  # (on the shard's own grid)
-                               else engine.JaccardSet(self.shard) if self._pw_family == "jaccard"
+            self._pw_packed = (engine.sad_set(self._pw_family, self.shard) if self._pw_sad()  # (on the shard's own grid)
                                else engine.RowSet(self.shard, eps=0.0, with_lo=False, device=self.device))
         return self._pw_packed
 
     def _pw_sad(self) -> bool:
         """The measure's filters are the SAD ones (K22 - K25): ``filter`` names the family, the pack is on a grid."""
-        return self._pw_family in ("l1", "jaccard")
+        return self._pw_family not in (None, "l2")
 
     def _pw_forced(self) -> bool:
         """The constructor's filter names this family's filter (True: Euclidean, "l1": L1, "jaccard": jaccard)."""
@@ -854,8 +854,7 @@ class MeasureShardedGallery(ShardedGallery):
     def _pw_count_auto(self, pairs: int) -> bool:
         """filter=None: the family's count filter pays from its measured number of pairs (None there: never)."""
         if self._pw_sad():
-            lo = engine.L1_FILTER_MIN_PAIRS if self._pw_family == "l1" else engine.JACCARD_FILTER_MIN_PAIRS
-            lo = lo if self.shard.shape[1] <= engine.L1_D_MAX else None
+            lo = engine.sad_min_pairs(self._pw_family) if self.shard.shape[1] <= engine.L1_D_MAX else None
         else:
             lo = engine.L2_FILTER_MIN_PAIRS
         return lo is not None and pairs >= lo
@@ -917,8 +916,7 @@ class MeasureShardedGallery(ShardedGallery):
         if self._pw_filter_off or (sad and self._pw_filter is False):
             return engine.pairwise_topk(q, self.shard, *self._pw_spec(), k, to_host=False, filter=False)
         forced = sad and self._pw_forced()
-        auto = {"l1": engine.l1_topk_auto, "jaccard": engine.jaccard_topk_auto}.get(self._pw_family,
-                                                                                    engine.l2_topk_auto)
+        auto = functools.partial(engine.sad_topk_auto, self._pw_family) if sad else engine.l2_topk_auto
         fits = not sad or self.shard.shape[1] <= engine.L1_D_MAX  # (beyond it auto stays on K18; forced: ValueError)
         if (self._pw_packed is None and self._pw_family is not None
                 and (forced or (fits and auto(q.shape[0], self.n, packed=True)))):

@@ -562,7 +562,7 @@ class JaccardSet(L1Set):
 def _l1_sets(a, b, a_set: Optional["L1Set"], b_set: Optional["L1Set"], cls=None):
     """Both sides as ``L1Set`` (``cls``: as ``JaccardSet``) on ONE grid: a resident side's when there is one, else
     both sets' elements."""
-    if cls is None:
+    if cls is None or cls is L1Set:
         cls = L1Set
     else:
         for given in (a_set, b_set):
@@ -587,31 +587,47 @@ class _SadFilter(NamedTuple):
     set_cls: type  # a packed side
     min_pairs: str  # the module-level auto threshold, by name: read at call time (the tests patch it)
     entry: str  # the C count entry; its workspace entry is ``entry + "_workspace"``
-    extras: Tuple[str, ...]  # the per-set arrays the count entry takes after the codes and the errors
+    extras: Tuple[str, ...]  # the per-set arrays both entries take after the codes and the errors
+    # the top-k half (K23, K25).  Module-level names again, read at call time: the tests and the tools patch them
+    set_words: str  # a packed side as the refusals name it
+    topk: str  # the public call; ``topk + "_workspace"`` / ``"_auto"`` are its workspace size and its auto rule,
+    #            ``"cmve_" + topk`` the C entry
+    topk_min: Tuple[str, str, str, str]  # the auto rule's MIN_GALLERY, MIN_PAIRS (packed), MIN_Q, MIN_PLAIN_PAIRS
 
     words = property(lambda self: str(self.score_dtype).split(".")[-1])  # as the refusals name the score words
 
     def applies(self, metric: int, score_dtype) -> bool:
         return metric == getattr(_lib, self.metric) and score_dtype == self.score_dtype
 
+    def set_now(self) -> type:
+        """``set_cls`` under the name the module gives it when called (the tests patch ``L1Set``)."""
+        return globals()[self.set_cls.__name__]
 
-# the routes of ``_filter_route`` that are SAD filters (K22, K24), in the order the auto rule asks them
+
+def _topk_min(prefix: str) -> Tuple[str, str, str, str]:
+    return tuple(f"{prefix}_TOPK_FILTER_MIN_{x}" for x in ("GALLERY", "PAIRS", "Q", "PLAIN_PAIRS"))
+
+
+# the routes of ``_filter_route`` that are SAD filters (K22 / K23, K24 / K25), in the order the auto rules ask them
 _SAD_FILTERS = {
-    "l1": _SadFilter("PW_L1", torch.float64, L1Set, "L1_FILTER_MIN_PAIRS", "cmve_l1_count", ()),
+    "l1": _SadFilter("PW_L1", torch.float64, L1Set, "L1_FILTER_MIN_PAIRS", "cmve_l1_count", (),
+                     "an L1Set", "l1_topk", _topk_min("L1")),
     "jaccard": _SadFilter("PW_JACCARD", torch.float32, JaccardSet, "JACCARD_FILTER_MIN_PAIRS",
-                          "cmve_jaccard_count", ("qsum", "asum")),
+                          "cmve_jaccard_count", ("qsum", "asum"), "a JaccardSet", "jaccard_topk", _topk_min("JACCARD")),
 }
+
+
+def _sad_side(f: _SadFilter, s: "L1Set") -> tuple:
+    """One packed side as both of the filter's entries take it."""
+    return (_ptr(s.raw), _dtype_code(s.raw), _pw_ld(s.raw), s.n, _ptr(s.codes), _ptr(s.err),
+            *(_ptr(getattr(s, x)) for x in f.extras))
 
 
 def _sad_count_call(route: str, h, a_set: "L1Set", b_set: "L1Set", alpha, beta, row, col, ws, ws_bytes: int, stats):
     """The route's count entry (row / col / ws / stats as ``_count_tail``; jaccard's item words are float32 values)."""
     f = _SAD_FILTERS[route]
-
-    def side(s):
-        return (_ptr(s.raw), _dtype_code(s.raw), _pw_ld(s.raw), s.n, _ptr(s.codes), _ptr(s.err),
-                *(_ptr(getattr(s, x)) for x in f.extras))
-    check(getattr(lib, f.entry)(h, *side(a_set), *side(b_set), a_set.d, _ptr(a_set.grid), float(alpha), float(beta),
-                                *_count_tail(row, col, ws, ws_bytes, stats)), f.entry)
+    check(getattr(lib, f.entry)(h, *_sad_side(f, a_set), *_sad_side(f, b_set), a_set.d, _ptr(a_set.grid), float(alpha),
+                                float(beta), *_count_tail(row, col, ws, ws_bytes, stats)), f.entry)
 
 
 _l1_count_call = functools.partial(_sad_count_call, "l1")            # (the names the bench tools call)
@@ -991,6 +1007,78 @@ def l2_topk(q: "RowSet", g: "RowSet", alpha: float, beta: float, k: int, cand_ca
                                l2_topk_workspace(q, g, k, cap, sample_rows), ws, g.device)
 
 
+# ---- the SAD-filtered top-ks (K23, K25): ONE implementation over the ``_SAD_FILTERS`` record; the public names below it
+# are one-line wrappers, and generic code reaches a family's functions and constants by name when called ----
+def _n_rows(s) -> int:
+    return int(s.n) if hasattr(s, "n") else int(s)
+
+
+def _sad_topk_auto(route: str, n_q: int, n_g: int, packed: bool = False) -> bool:
+    """The route's auto rule from ITS four constants alone: a packed gallery takes the filter from MIN_GALLERY rows or
+    MIN_PAIRS pairs, plain rows from MIN_Q queries AND MIN_PLAIN_PAIRS pairs; None switches a clause off."""
+    if n_q < 1 or n_g < 1:
+        return False
+    min_gallery, min_pairs, min_q, min_plain = (globals()[name] for name in _SAD_FILTERS[route].topk_min)
+    if packed:
+        return ((min_gallery is not None and n_g >= min_gallery)
+                or (min_pairs is not None and n_q * n_g >= min_pairs))
+    return min_q is not None and min_plain is not None and n_q >= min_q and n_q * n_g >= min_plain
+
+
+def _sad_topk_workspace(route: str, q, g, k: int, cand_cap: Optional[int] = None,
+                        sample_rows: Optional[int] = None) -> int:
+    """Bytes of workspace the route's top-k entry needs (host only: no launch).  q / g: a packed set or a row count."""
+    entry = f"cmve_{_SAD_FILTERS[route].topk}_workspace"
+    n = C.c_int64()
+    check(getattr(lib, entry)(_n_rows(q), _n_rows(g), int(k), L2_TOPK_CAND_MAX if cand_cap is None else int(cand_cap),
+                              int(sample_rows or 0), C.byref(n)), entry)
+    return n.value
+
+
+def _sad_topk(route: str, q: "L1Set", g: "L1Set", alpha: float, beta: float, k: int, cand_cap: Optional[int] = None,
+              sample_rows: Optional[int] = None, ws: Optional[torch.Tensor] = None):
+    """The route's top-k entry over two sets packed on ONE grid: (idx, err, stats) as ``l2_topk``.  (The three
+    ``*_TOPK_CAND_MAX`` are one number: the same last launch, the same LDS.)"""
+    f = _SAD_FILTERS[route]
+    q, g = _l1_sets(None, None, q, g, f.set_now())
+    if q.d != g.d:
+        raise ValueError(f"{f.topk}: dimensions differ ({q.d}, {g.d})")
+    cap = L2_TOPK_CAND_MAX if cand_cap is None else int(cand_cap)
+    head = (*_sad_side(f, q), *_sad_side(f, g), g.d, _ptr(g.grid), float(alpha), float(beta), int(k), cap,
+            int(sample_rows or 0))
+    return _filtered_topk_call(getattr(lib, "cmve_" + f.topk), "cmve_" + f.topk, head, q.n, k,
+                               _sad_topk_workspace(route, q, g, k, cap, sample_rows), ws, g.device)
+
+
+# the public face of a SAD route: what a caller that holds a resident gallery (cmve.linas.inference, cmve.dist) needs,
+# without naming the families.  The per-family names are resolved when called, so a patched ``l1_topk_auto`` is asked.
+def sad_route_of(metric: int, score_dtype) -> Optional[str]:
+    """The SAD filter family that speaks for ``metric`` with these score words: ``"l1"``, ``"jaccard"`` or None.  The
+    word is the ``filter=`` value that forces it."""
+    return next((route for route, f in _SAD_FILTERS.items() if f.applies(metric, score_dtype)), None)
+
+
+def sad_set(route: str, rows, grid: Optional[torch.Tensor] = None) -> "L1Set":
+    """``rows`` packed for the route (an ``L1Set`` / a ``JaccardSet``), on their own grid or on ``grid``."""
+    return _SAD_FILTERS[route].set_now()(rows, grid=grid)
+
+
+def sad_min_pairs(route: str) -> Optional[int]:
+    """The pairs from which ``filter=None`` takes the route's COUNT filter (None: never)."""
+    return globals()[_SAD_FILTERS[route].min_pairs]
+
+
+def sad_topk_auto(route: str, n_q: int, n_g: int, packed: bool = False) -> bool:
+    """Whether ``pairwise_topk(filter=None)`` takes the route's top-k filter at this size (``l1_topk_auto`` /
+    ``jaccard_topk_auto``)."""
+    return globals()[_SAD_FILTERS[route].topk + "_auto"](n_q, n_g, packed=packed)
+
+
+def sad_topk_workspace(route: str, n_q, n_g, k: int) -> int:
+    """Bytes of workspace the route's top-k needs (``l1_topk_workspace`` / ``jaccard_topk_workspace``)."""
+    return globals()[_SAD_FILTERS[route].topk + "_workspace"](n_q, n_g, k)
+
+
 L1_TOPK_CAND_MAX = L2_TOPK_CAND_MAX  # cmve_l1_topk's limit on cand_cap: the same last launch, the same LDS
 # Auto dispatch of the K23 filter (``filter=None``), a rule of its own beside K20's (None in a constant switches its
 # clause off: "never taken automatically", as K22 allowed for ``L1_FILTER_MIN_PAIRS``).  From tools/l1_topk_bench.py ->
@@ -1014,26 +1102,12 @@ L1_TOPK_FILTER_MIN_PLAIN_PAIRS = 1 << 26  # plain rows: 64 x 1,048,576
 def l1_topk_auto(n_q: int, n_g: int, packed: bool = False) -> bool:
     """Whether ``pairwise_topk(filter=None)`` takes the K23 filter at this size (given PW_L1 with fp64 words);
     ``packed``: the gallery is an L1Set already.  A constant left None switches its clause off."""
-    if n_q < 1 or n_g < 1:
-        return False
-    if packed:
-        return ((L1_TOPK_FILTER_MIN_GALLERY is not None and n_g >= L1_TOPK_FILTER_MIN_GALLERY)
-                or (L1_TOPK_FILTER_MIN_PAIRS is not None and n_q * n_g >= L1_TOPK_FILTER_MIN_PAIRS))
-    return (L1_TOPK_FILTER_MIN_Q is not None and L1_TOPK_FILTER_MIN_PLAIN_PAIRS is not None
-            and n_q >= L1_TOPK_FILTER_MIN_Q and n_q * n_g >= L1_TOPK_FILTER_MIN_PLAIN_PAIRS)
-
-
-def _n_rows(s) -> int:
-    return int(s.n) if hasattr(s, "n") else int(s)
+    return _sad_topk_auto("l1", n_q, n_g, packed)
 
 
 def l1_topk_workspace(q, g, k: int, cand_cap: Optional[int] = None, sample_rows: Optional[int] = None) -> int:
     """Bytes of workspace ``cmve_l1_topk`` needs (host only: no launch).  q / g: an ``L1Set`` or a row count."""
-    n = C.c_int64()
-    check(lib.cmve_l1_topk_workspace(_n_rows(q), _n_rows(g), int(k),
-                                     L1_TOPK_CAND_MAX if cand_cap is None else int(cand_cap),
-                                     int(sample_rows or 0), C.byref(n)), "cmve_l1_topk_workspace")
-    return n.value
+    return _sad_topk_workspace("l1", q, g, k, cand_cap, sample_rows)
 
 
 def l1_topk(q: "L1Set", g: "L1Set", alpha: float, beta: float, k: int, cand_cap: Optional[int] = None,
@@ -1043,16 +1117,7 @@ def l1_topk(q: "L1Set", g: "L1Set", alpha: float, beta: float, k: int, cand_cap:
     on ONE grid (ValueError otherwise).  An unresolved query has idx[i, 0] == -2 and the rest of its row unwritten.
     k must not exceed the gallery.  ws: a caller-held device workspace, used when it holds ``l1_topk_workspace``
     bytes (a fresh one otherwise)."""
-    q, g = _l1_sets(None, None, q, g)
-    if q.d != g.d:
-        raise ValueError(f"l1_topk: dimensions differ ({q.d}, {g.d})")
-    cap = L1_TOPK_CAND_MAX if cand_cap is None else int(cand_cap)
-    a, b = q.raw, g.raw
-    head = (_ptr(a), _dtype_code(a), _pw_ld(a), q.n, _ptr(q.codes), _ptr(q.err), _ptr(b), _dtype_code(b), _pw_ld(b),
-            g.n, _ptr(g.codes), _ptr(g.err), g.d, _ptr(g.grid), float(alpha), float(beta), int(k), cap,
-            int(sample_rows or 0))
-    return _filtered_topk_call(lib.cmve_l1_topk, "cmve_l1_topk", head, q.n, k,
-                               l1_topk_workspace(q, g, k, cap, sample_rows), ws, g.device)
+    return _sad_topk("l1", q, g, alpha, beta, k, cand_cap, sample_rows, ws)
 
 
 JACCARD_TOPK_CAND_MAX = L2_TOPK_CAND_MAX  # cmve_jaccard_topk's limit on cand_cap: the same last launch, the same LDS
@@ -1079,23 +1144,13 @@ JACCARD_TOPK_FILTER_MIN_PLAIN_PAIRS = 1 << 26  # plain rows: 64 x 1,048,576
 def jaccard_topk_auto(n_q: int, n_g: int, packed: bool = False) -> bool:
     """Whether ``pairwise_topk(filter=None)`` takes the K25 filter at this size (given PW_JACCARD with float32 words);
     ``packed``: the gallery is a JaccardSet already.  A constant left None switches its clause off."""
-    if n_q < 1 or n_g < 1:
-        return False
-    if packed:
-        return ((JACCARD_TOPK_FILTER_MIN_GALLERY is not None and n_g >= JACCARD_TOPK_FILTER_MIN_GALLERY)
-                or (JACCARD_TOPK_FILTER_MIN_PAIRS is not None and n_q * n_g >= JACCARD_TOPK_FILTER_MIN_PAIRS))
-    return (JACCARD_TOPK_FILTER_MIN_Q is not None and JACCARD_TOPK_FILTER_MIN_PLAIN_PAIRS is not None
-            and n_q >= JACCARD_TOPK_FILTER_MIN_Q and n_q * n_g >= JACCARD_TOPK_FILTER_MIN_PLAIN_PAIRS)
+    return _sad_topk_auto("jaccard", n_q, n_g, packed)
 
 
 def jaccard_topk_workspace(q, g, k: int, cand_cap: Optional[int] = None, sample_rows: Optional[int] = None) -> int:
     """Bytes of workspace ``cmve_jaccard_topk`` needs (host only: no launch).  q / g: a ``JaccardSet`` or a row
     count."""
-    n = C.c_int64()
-    check(lib.cmve_jaccard_topk_workspace(_n_rows(q), _n_rows(g), int(k),
-                                          JACCARD_TOPK_CAND_MAX if cand_cap is None else int(cand_cap),
-                                          int(sample_rows or 0), C.byref(n)), "cmve_jaccard_topk_workspace")
-    return n.value
+    return _sad_topk_workspace("jaccard", q, g, k, cand_cap, sample_rows)
 
 
 def jaccard_topk(q: "JaccardSet", g: "JaccardSet", alpha: float, beta: float, k: int, cand_cap: Optional[int] = None,
@@ -1105,17 +1160,7 @@ def jaccard_topk(q: "JaccardSet", g: "JaccardSet", alpha: float, beta: float, k:
     are ``JaccardSet`` packed on ONE grid (TypeError / ValueError otherwise).  An unresolved query has
     idx[i, 0] == -2 and the rest of its row unwritten.  k must not exceed the gallery.  ws: a caller-held device
     workspace, used when it holds ``jaccard_topk_workspace`` bytes (a fresh one otherwise)."""
-    q, g = _l1_sets(None, None, q, g, cls=JaccardSet)
-    if q.d != g.d:
-        raise ValueError(f"jaccard_topk: dimensions differ ({q.d}, {g.d})")
-    cap = JACCARD_TOPK_CAND_MAX if cand_cap is None else int(cand_cap)
-
-    def side(s):
-        return (_ptr(s.raw), _dtype_code(s.raw), _pw_ld(s.raw), s.n, _ptr(s.codes), _ptr(s.err), _ptr(s.qsum),
-                _ptr(s.asum))
-    head = (*side(q), *side(g), g.d, _ptr(g.grid), float(alpha), float(beta), int(k), cap, int(sample_rows or 0))
-    return _filtered_topk_call(lib.cmve_jaccard_topk, "cmve_jaccard_topk", head, q.n, k,
-                               jaccard_topk_workspace(q, g, k, cap, sample_rows), ws, g.device)
+    return _sad_topk("jaccard", q, g, alpha, beta, k, cand_cap, sample_rows, ws)
 
 
 def _topk_filtered(metric: int, filtered, q, g, alpha, beta, k, score_dtype=torch.float64):
@@ -1198,25 +1243,21 @@ def pairwise_topk(q, g, metric: int, alpha: float, beta: float, score_dtype, k: 
         if _l2_applies(metric, score_dtype):
             if l2_topk_auto(n_q, n_g, g_set is not None) and _l2_set_ok(q_set) and _l2_set_ok(g_set):
                 route = "l2"
-        elif _SAD_FILTERS["l1"].applies(metric, score_dtype):
-            if l1_topk_auto(n_q, n_g, g_l1 is not None) and q.shape[1] <= L1_D_MAX:
-                route = "l1"
-        elif _SAD_FILTERS["jaccard"].applies(metric, score_dtype):
-            if jaccard_topk_auto(n_q, n_g, isinstance(g_l1, JaccardSet)) and q.shape[1] <= L1_D_MAX:
-                route = "jaccard"
+        else:
+            for name, f in _SAD_FILTERS.items():  # (the one family that speaks for the call, and its own rule alone)
+                if f.applies(metric, score_dtype):
+                    if sad_topk_auto(name, n_q, n_g, isinstance(g_l1, f.set_now())) and q.shape[1] <= L1_D_MAX:
+                        route = name
+                    break
     topk_stats = None
     if route and n_q > 0 and k <= L2_TOPK_CAND_MAX:
-        if route == "l1":
+        if route in _SAD_FILTERS:
+            f = _SAD_FILTERS[route]
             if q_set is not None or g_set is not None:
-                raise TypeError('pairwise_topk: a RowSet is packed for the Euclidean filter; filter="l1" takes an L1Set')
-            q_l1, g_l1 = _l1_sets(q, g, q_l1, g_l1)
-            filtered = lambda: l1_topk(q_l1, g_l1, alpha, beta, k, cand_cap, sample_rows, ws)  # noqa: E731
-        elif route == "jaccard":
-            if q_set is not None or g_set is not None:
-                raise TypeError('pairwise_topk: a RowSet is packed for the Euclidean filter; filter="jaccard" takes a '
-                                "JaccardSet")
-            q_l1, g_l1 = _l1_sets(q, g, q_l1, g_l1, cls=JaccardSet)
-            filtered = lambda: jaccard_topk(q_l1, g_l1, alpha, beta, k, cand_cap, sample_rows, ws)  # noqa: E731
+                raise TypeError(f'pairwise_topk: a RowSet is packed for the Euclidean filter; filter="{route}" takes '
+                                f"{f.set_words}")
+            q_l1, g_l1 = _l1_sets(q, g, q_l1, g_l1, f.set_now())
+            filtered = lambda: globals()[f.topk](q_l1, g_l1, alpha, beta, k, cand_cap, sample_rows, ws)  # noqa: E731
         elif route == "l2":
             if q_l1 is not None or g_l1 is not None:
                 raise TypeError('pairwise_topk: an L1Set is packed for filter="l1"; the Euclidean filter takes a RowSet')

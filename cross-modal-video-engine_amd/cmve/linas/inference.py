@@ -31,7 +31,7 @@ overrides the checkpoint's opt.measure (with both bypasses no checkpoint is read
 from __future__ import annotations
 
 import argparse
-import collections
+import functools
 import os
 import sys
 
@@ -39,11 +39,6 @@ import numpy as np
 
 from .. import engine
 from .._lib import SIM_F16
-
-
-# the SAD-filtered top-k that serves a measure (K23, K25): the ``filter`` word, the packed gallery's class, the auto
-# rule and the workspace size
-_SadRoute = collections.namedtuple("_SadRoute", "word set_cls auto workspace")
 
 
 class GalleryScorer:
@@ -98,9 +93,9 @@ class GalleryScorer:
             n_g = self.gallery.shape[0]
             sad = self._sad_route()
             if sad is not None and n_g and 1 <= self.gallery.shape[1] <= engine.L1_D_MAX and (
-                    (isinstance(filter, str) and filter == sad.word)
-                    or (filter is None and sad.auto(1 << 30, n_g, packed=True))):
-                self._packed = sad.set_cls(self.gallery)
+                    (isinstance(filter, str) and filter == sad)
+                    or (filter is None and engine.sad_topk_auto(sad, 1 << 30, n_g, packed=True))):
+                self._packed = engine.sad_set(sad, self.gallery)
                 self.gallery = self._packed.raw
             return
         emb = video_embs if hasattr(video_embs, "data_ptr") else np.asarray(video_embs)
@@ -110,13 +105,10 @@ class GalleryScorer:
         self._out = {}  # resident top-k outputs by (rows, k)
 
     def _sad_route(self):
-        """The SAD-filtered top-k that serves this measure, or None.  (Looked up per call: the tests patch the engine's
-        names.)"""
-        if self.measure in ('l1', 'l1_norm'):
-            return _SadRoute("l1", engine.L1Set, engine.l1_topk_auto, engine.l1_topk_workspace)
-        if self.measure == 'jaccard':
-            return _SadRoute("jaccard", engine.JaccardSet, engine.jaccard_topk_auto, engine.jaccard_topk_workspace)
-        return None
+        """The SAD-filtered top-k that serves this measure: its ``filter`` word (``engine.sad_route_of``), or None."""
+        from .evaluation import measure_spec
+        metric, _, _, _, sc_dt = measure_spec(self.measure, 1)
+        return engine.sad_route_of(metric, sc_dt)
 
     def topk_indices(self, cap_embs, topK=10):
         """[N_q, topK] gallery indices, best first (== np.argsort(cal_error(...)[i])[:topK])."""
@@ -159,14 +151,15 @@ class GalleryScorer:
         flt = False
         sad = self._sad_route() if isinstance(self._packed, engine.L1Set) else None
         if self._packed is not None and q.shape[0] and 1 <= k <= engine.L2_TOPK_CAND_MAX:
-            forced = (isinstance(self.filter, str) and self.filter == sad.word) if sad else self.filter is True
-            auto = sad.auto if sad else engine.l2_topk_auto
+            forced = (isinstance(self.filter, str) and self.filter == sad) if sad else self.filter is True
+            auto = functools.partial(engine.sad_topk_auto, sad) if sad else engine.l2_topk_auto
             flt = forced or (self.filter is None and not self._filter_off
                              and auto(q.shape[0], g.shape[0], packed=True))
         # ONE workspace stays resident between calls, sized for that route only and grown when a call needs more
         need = 0
         if flt and sad:
-            need = sad.workspace(q.shape[0], g.shape[0], k)  # (the queries are packed on the gallery's grid)
+            # (the queries are packed on the gallery's grid)
+            need = engine.sad_topk_workspace(sad, q.shape[0], g.shape[0], k)
         elif flt:
             q = engine.RowSet(q, eps=0.0, with_lo=False, device=g.device)
             need = engine.l2_topk_workspace(q, self._packed, k)
@@ -175,7 +168,7 @@ class GalleryScorer:
         if need and (self._ws is None or self._ws.numel() < need):
             self._ws = torch.empty(need, dtype=torch.uint8, device=g.device)
         idx, _, st = engine.pairwise_topk(q, self._packed if flt else g, metric, alpha, beta, sc_dt, k, ws=self._ws,
-                                          filter=(sad.word if sad else True) if flt else False, return_stats=True)
+                                          filter=(sad if sad else True) if flt else False, return_stats=True)
         if st is not None and st["fallback"]:
             self._filter_off = True
         return idx

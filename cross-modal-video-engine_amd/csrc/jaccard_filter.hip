@@ -137,7 +137,7 @@ extern "C" int cmve_jaccard_count(cmve_handle_t h, const void* A, int32_t a_dtyp
   CMVE_REQUIRE(h && stats && (A || !na) && (B || !nb), "%s: NULL argument", name);
   const FltRows rows{A, a_dtype, lda, na, B, b_dtype, ldb, nb, d};
   auto own_checks = [&]() -> int {
-    return sad_count_checks(name, d, rows, a_codes, b_codes, grid, a_codes && a_err && a_qsum && a_asum,
+    return sad_checks(name, d, rows, a_codes, b_codes, grid, a_codes && a_err && a_qsum && a_asum,
                             b_codes && b_err && b_qsum && b_asum,
                             "the codes, the row errors, the row sums or the grid are missing (cmve_l1_grid, "
                             "cmve_l1_pack, cmve_jaccard_rowsums)");

@@ -225,7 +225,7 @@ extern "C" int cmve_l1_count(cmve_handle_t h, const void* A, int32_t a_dtype, in
   CMVE_REQUIRE(h && stats && (A || !na) && (B || !nb), "%s: NULL argument", name);
   const FltRows rows{A, a_dtype, lda, na, B, b_dtype, ldb, nb, d};
   auto own_checks = [&]() -> int {
-    return sad_count_checks(name, d, rows, a_codes, b_codes, grid, a_codes && a_err, b_codes && b_err,
+    return sad_checks(name, d, rows, a_codes, b_codes, grid, a_codes && a_err, b_codes && b_err,
                             "the codes, the row errors or the grid are missing (cmve_l1_grid, cmve_l1_pack)");
   };
   auto main_launch = [&](hipStream_t st, const FltArgs& f) {

@@ -35,6 +35,21 @@ static inline void l1f_pads(int64_t n, int64_t d, int64_t& n_pad, int64_t& d_pad
 // the raw rows every L1 entry takes beside the codes
 static inline bool l1f_dtype_ok(int32_t t) { return t == CMVE_F32 || t == CMVE_F64; }
 
+// what the four SAD entries (K22 / K24: the counts, K23 / K25: the top-ks) ask of their own operands (`name`: the
+// entry; r: the raw rows, a top-k's queries as A).  a_have / b_have: every per-row array of the side is there;
+// `missing`: the entry's words for one that is not
+static inline int sad_checks(const char* name, int64_t d, const FltRows& r, const void* a_codes, const void* b_codes,
+                             const double* grid, bool a_have, bool b_have, const char* missing) {
+  CMVE_REQUIRE(d > 0 && d <= L1F_D_MAX, "%s: d must be in [1, %lld] (%lld): the u32 SAD is exact up to there", name,
+               (long long)L1F_D_MAX, (long long)d);
+  CMVE_REQUIRE(r.na >= 0 && r.nb >= 0 && r.na < (1ll << 31) && r.nb < (1ll << 31) && r.lda >= d && r.ldb >= d,
+               "%s: bad shape", name);
+  CMVE_REQUIRE(l1f_dtype_ok(r.a_dtype) && l1f_dtype_ok(r.b_dtype), "%s: rows must be CMVE_F32/CMVE_F64", name);
+  CMVE_REQUIRE(grid && (a_have || !r.na) && (b_have || !r.nb), "%s: %s", name, missing);
+  CMVE_REQUIRE(((((uintptr_t)a_codes) | ((uintptr_t)b_codes)) & 15) == 0, "%s: codes must be 16-byte aligned", name);
+  return CMVE_OK;
+}
+
 // THE grid (lo, s) every kernel derives from the two device words {lo, hi}: min and max of the eligible elements.
 // No eligible element (the words are still +inf, -inf), hi == lo, NaN: lo = 0, s = 1.  Any grid is a correct one --
 // a bad one only enlarges the rows' errors, and with them the band.

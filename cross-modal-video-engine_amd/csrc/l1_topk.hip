@@ -17,100 +17,43 @@
 //                                        emitted
 // so out_idx / out_err are, word for word, cmve_pairwise_topk's.  The grid offset lo cancels in the SAD: rows
 // clustered far from the origin keep intervals as tight as rows around it.  Plain vector stores and integer atomics
-// only.  This file holds what is this filter's alone: the pass kernel's argument block, its interval and thread
-// layout, and the entry's checks of its own operands.  The SAD tile is l1_filter_tile.h's (l1f_sad_tile, shared with
-// K22's count kernel); the tail of the epilogue, launches A' and C and the host body (l2t_topk_run: checks, workspace,
-// the rounds of four launches) are topk_filter_tile.h's, shared with K20.
-#include "l1_filter_tile.h"
-#include "topk_filter_tile.h"
+// only.  This file holds what is this filter's alone: the policy of the pass kernel (L1tPass: its own argument, a
+// side's row error, l1f_interval + l2t_pair as the pair step) and the entry.  The pass kernel's body, its argument
+// prefix and the workspace entry are sad_topk.h's, shared with K25; the SAD tile and the entry's checks of its own
+// operands l1_filter_tile.h's (l1f_sad_tile, sad_checks: shared with the count kernels); the tail of the epilogue,
+// launches A' and C and the host body (l2t_topk_run: checks, workspace, the rounds of four launches)
+// topk_filter_tile.h's, shared with K20.
+#include "sad_topk.h"
 
 namespace cmve {
 namespace {
 
-struct L1tArgs {
-  const uint32_t* q_codes;  // tiled (l1_filter_tile.h)
-  const uint32_t* g_codes;
-  const double* q_err;
-  const double* g_err;
-  const double* grid;
-  int64_t q0, q_end;  // this round's queries; q0 is a multiple of 128
-  int64_t ng;         // columns of this pass: the sample (A) or the gallery (B)
-  int nkt;            // K tiles
-  double alpha, lim;
-  float* ub;          // A: [q_end - q0][ub_ld] upper key bounds
-  int64_t ub_ld;
-  const double* thr;  // B: per query the L1-distance threshold (NaN: unresolved, nothing is appended)
-  int32_t* cnt;       // B: candidates found per query
-  int32_t* list;      // B: [q_end - q0][cap] column ids
-  int64_t cap;
-  l2f_u64* stats;     // {pairs excluded, candidates found, candidates re-scored, unresolved queries}
-  int tiles_a, tiles_b;
+// sad_topk.h's pass kernel under the L1 policy: a side carries its row error, a pair's interval is l1f_interval's and
+// its step l2t_pair's
+struct L1tPass {
+  struct Args : SadTopkArgs {
+    double lim;  // below it alpha * S + beta cannot overflow
+  };
+  static constexpr int NS = 1;
+  template <bool G>
+  static __device__ __forceinline__ void side(const Args& a, bool v, int64_t i, double, double, double (&x)[NS]) {
+    x[0] = v ? (G ? a.g_err : a.q_err)[i] : (double)NAN;  // a row beyond the pass: no interval (and never used)
+  }
+  static __device__ __forceinline__ double step(const double& s) { return s; }
+  template <int MODE>
+  static __device__ __forceinline__ void pair(const Args& a, bool pos, int64_t i, int64_t j, uint32_t sad, double s,
+                                              const double (&eq)[NS], const double (&eg)[NS], double thr, bool full,
+                                              int& n_cand, int& n_excl) {
+    double dlo, dhi;
+    l1f_interval(sad, s, eq[0], eg[0], a.lim, dlo, dhi);
+    l2t_pair<MODE>(a, pos, i, j, dlo, dhi, thr, full, n_cand, n_excl);
+  }
 };
-
-// the epilogue's LDS, laid over the staging buffers once the K loop is done
-struct L1tEpi {
-  double qe[L1F_BM], ge[L1F_BN];  // row errors of the tile's rows / columns
-  double thr[L1F_BM];
-  int full[L1F_BM];  // the row's list had overflowed when this tile began: its candidates are counted, not appended
-  int n_cand, n_excl;
-  double s;  // the grid's step
-};
-static_assert(sizeof(L1tEpi) <= L1F_SMEM, "the epilogue's LDS fits the staging buffers");
 
 // MODE 0: launch A (the witnesses' bounds), MODE 1: launch B (the candidates)
 template <int MODE>
-__global__ __launch_bounds__(256, 4) void l1t_pass_kernel(L1tArgs a) {
-  __shared__ __attribute__((aligned(16))) char smem[L1F_SMEM];
-  const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
-  int ta, tb_;
-  l2f_tile_of_block(blockIdx.x, a.tiles_a, a.tiles_b, ta, tb_);
-  // q0 is a multiple of 128: the round's tile ta is tile q0 / 128 + ta of the tiled codes.  Both sets hold n_pad (a
-  // multiple of 128) rows and d_pad elements: the tiles' blocks are in bounds.
-  const int64_t qt = a.q0 / L1F_BM + ta;
-  const int64_t i0 = qt * L1F_BM, j0 = (int64_t)tb_ * L1F_BN;
-
-  // ---- the SADs: acc[u][v] of the pair (query i0 + l1f_row(ty, u), gallery row j0 + l1f_row(tx, v))
-  uint32_t acc[8][8];
-  l1f_sad_tile(a.q_codes + qt * a.nkt * L1F_TILE_DW, a.g_codes + (int64_t)tb_ * a.nkt * L1F_TILE_DW, a.nkt, smem, acc);
-
-  // ---- epilogue (every wave has passed the loop's last barrier: smem is free): one threshold per row, no rounds ----
-  L1tEpi& E = *(L1tEpi*)smem;
-  if (tid < L1F_BM) {
-    const int64_t i = i0 + tid;
-    const bool v = i < a.q_end;
-    E.qe[tid] = v ? a.q_err[i] : (double)NAN;  // a row beyond the round: no interval (and never used)
-    l2t_row_state<MODE>(a, E, tid, i, v);
-  } else {
-    const int t = tid - L1F_BM;
-    const int64_t j = j0 + t;
-    E.ge[t] = j < a.ng ? a.g_err[j] : (double)NAN;
-  }
-  if (tid == 0) {
-    E.n_cand = E.n_excl = 0;
-    double lo_unused, s;
-    l1f_grid_of(a.grid, lo_unused, s);
-    E.s = s;
-  }
-  __syncthreads();
-  const bool pos = a.alpha > 0.0;
-  const double s = E.s;
-  int n_cand = 0, n_excl = 0;
-#pragma unroll
-  for (int u = 0; u < 8; ++u) {
-    const int64_t i = i0 + l1f_row(ty, u);
-    const double qe = E.qe[l1f_row(ty, u)];
-    const double thr = MODE == 1 ? E.thr[l1f_row(ty, u)] : 0.0;
-    const bool full = MODE == 1 ? E.full[l1f_row(ty, u)] != 0 : false;
-#pragma unroll
-    for (int v = 0; v < 8; ++v) {
-      const int64_t j = j0 + l1f_row(tx, v);
-      if (i >= a.q_end || j >= a.ng) continue;
-      double dlo, dhi;
-      l1f_interval(acc[u][v], s, qe, E.ge[l1f_row(tx, v)], a.lim, dlo, dhi);
-      l2t_pair<MODE>(a, pos, i, j, dlo, dhi, thr, full, n_cand, n_excl);
-    }
-  }
-  l2t_flush<MODE>(a, E, tid, n_cand, n_excl);
+__global__ __launch_bounds__(256, 4) void l1t_pass_kernel(L1tPass::Args a) {
+  sad_topk_body<L1tPass, MODE>(a);
 }
 
 }  // namespace
@@ -120,12 +63,7 @@ using namespace cmve;
 
 extern "C" int cmve_l1_topk_workspace(int64_t n_q, int64_t n_g, int32_t k, int64_t cand_cap, int64_t sample_rows,
                                       int64_t* bytes) {
-  CMVE_REQUIRE(bytes, "cmve_l1_topk_workspace: NULL argument");
-  if (int rc = l2t_check_params("cmve_l1_topk_workspace", k, cand_cap, sample_rows)) return rc;
-  CMVE_REQUIRE(n_q >= 0 && n_g >= 0 && n_q < (1ll << 31) && n_g < (1ll << 31),
-               "cmve_l1_topk_workspace: bad shape (%lld, %lld rows)", (long long)n_q, (long long)n_g);
-  *bytes = l2t_layout(n_q, n_g, k, cand_cap, sample_rows).bytes;
-  return CMVE_OK;
+  return sad_topk_workspace("cmve_l1_topk_workspace", n_q, n_g, k, cand_cap, sample_rows, bytes);
 }
 
 extern "C" int cmve_l1_topk(cmve_handle_t h, const void* Q, int32_t q_dtype, int64_t ldq, int64_t n_q,
@@ -135,29 +73,19 @@ extern "C" int cmve_l1_topk(cmve_handle_t h, const void* Q, int32_t q_dtype, int
                             int64_t ws_bytes, int64_t* out_idx, double* out_err, int64_t* stats) {
   const char* name = "cmve_l1_topk";
   CMVE_REQUIRE(h && stats && (Q || !n_q) && (G || !n_g), "%s: NULL argument", name);
+  const FltRows rows{Q, q_dtype, ldq, n_q, G, g_dtype, ldg, n_g, d};
   auto own_checks = [&]() -> int {
-    CMVE_REQUIRE(d > 0 && d <= L1F_D_MAX, "%s: d must be in [1, %lld] (%lld): the u32 SAD is exact up to there", name,
-                 (long long)L1F_D_MAX, (long long)d);
-    CMVE_REQUIRE(n_q >= 0 && n_g >= 0 && n_q < (1ll << 31) && n_g < (1ll << 31) && ldq >= d && ldg >= d,
-                 "%s: bad shape", name);
-    CMVE_REQUIRE(l1f_dtype_ok(q_dtype) && l1f_dtype_ok(g_dtype), "%s: rows must be CMVE_F32/CMVE_F64", name);
-    CMVE_REQUIRE(grid && ((q_codes && q_err) || !n_q) && ((g_codes && g_err) || !n_g),
-                 "%s: the codes, the row errors or the grid are missing (cmve_l1_grid, cmve_l1_pack)", name);
-    CMVE_REQUIRE(((((uintptr_t)q_codes) | ((uintptr_t)g_codes)) & 15) == 0, "%s: codes must be 16-byte aligned", name);
-    return CMVE_OK;
+    return sad_checks(name, d, rows, q_codes, g_codes, grid, q_codes && q_err, g_codes && g_err,
+                      "the codes, the row errors or the grid are missing (cmve_l1_grid, cmve_l1_pack)");
   };
   auto pass_launch = [&](int mode, hipStream_t st, const L2tRound& r, const L2tWs& w) {
-    int64_t n_pad = 0, d_pad = 0;
-    l1f_pads(n_q, d, n_pad, d_pad);
-    const L1tArgs a{(const uint32_t*)q_codes, (const uint32_t*)g_codes, q_err, g_err, grid, r.q0, r.q_end, r.ng,
-                    (int)(d_pad / L1F_BK), alpha,
-                    (1e300 - fabs(beta)) / fabs(alpha),  // lim: below it alpha * S + beta cannot overflow
-                    w.ub, w.ub_ld, w.thr, w.cnt, w.list, w.cap, w.stats, r.tiles_a, r.tiles_b};
+    const L1tPass::Args a{sad_topk_args(r, w, q_codes, q_err, g_codes, g_err, grid, n_q, d, alpha),
+                          (1e300 - fabs(beta)) / fabs(alpha)};
     hipLaunchKernelGGL(mode == 0 ? l1t_pass_kernel<0> : l1t_pass_kernel<1>, dim3((unsigned)(r.tiles_a * r.tiles_b)),
                        dim3(256), 0, st, a);
   };
-  return l2t_topk_run<CMVE_PW_L1>(name, "l1_topk", h, FltRows{Q, q_dtype, ldq, n_q, G, g_dtype, ldg, n_g, d}, alpha,
-                                  beta, k, cand_cap, sample_rows, ws, ws_bytes, out_idx, out_err, stats,
+  return l2t_topk_run<CMVE_PW_L1>(name, "l1_topk", h, rows, alpha, beta, k, cand_cap, sample_rows, ws, ws_bytes,
+                                  out_idx, out_err, stats,
                                   2.0 * ((double)d + 16.0) * L2F_U,  // rho: DESIGN s4 (K22)
                                   own_checks, pass_launch);
 }

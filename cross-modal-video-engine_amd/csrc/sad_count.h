@@ -277,21 +277,6 @@ static inline SadArgs sad_count_args(const FltArgs& f, const void* a_codes, cons
                  l.col_pos, f.band.band, f.band.cap, f.band.stats, f.tiles_a, f.tiles_b};
 }
 
-// what both count entries ask of their own operands (`name`: the entry).  a_have / b_have: every per-row array of
-// the side is there; `missing`: the entry's words for one that is not
-static inline int sad_count_checks(const char* name, int64_t d, const FltRows& r, const void* a_codes,
-                                   const void* b_codes, const double* grid, bool a_have, bool b_have,
-                                   const char* missing) {
-  CMVE_REQUIRE(d > 0 && d <= L1F_D_MAX, "%s: d must be in [1, %lld] (%lld): the u32 SAD is exact up to there", name,
-               (long long)L1F_D_MAX, (long long)d);
-  CMVE_REQUIRE(r.na >= 0 && r.nb >= 0 && r.na < (1ll << 31) && r.nb < (1ll << 31) && r.lda >= d && r.ldb >= d,
-               "%s: bad shape", name);
-  CMVE_REQUIRE(l1f_dtype_ok(r.a_dtype) && l1f_dtype_ok(r.b_dtype), "%s: rows must be CMVE_F32/CMVE_F64", name);
-  CMVE_REQUIRE(grid && (a_have || !r.na) && (b_have || !r.nb), "%s: %s", name, missing);
-  CMVE_REQUIRE(((((uintptr_t)a_codes) | ((uintptr_t)b_codes)) & 15) == 0, "%s: codes must be 16-byte aligned", name);
-  return CMVE_OK;
-}
-
 // the workspace of a count entry (`name`: the *_count_workspace entry)
 static inline int sad_count_workspace(const char* name, int64_t band_cap, int64_t* bytes) {
   CMVE_REQUIRE(bytes, "%s: NULL argument", name);

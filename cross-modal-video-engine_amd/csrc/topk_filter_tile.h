@@ -11,8 +11,9 @@
 //   l2t_finish_kernel      launch C: re-score, sort, emit
 //   l2t_sample, l2t_layout, l2t_check_params   the sample, the workspace and the checks of k / cand_cap / sample_rows
 //   l2t_topk_run           the host body: checks, memset, the rounds of four launches
-// A filter supplies its operands' checks, its pass kernel (tile, interval, thread layout) and the launch of it.  The
-// derivations are DESIGN s4, "K20", "K23" and "K25".
+// A filter supplies its operands' checks, its pass kernel (tile, interval, thread layout) and the launch of it; the
+// two SAD filters' pass kernels are one body (sad_topk.h) under a policy each.  The derivations are DESIGN s4, "K20",
+// "K23" and "K25".
 #ifndef CMVE_TOPK_FILTER_TILE_H
 #define CMVE_TOPK_FILTER_TILE_H
 #include "l2_filter_tile.h"
@@ -34,9 +35,9 @@ __device__ __forceinline__ float l2t_f32_up(double x) {
 }
 
 // ---- the common tail of the two pass kernels' epilogues.  MODE 0: launch A (the witnesses' bounds), MODE 1: launch B
-// (the candidates).  `Args` is the kernel's own flat argument block (L2tArgs, L1tArgs): it names q0, thr, cnt, cap, ub,
-// ub_ld, list and stats; `Epi` its epilogue LDS: it names thr[128] and full[128] by tile row, and n_cand and n_excl,
-// zeroed before the pairs.  (The helpers take a, E and the global row i whole: handed `double& thr`, `int& full` or
+// (the candidates).  `Args` is the kernel's own flat argument block (L2tArgs; sad_topk.h's SadTopkArgs under a policy's
+// Args): it names q0, thr, cnt, cap, ub, ub_ld, list and stats; `Epi` its epilogue LDS (L2tEpi, SadTopkEpi<NS>): it names
+// thr[128] and full[128] by tile row, and n_cand and n_excl, zeroed before the pairs.  (The helpers take a, E and the global row i whole: handed `double& thr`, `int& full` or
 // i - a.q0 instead, l2t_pass_kernel<1> compiles to another instruction stream; as they are, K20's two kernels keep
 // the streams they had with the statements written out.)
 
@@ -296,8 +297,9 @@ static inline int l2t_check_params(const char* name, int32_t k, int64_t cand_cap
 
 // ---- the host body -------------------------------------------------------------------------------------------------------
 // what l2t_topk_run hands a filter's pass launch beside the filter's own operands: the workspace carved up (the same
-// for every round) and one pass of one round.  The pass kernels keep their flat argument blocks (L2tArgs, L1tArgs) and
-// are filled from these: an embedded struct moves a kernel's scalar loads (filter_count.h).
+// for every round) and one pass of one round.  The pass kernels keep their flat argument blocks (L2tArgs; SadTopkArgs,
+// which sad_topk_args fills) and are filled from these: an embedded struct moves a kernel's scalar loads
+// (filter_count.h).
 struct L2tWs {
   float* ub;       // [qc][ub_ld] upper key bounds
   int64_t ub_ld;
