@@ -168,6 +168,9 @@ SIGNATURES = {
     "cmve_cos_count_workspace": (C.c_int, [_P(Rows), _P(Rows), _i64, _P(_i64)]),
     "cmve_cos_count": (C.c_int, [_vp, _P(Rows), _P(Rows), _vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _vp,
                                  _i64, _vp]),
+    "cmve_cos_item_scores_sharded": (C.c_int, [_vp, _P(Rows), _P(Rows), _vp, _vp, _i64, _i64, _i32, _i64, _vp]),
+    "cmve_cos_count_resolved": (C.c_int, [_vp, _P(Rows), _P(Rows), _vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _i64, _vp,
+                                          _vp, _i64, _vp]),
     "cmve_l2_topk_workspace": (C.c_int, [_P(Rows), _P(Rows), _i32, _i64, _i64, _P(_i64)]),
     "cmve_l2_topk": (C.c_int, [_vp, _P(Rows), _P(Rows), _f64, _f64, _i32, _i64, _i64, _vp, _i64, _vp, _vp, _vp]),
     "cmve_l1_topk_workspace": (C.c_int, [_i64, _i64, _i32, _i64, _i64, _P(_i64)]),

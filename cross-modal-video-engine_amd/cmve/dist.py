@@ -493,11 +493,14 @@ class ShardedGallery:
 
     ``comm``: a communicator (default: TorchComm over torch.distributed's process group).
     ``filter=True`` needs a Euclidean measure: ValueError under any other, cosine included; ``filter="l1"`` needs
-    l1 / l1_norm, ``filter="jaccard"`` needs jaccard: ValueError under any other."""
+    l1 / l1_norm, ``filter="jaccard"`` needs jaccard, ``filter="cosine"`` needs cosine: ValueError under any other.
+    Under cosine ``filter="cosine"`` builds a ``CosineFilterShardedGallery``, the cosine family with the one-pass route
+    (K27) that the measure family takes: ``_OnePassRoute`` holds that route's coordination once, for both."""
 
     def __new__(cls, *args, **kw):
-        if cls is ShardedGallery:  # measure: __init__'s 10th argument
-            cls = _family(kw.get('measure', args[9] if len(args) > 9 else 'cosine'))
+        if cls is ShardedGallery:  # measure, filter: __init__'s 10th and 11th arguments
+            cls = _family(kw.get('measure', args[9] if len(args) > 9 else 'cosine'),
+                          kw.get('filter', args[10] if len(args) > 10 else None))
         return object.__new__(cls)
 
     def __init__(self, local_embs, offset: int, n_global: int, with_lo: bool = False, eps: float = 0.0,
@@ -509,10 +512,14 @@ class ShardedGallery:
         elif isinstance(filter, str) and filter == "jaccard":
             if measure not in _JACCARD_MEASURES:
                 raise ValueError(f'ShardedGallery: filter="jaccard" needs the jaccard measure, not {measure!r}')
+        elif isinstance(filter, str) and filter == "cosine":
+            if measure != 'cosine':
+                raise ValueError(f'ShardedGallery: filter="cosine" needs the cosine measure, not {measure!r}')
         elif filter and measure not in _L2_MEASURES:
             raise ValueError(f"ShardedGallery: filter=True needs a Euclidean measure {_L2_MEASURES}, not {measure!r}")
-        if not isinstance(self, _family(measure)):  # a family built directly, or a subclass of this base alone
-            raise ValueError(f"ShardedGallery: measure {measure!r} needs a {_family(measure).__name__}, "
+        family = _family(measure, filter)
+        if not isinstance(self, family):  # a family built directly, or a subclass of this base alone
+            raise ValueError(f"ShardedGallery: measure {measure!r} needs a {family.__name__}, "
                              f"not a {type(self).__name__}")
         self.comm = _comm(comm)
         self.rank, self.world = self.comm.rank, self.comm.world
@@ -585,6 +592,131 @@ class ShardedGallery:
             idx = torch.where(idx >= 0, idx + self.offset, idx)
             idx, sc = pad_topk(idx, sc, k)  # (shards may hold fewer than k rows)
         return merge_topk(idx, sc, k, self.comm, to_host=to_host)
+
+
+class _OnePassRoute:
+    """The coordination of the one-pass route, once, for the families that take it (mixed in ahead of
+    ``ShardedGallery``): global-id lists, the item words scored where they live and merged by an int64 SUM, ONE count
+    over (all gathered captions) x (this shard), ONE all-reduce(SUM) of the t2v positions and the v2t R@K sums, and
+    cal_perf's ending on those positions; the shard's band list, its counters and the plan after a pass that ended on
+    the host.  A family supplies the shard-local arithmetic: ``_pw_rows`` (the captions as the count takes them),
+    ``_pw_items``, ``_pw_count`` and ``_pw_ranks``."""
+
+    def _pw_init(self, filter, band_cap):
+        self._pw_filter = filter
+        self._pw_band_cap = band_cap
+        self._pw_stats = None  # the device counters of the last pass's filtered count
+        self._pw_filter_off = False  # latched by a top-k the filter handed back whole, or a count whose band
+        #                              exceeds 1/8 of the pairs: this shard stays on its unfiltered route
+        self._pw_band = None  # the shard's band list, persistent; _pw_plan grows it
+        self._pw_pairs = 0  # the pairs of the last filtered count
+
+    @property
+    def filter_stats(self):
+        """The counters of the last pass's filtered count over this shard -- {decided, band, rescored, overflow,
+        fallback}, fallback = the band list overflowed and the canonical count gave the words -- or None when that
+        pass did not try the filter.  Read from the device: this synchronises."""
+        if self._pw_stats is None:
+            return None
+        st = engine._l2_count_stats(self._pw_stats.cpu().numpy())
+        return dict(st, fallback=st["overflow"] == 1)
+
+    def _pw_plan(self):
+        """After a pass that ended on the host anyway: grow this shard's band list to the reported need, or latch
+        the unfiltered route when the band exceeds 1/8 of the pairs (``engine.l2_band_plan``).  Shard-local: it may
+        change what a later ``_pw_count`` launches, never its words and never a collective, so the ranks need not
+        agree on it."""
+        st = self.filter_stats
+        if st is None:
+            return
+        cap = engine.l2_band_plan(self._pw_pairs, st["band"], st["overflow"], self._pw_band.numel())
+        if cap is None:
+            self._pw_filter_off = True
+        elif cap > self._pw_band.numel():
+            self._pw_band = torch.empty(cap, dtype=torch.int64, device=self.device)
+
+    def _pw_csr(self, lists, n_other: Optional[int], what: str):
+        """(off, idx, items, end) of GT lists with GLOBAL ids, end = the largest id + 1 (a host int: _pw_pass checks
+        it where the other side's size is known).  An id outside [0, n_other) has no owner: ValueError."""
+        off = np.zeros(len(lists) + 1, np.int64)
+        np.cumsum(np.fromiter((len(l) for l in lists), np.int64, count=len(lists)), out=off[1:])
+        items = int(off[-1])
+        ids = np.fromiter((g for l in lists for g in l), np.int64, count=items)  # int64: no wrap before the check
+        end = int(ids.max()) + 1 if items else 0
+        if items and (ids.min() < 0 or end > (1 << 31 if n_other is None else n_other)):
+            raise ValueError(f"ShardedGallery: a {what} id outside [0, {'2^31' if n_other is None else n_other})")
+        idx = ids.astype(np.int32) if items else np.zeros(1, np.int32)
+        return torch.from_numpy(off).to(self.device), torch.from_numpy(idx).to(self.device), items, end
+
+    def _pw_pass(self, q, n_q: int, row, col):
+        """One evaluation of the gathered captions q against every shard, no host
+        synchronisation.  row: _pw_csr of every caption's GT videos (global ids, the same on every rank) or
+        None; col: _pw_csr of this shard's videos' GT captions (gathered order) or None.  Returns
+        (t2v ranks | None, t2v 0-based positions int32 [items] | None -- both global, equal on every rank; v2t ranks
+        | None, v2t positions | None -- this shard's videos; v2t recall sums int64 [4] of all shards | None; the merged
+        t2v item words fp64 [items] | None -- equal on every rank)."""
+        # an item outside the other side would get the zero word, a legitimate score: refuse it (host ints, no sync)
+        if row is not None and row[3] > self.n_global:
+            raise ValueError(f"ShardedGallery: a GT video id outside [0, {self.n_global})")
+        if col is not None and col[3] > n_q:
+            raise ValueError(f"ShardedGallery: a GT caption id outside [0, {n_q})")
+        solo = _solo(self.comm)
+        row_side = col_side = None
+        if row is not None:
+            off, idx, items = row[:3]
+            # each item is scored where its video lives; the other shards hold the zero word, so the SUM of the
+            # scores' integer words is the owner's word on every rank (NaN, +-inf and -0.0 as they are)
+            row_sc = self._pw_items(q, (off, idx), items, False, self.offset)
+            if not solo and items:
+                self.comm.all_reduce(row_sc.view(torch.int64), "sum")
+            # the NaN items' n_global - ... comes from ONE rank (the count entry applies it on an empty shard too)
+            row_side = (off, row_sc, self.n_global if self.rank == 0 else 0)
+        if col is not None:
+            coff, cidx, citems = col[:3]
+            # a shard video's GT captions are all here after the gather: scores and positions are rank-local
+            col_side = (coff, self._pw_items(q, (coff, cidx), citems, True, 0), n_q)
+        rpos, cpos = self._pw_count(q, row_side, col_side)
+        v2t = self._pw_ranks(col_side[0], col_side[1], cpos, n_q) if col is not None else None
+        rec = recall_counts_device(v2t) if col is not None else torch.zeros(4, dtype=torch.int64, device=self.device)
+        parts = ([rpos.to(torch.int64)] if row is not None else []) + [rec.to(torch.int64)]
+        # ONE all-reduce(SUM): the t2v positions and the v2t R@K sums
+        both = reduce_counts(torch.cat(parts), self.comm)
+        t2v = t2v_pos = None
+        if row is not None:
+            t2v_pos = both[:-4].to(torch.int32)
+            t2v = self._pw_ranks(row_side[0], row_side[1], t2v_pos, self.n_global)
+        return (t2v, t2v_pos, v2t, cpos, (both[-4:] if col is not None else None),
+                row_side[1] if row is not None else None)
+
+    def _pw_evaluate_gathered(self, q, n_q: int, t2v_gts, v2t_gts, words: bool = False):
+        """(t2v ranks, t2v positions, v2t ranks of ALL videos, this shard's v2t positions) on the host from one
+        _pw_pass; ``words``: also the merged t2v item words, as the pass left them on the device."""
+        row = self._pw_csr(t2v_gts, self.n_global, "GT video") if t2v_gts is not None else None
+        col = self._pw_csr(self.local_v2t_lists(v2t_gts), n_q, "GT caption") if v2t_gts is not None else None
+        t2v, t2v_pos, v2t, v2t_pos, _, row_words = self._pw_pass(q, n_q, row, col)
+        t2v, v2t, t2v_pos, v2t_pos = self._ranks_to_host(t2v, v2t, t2v_pos, v2t_pos)
+        self._pw_plan()  # (after the result copies: the stream has drained)
+        return (t2v, t2v_pos, v2t, v2t_pos) + ((row_words,) if words else ())
+
+    def _pw_first_positions(self, t2v_pos, firsts, row_words):
+        """The 1-based position of each caption's FIRST GT from the positions of every item (firsts: the first
+        item of every non-empty list; row_words: the items' merged words on the device)."""
+        return t2v_pos[firsts] + 1
+
+    def _pw_cal_perf(self, q, n_q: int, v2t_gt, t2v_gt):
+        """cal_perf's two 6-tuples from ONE _pw_pass over the captions' rows q: ranks and both mAPs (t2v: each
+        caption's FIRST GT; v2t: every GT caption of a video) come from its positions, multi-GT lists included."""
+        v2t_lists, t2v_lists = self._perf_lists(n_q, v2t_gt, t2v_gt)
+        t2v, t2v_pos, v2t, v2t_pos, row_words = self._pw_evaluate_gathered(q, n_q, t2v_lists, v2t_lists, words=True)
+        # the first GT's position is among every item's
+        lens = np.fromiter((len(l) for l in t2v_lists), np.int64, count=n_q)
+        has = lens > 0
+        ap = np.zeros(n_q, np.float64)
+        ap[has] = 1.0 / self._pw_first_positions(t2v_pos, (np.cumsum(lens) - lens)[has], row_words)
+        t2v_map = float(np.mean(ap))
+        offs = np.cumsum([0] + [len(l) for l in self.local_v2t_lists(v2t_lists)])
+        aps = [ap_from_positions(v2t_pos[offs[j]:offs[j + 1]] + 1) for j in range(self.n)]
+        return self._perf(t2v, v2t, t2v_map, aps)
 
 
 class CosineShardedGallery(ShardedGallery):
@@ -777,7 +909,7 @@ class CosineShardedGallery(ShardedGallery):
         return self._merge_local_topk(local, q.n, k, to_host=True)
 
 
-class MeasureShardedGallery(ShardedGallery):
+class MeasureShardedGallery(_OnePassRoute, ShardedGallery):
     """The shard under euclidean / l1 / l2 / l1_norm / l2_norm / jaccard: the rows stay resident unnormalised in the
     measure's input dtype (``shard``: a Tensor) and K18's launches (csrc/pairwise_rank.hip) do the arithmetic.  The
     methods have the cosine family's signatures and return types; their ``mode`` / ``events`` / ``chunks`` are unused,
@@ -802,9 +934,7 @@ class MeasureShardedGallery(ShardedGallery):
     def _init_shard(self, local_embs, device, filter, band_cap, **_):
         from .linas.evaluation import measure_spec
         measure_spec(self.measure, 1)  # ValueError on an unknown measure
-        self._pw_filter = filter
-        self._pw_band_cap = band_cap
-        self._pw_stats = None
+        self._pw_init(filter, band_cap)
         self._pw_device = device
         self.shard = self._pw_rows(local_embs)  # resident, unnormalised, in the measure's input dtype
         self.device = self.shard.device
@@ -814,10 +944,6 @@ class MeasureShardedGallery(ShardedGallery):
         metric, _, _, sc_dt = self._pw_spec()
         self._pw_family = "l2" if self.measure in _L2_MEASURES else engine.sad_route_of(metric, sc_dt)
         self._pw_packed = None  # the shard's pack for its family's filters, made by the first call that needs it
-        self._pw_filter_off = False  # latched by a top-k the filter handed back whole, or a count whose band
-        #                              exceeds 1/8 of the pairs: this shard stays on fp64
-        self._pw_band = None  # K21's band list, persistent; _pw_plan grows it
-        self._pw_pairs = 0  # the pairs of the last filtered count
 
     def _pw_spec(self):
         from .linas.evaluation import measure_spec
@@ -880,29 +1006,6 @@ class MeasureShardedGallery(ShardedGallery):
         self._pw_pairs = pairs
         return rpos, cpos
 
-    @property
-    def filter_stats(self):
-        """The counters of the last pass's filtered count over this shard -- {decided, band, rescored, overflow,
-        fallback}, fallback = the band list overflowed and the canonical count gave the words -- or None when that
-        pass did not try the filter.  Read from the device: this synchronises."""
-        if self._pw_stats is None:
-            return None
-        st = engine._l2_count_stats(self._pw_stats.cpu().numpy())
-        return dict(st, fallback=st["overflow"] == 1)
-
-    def _pw_plan(self):
-        """After a pass that ended on the host anyway: grow this shard's band list to the reported need, or latch
-        the fp64 route when the band exceeds 1/8 of the pairs (``engine.l2_band_plan``).  Shard-local: it changes the
-        route of later passes, never their words, so the ranks need not agree on it."""
-        st = self.filter_stats
-        if st is None:
-            return
-        cap = engine.l2_band_plan(self._pw_pairs, st["band"], st["overflow"], self._pw_band.numel())
-        if cap is None:
-            self._pw_filter_off = True
-        elif cap > self._pw_band.numel():
-            self._pw_band = torch.empty(cap, dtype=torch.int64, device=self.device)
-
     def _pw_ranks(self, off, sc, pos, n_m: int) -> torch.Tensor:
         return engine.pairwise_list_ranks(off, sc, pos, n_m)
 
@@ -926,68 +1029,6 @@ class MeasureShardedGallery(ShardedGallery):
                                             filter=self._pw_family if forced else None)
         self._pw_filter_off = st is not None and st["fallback"]
         return idx, err
-
-    # ---- coordination (every communicator) ----
-    def _pw_csr(self, lists, n_other: Optional[int], what: str):
-        """(off, idx, items, end) of GT lists with GLOBAL ids, end = the largest id + 1 (a host int: _pw_pass checks
-        it where the other side's size is known).  An id outside [0, n_other) has no owner: ValueError."""
-        off = np.zeros(len(lists) + 1, np.int64)
-        np.cumsum(np.fromiter((len(l) for l in lists), np.int64, count=len(lists)), out=off[1:])
-        items = int(off[-1])
-        ids = np.fromiter((g for l in lists for g in l), np.int64, count=items)  # int64: no wrap before the check
-        end = int(ids.max()) + 1 if items else 0
-        if items and (ids.min() < 0 or end > (1 << 31 if n_other is None else n_other)):
-            raise ValueError(f"ShardedGallery: a {what} id outside [0, {'2^31' if n_other is None else n_other})")
-        idx = ids.astype(np.int32) if items else np.zeros(1, np.int32)
-        return torch.from_numpy(off).to(self.device), torch.from_numpy(idx).to(self.device), items, end
-
-    def _pw_pass(self, q, n_q: int, row, col):
-        """One evaluation of the gathered captions q against every shard under the measure, no host
-        synchronisation.  row: _pw_csr of every caption's GT videos (global ids, the same on every rank) or
-        None; col: _pw_csr of this shard's videos' GT captions (gathered order) or None.  Returns
-        (t2v ranks | None, t2v 0-based positions int32 [items] | None -- both global, equal on every rank; v2t ranks
-        | None, v2t positions | None -- this shard's videos; v2t recall sums int64 [4] of all shards | None)."""
-        # an item outside the other side would get the zero word, a legitimate score: refuse it (host ints, no sync)
-        if row is not None and row[3] > self.n_global:
-            raise ValueError(f"ShardedGallery: a GT video id outside [0, {self.n_global})")
-        if col is not None and col[3] > n_q:
-            raise ValueError(f"ShardedGallery: a GT caption id outside [0, {n_q})")
-        solo = _solo(self.comm)
-        row_side = col_side = None
-        if row is not None:
-            off, idx, items = row[:3]
-            # each item is scored where its video lives; the other shards hold the zero word, so the SUM of the
-            # scores' integer words is the owner's word on every rank (NaN, +-inf and -0.0 as they are)
-            row_sc = self._pw_items(q, (off, idx), items, False, self.offset)
-            if not solo and items:
-                self.comm.all_reduce(row_sc.view(torch.int64), "sum")
-            # the NaN items' n_global - ... comes from ONE rank (the count entry applies it on an empty shard too)
-            row_side = (off, row_sc, self.n_global if self.rank == 0 else 0)
-        if col is not None:
-            coff, cidx, citems = col[:3]
-            # a shard video's GT captions are all here after the gather: scores and positions are rank-local
-            col_side = (coff, self._pw_items(q, (coff, cidx), citems, True, 0), n_q)
-        rpos, cpos = self._pw_count(q, row_side, col_side)
-        v2t = self._pw_ranks(col_side[0], col_side[1], cpos, n_q) if col is not None else None
-        rec = recall_counts_device(v2t) if col is not None else torch.zeros(4, dtype=torch.int64, device=self.device)
-        parts = ([rpos.to(torch.int64)] if row is not None else []) + [rec.to(torch.int64)]
-        # ONE all-reduce(SUM): the t2v positions and the v2t R@K sums
-        both = reduce_counts(torch.cat(parts), self.comm)
-        t2v = t2v_pos = None
-        if row is not None:
-            t2v_pos = both[:-4].to(torch.int32)
-            t2v = self._pw_ranks(row_side[0], row_side[1], t2v_pos, self.n_global)
-        return t2v, t2v_pos, v2t, cpos, (both[-4:] if col is not None else None)
-
-    def _pw_evaluate_gathered(self, q, n_q: int, t2v_gts, v2t_gts):
-        """(t2v ranks, t2v positions, v2t ranks of ALL videos, this shard's v2t positions) on the host from one
-        _pw_pass."""
-        row = self._pw_csr(t2v_gts, self.n_global, "GT video") if t2v_gts is not None else None
-        col = self._pw_csr(self.local_v2t_lists(v2t_gts), n_q, "GT caption") if v2t_gts is not None else None
-        t2v, t2v_pos, v2t, v2t_pos, _ = self._pw_pass(q, n_q, row, col)
-        t2v, v2t, t2v_pos, v2t_pos = self._ranks_to_host(t2v, v2t, t2v_pos, v2t_pos)
-        self._pw_plan()  # (after the result copies: the stream has drained)
-        return t2v, t2v_pos, v2t, v2t_pos
 
     # ---- GT lists: global ids ----
     def local_gt_csr(self, gts_global: Sequence[Sequence[int]]):
@@ -1028,7 +1069,7 @@ class MeasureShardedGallery(ShardedGallery):
         (``_pw_rows(q_all)``) when the caller holds them.  Returns (t2v ranks int64 [n_q] | None -- global, equal on
         every rank; v2t ranks int64 [n] | None -- this shard's videos; v2t recall sums int64 [4] | None -- all
         shards; an overflow flag bool [] that is never set)."""
-        t2v, _, v2t, _, rec = self._pw_pass(self._pw_rows(q_all) if q is None else q, n_q, row_csr, col_csr)
+        t2v, _, v2t, _, rec, _ = self._pw_pass(self._pw_rows(q_all) if q is None else q, n_q, row_csr, col_csr)
         return t2v, v2t, rec, torch.zeros((), dtype=torch.bool, device=self.device)
 
     def evaluate(self, q_local: torch.Tensor, t2v_gts=None, v2t_gts=None, mode: int = _lib.SIM_F16):
@@ -1046,15 +1087,7 @@ class MeasureShardedGallery(ShardedGallery):
         them (gathered caption order).  Ranks and both mAPs (t2v: each caption's FIRST GT; v2t: every GT caption
         of a video) come from the positions of ONE pass, multi-GT lists included."""
         q_all = all_gather_var(q_local, self.comm)
-        n_q = q_all.shape[0]
-        v2t_lists, t2v_lists = self._perf_lists(n_q, v2t_gt, t2v_gt)
-        t2v, t2v_pos, v2t, v2t_pos = self._pw_evaluate_gathered(self._pw_rows(q_all), n_q, t2v_lists, v2t_lists)
-        # the first GT's position is among every item's
-        firsts = np.cumsum([0] + [len(l) for l in t2v_lists])[:-1]
-        t2v_map = float(np.mean([1.0 / (t2v_pos[f] + 1) if l else 0.0 for f, l in zip(firsts, t2v_lists)]))
-        offs = np.cumsum([0] + [len(l) for l in self.local_v2t_lists(v2t_lists)])
-        aps = [ap_from_positions(v2t_pos[offs[j]:offs[j + 1]] + 1) for j in range(self.n)]
-        return self._perf(t2v, v2t, t2v_map, aps)
+        return self._pw_cal_perf(self._pw_rows(q_all), q_all.shape[0], v2t_gt, t2v_gt)
 
     def topk(self, q_local: torch.Tensor, k: int, mode: int = _lib.SIM_F16):
         """Global exact top-k of all gathered queries (row counts may differ: a single caption may sit on one
@@ -1074,6 +1107,141 @@ class MeasureShardedGallery(ShardedGallery):
         return ids.cpu().numpy(), (-sc).cpu().numpy()
 
 
-def _family(measure) -> type:
-    """The ONE dispatch on the measure: the class that ``ShardedGallery(..., measure=)`` builds."""
-    return CosineShardedGallery if measure == 'cosine' else MeasureShardedGallery
+class CosineFilterShardedGallery(_OnePassRoute, CosineShardedGallery):
+    """The cosine family under ``filter="cosine"`` (K27): cal_perf, evaluate, evaluate_device, rank_queries and
+    rank_queries_device take ONE pass per shard, the measure family's plan (``_pw_pass``) on K26's count -- the item
+    words scored where the video lives and merged by an int64 SUM, one ``engine.cos_count(resolved=True)`` over (all
+    captions) x (this shard): the same words whatever the band list does, an overflow resolved on the device, so
+    nothing synchronises, no flag rides a collective and the flags the ``*_device`` methods return are never set --,
+    one all-reduce(SUM) of the t2v positions and the v2t R@K sums.  It needs eps = 0 and the fp16 plane (ValueError),
+    and ``mode=SIM_F16`` on those methods (ValueError); ``local_gt_csr`` / ``local_v2t_csr`` return global-id lists.
+    ``band_cap``: the slots of the shard's first band list (default ``engine.l2_band_cap`` of the first pass); the
+    methods that end on the host grow it to the need the counters report (``filter_stats``).  There is no latch back to
+    the cosine family's route: that route issues other collectives (an encoded MAX, other lengths, redo loops), and a
+    shard that left the one pass on its own counters would leave the other ranks waiting in theirs -- a shard whose
+    band is large keeps the pass, with a list that holds the band.  topk is the cosine family's.  Built with ``filter``
+    None / False it is the cosine family."""
+
+    def _init_shard(self, local_embs, device, with_lo, eps, with_f16, cap, filter=None, band_cap=None, **_):
+        self._pw_init(filter, band_cap)
+        if self._pw_forced():  # the pass is fp16 on what cmve_cos_count accepts
+            if eps != 0:
+                raise ValueError(f'ShardedGallery: filter="cosine" needs eps = 0, not {eps!r}')
+            if not with_f16:
+                raise ValueError('ShardedGallery: filter="cosine" needs the fp16 plane (with_f16=True)')
+        super()._init_shard(local_embs, device, with_lo=with_lo, eps=eps, with_f16=with_f16, cap=cap)
+
+    # ---- shard-local arithmetic (HIP kernels) ----
+    def _pw_rows(self, x):
+        """The gathered captions packed as ``cmve_cos_count`` takes them."""
+        return self._pack(x, _lib.SIM_F16)
+
+    def _pw_items(self, q, csr, n_items: int, col_dir: bool, idx_base: int) -> torch.Tensor:
+        """fp64 [n_items]: cos64 of the listed items this shard owns, the all-zero word elsewhere."""
+        off, idx = csr
+        return engine.cos_item_scores(q, self.shard, off, idx, n_items, col_dir, idx_base=idx_base)
+
+    def _pw_count(self, q, row, col):
+        """ONE ``cmve_cos_count_resolved`` over (all captions) x (this shard): (row positions | None, column
+        positions | None), int32; its counters stay on the device as this pass's ``filter_stats``."""
+        pairs = int(q.n) * self.n
+        if self._pw_band is None:
+            cap = engine.l2_band_cap(pairs) if self._pw_band_cap is None else int(self._pw_band_cap)
+            self._pw_band = torch.empty(cap, dtype=torch.int64, device=self.device)
+        rpos, cpos, self._pw_stats = engine.cos_count(q, self.shard, row, col, band=self._pw_band, resolved=True)
+        self._pw_pairs = pairs
+        return rpos, cpos
+
+    def _pw_ranks(self, off, sc, pos, n_m: int) -> torch.Tensor:
+        return engine.pairwise_list_ranks(off, sc, pos, n_m)
+
+    def _pw_first_positions(self, t2v_pos, firsts, row_words):
+        """As the cosine family ranks a caption's first GT ALONE: a first item whose word is NaN takes the last
+        place, n_global, wherever the list's other NaN items put it among them."""
+        first = t2v_pos[firsts] + 1
+        nan = torch.isnan(row_words[torch.from_numpy(firsts).to(row_words.device)])
+        first[nan.cpu().numpy()] = self.n_global
+        return first
+
+    def _pw_plan(self):
+        """After a pass that ended on the host anyway: grow this shard's band list to the reported need.  Shard-local,
+        and it never changes the route (class docstring): the collectives of every later pass are the same on every
+        rank."""
+        st = self.filter_stats
+        if st is not None and st["overflow"] and st["band"] > self._pw_band.numel():
+            self._pw_band = torch.empty(st["band"], dtype=torch.int64, device=self.device)
+
+    # ---- the route of a call ----
+    def _pw_forced(self) -> bool:
+        return isinstance(self._pw_filter, str) and self._pw_filter == "cosine"
+
+    def _pw_due(self, mode: int) -> bool:
+        """This call takes the one pass: the constructor forced it -- on every rank alike, so the ranks agree.  A call
+        on the cosine family's own route leaves no counters."""
+        if not self._pw_forced():
+            self._pw_stats = None
+            return False
+        if mode != _lib.SIM_F16:
+            raise ValueError('ShardedGallery: filter="cosine" is an fp16 pass: mode must be SIM_F16')
+        return True
+
+    # ---- GT lists ----
+    def local_gt_csr(self, gts_global: Sequence[Sequence[int]]):
+        """t2v: (off, idx, items, end) of every caption's GT videos with GLOBAL ids -- the same on every rank (the
+        items are scored where they live)."""
+        if not self._pw_forced():
+            return super().local_gt_csr(gts_global)
+        return self._pw_csr(gts_global, self.n_global, "GT video")
+
+    def local_v2t_csr(self, v2t_gts_global: Sequence[Sequence[int]]):
+        """v2t: (off, idx, items, end) of the GT captions (gathered order) of this shard's videos."""
+        if not self._pw_forced():
+            return super().local_v2t_csr(v2t_gts_global)
+        return self._pw_csr(self.local_v2t_lists(v2t_gts_global), None, "GT caption")
+
+    # ---- the methods: one pass under the filter, the cosine family's otherwise ----
+    def rank_queries(self, q_local: torch.Tensor, gt_csr, n_q: int, mode: int = _lib.SIM_F16, events=None,
+                     return_host: bool = True, chunks: int = 1):
+        if not self._pw_due(mode):  # (a refusal comes before any collective)
+            return super().rank_queries(q_local, gt_csr, n_q, mode, events, return_host, chunks)
+        ranks, _ = self.rank_queries_device(self.all_gather_rows(q_local), gt_csr, n_q, mode)
+        if not return_host:
+            return ranks
+        ranks = ranks.cpu().numpy().astype(np.int64)
+        self._pw_plan()
+        return ranks
+
+    def rank_queries_device(self, q_all: torch.Tensor, gt_csr, n_q: int, mode: int = _lib.SIM_F16, events=None,
+                            chunks: int = 1):
+        if not self._pw_due(mode):
+            return super().rank_queries_device(q_all, gt_csr, n_q, mode, events, chunks)
+        t2v = self._pw_pass(self._pw_rows(q_all), n_q, gt_csr, None)[0]
+        return t2v, torch.zeros((), dtype=torch.bool, device=self.device)
+
+    def evaluate_device(self, q_all: torch.Tensor, row_csr, col_csr, n_q: int, mode: int = _lib.SIM_F16,
+                        events=None, q=None):
+        if not self._pw_due(mode):
+            return super().evaluate_device(q_all, row_csr, col_csr, n_q, mode, events, q)
+        t2v, _, v2t, _, rec, _ = self._pw_pass(self._pw_rows(q_all) if q is None else q, n_q, row_csr, col_csr)
+        return t2v, v2t, rec, torch.zeros((), dtype=torch.bool, device=self.device)
+
+    def evaluate(self, q_local: torch.Tensor, t2v_gts=None, v2t_gts=None, mode: int = _lib.SIM_F16):
+        if not self._pw_due(mode):
+            return super().evaluate(q_local, t2v_gts, v2t_gts, mode)
+        q_all = all_gather_var(q_local, self.comm)
+        t2v, _, v2t, _ = self._pw_evaluate_gathered(self._pw_rows(q_all), q_all.shape[0], t2v_gts, v2t_gts)
+        return t2v, v2t
+
+    def cal_perf(self, q_local: torch.Tensor, v2t_gt, t2v_gt, mode: int = _lib.SIM_F16):
+        if not self._pw_due(mode):
+            return super().cal_perf(q_local, v2t_gt, t2v_gt, mode)
+        q_all = all_gather_var(q_local, self.comm)
+        return self._pw_cal_perf(self._pw_rows(q_all), q_all.shape[0], v2t_gt, t2v_gt)
+
+
+def _family(measure, filter=None) -> type:
+    """The ONE dispatch on the measure (and, under cosine, on ``filter="cosine"``): the class that
+    ``ShardedGallery(..., measure=, filter=)`` builds."""
+    if measure != 'cosine':
+        return MeasureShardedGallery
+    return CosineFilterShardedGallery if isinstance(filter, str) and filter == "cosine" else CosineShardedGallery

@@ -1943,11 +1943,14 @@ def _cos_sets(a, b, name: str):
 
 
 def cos_item_scores(a: RowSet, b: RowSet, off: torch.Tensor, idx: torch.Tensor, n_items: int, col_dir: bool = False,
-                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                    out: Optional[torch.Tensor] = None, idx_base: Optional[int] = None) -> torch.Tensor:
     """fp64 [n_items] on the device: cos64 of every listed item of one CSR side (``cmve_cos_item_scores``) -- the word
     ``gt_thresholds`` and the rank fix-up compute.  (off, idx): ``csr`` of the lists of a's rows naming b's rows
     (col_dir: of b's rows naming a's rows).  An index outside the other set scores NaN.  No host copy, no
-    synchronisation."""
+    synchronisation.  ``idx_base`` (an int, K27: ``cmve_cos_item_scores_sharded``, for a gallery sharded by rows): idx
+    holds GLOBAL rows of the other side, of which the operand given here is [idx_base, idx_base + n); an item outside
+    that range gets the all-zero word, not NaN: the int64 SUM over the shards of ``out.view(torch.int64)`` is every
+    item's word, bit for bit."""
     _cos_sets(a, b, "cos_item_scores")
     n_items = int(n_items)
     if idx.numel() < n_items or idx.dtype != torch.int32 or off.dtype != torch.int64:
@@ -1956,8 +1959,12 @@ def cos_item_scores(a: RowSet, b: RowSet, off: torch.Tensor, idx: torch.Tensor, 
         out = torch.empty(max(n_items, 1), dtype=torch.float64, device=a.device)
     elif out.dtype != torch.float64 or not out.is_contiguous() or out.numel() < n_items:
         raise TypeError("cos_item_scores: out is a contiguous float64 tensor of at least n_items words")
-    check(lib.cmve_cos_item_scores(handle(a.device), C.byref(a.desc), C.byref(b.desc), _ptr(off), _ptr(idx),
-                                   off.numel() - 1, n_items, 1 if col_dir else 0, _ptr(out)), "cmve_cos_item_scores")
+    head = (handle(a.device), C.byref(a.desc), C.byref(b.desc), _ptr(off), _ptr(idx), off.numel() - 1, n_items,
+            1 if col_dir else 0)
+    if idx_base is None:
+        check(lib.cmve_cos_item_scores(*head, _ptr(out)), "cmve_cos_item_scores")
+    else:
+        check(lib.cmve_cos_item_scores_sharded(*head, int(idx_base), _ptr(out)), "cmve_cos_item_scores_sharded")
     return out[:n_items]
 
 
@@ -1971,13 +1978,16 @@ def cos_count_workspace(a: RowSet, b: RowSet, band_cap: int) -> int:
 
 def cos_count(a: RowSet, b: RowSet, row=None, col=None, band: Optional[torch.Tensor] = None,
               stats: Optional[torch.Tensor] = None, row_pos: Optional[torch.Tensor] = None,
-              col_pos: Optional[torch.Tensor] = None):
+              col_pos: Optional[torch.Tensor] = None, resolved: bool = False):
     """(row_pos, col_pos, stats): ``cmve_cos_count`` on device tensors, no host copy, no synchronisation.
     row = (off [na + 1], item words fp64 [items], n): a non-NaN item's word is #{ j : cos64(i, j) > word }, a NaN item's
     n - (NaN items of its list) + (its place among them); col: the mirror; a direction left None gives None.
     ``band``: a caller-owned contiguous int64 device tensor, one slot per element (None: ``l2_band_cap(na * nb)``
     slots).  ``stats``: int64 [4] on the device, {decided, band found, band re-scored, overflow}: when the overflow
-    word is 1 the positions are NOT valid and ``stats[1]`` is the capacity a redo needs (``cos_gt_eval`` does that)."""
+    word is 1 the positions are NOT valid and ``stats[1]`` is the capacity a redo needs (``cos_gt_eval`` does that).
+    ``resolved`` (K27: ``cmve_cos_count_resolved``): an overflow is resolved on the device -- the positions are those
+    of a list large enough whatever the list did; the overflow word and ``stats[1]`` still say what a later call's
+    list should hold."""
     _cos_sets(a, b, "cos_count")
     dev = a.device
     sides = []
@@ -2001,8 +2011,9 @@ def cos_count(a: RowSet, b: RowSet, row=None, col=None, band: Optional[torch.Ten
         raise TypeError("cos_count: band is a contiguous int64 tensor on the sets' device")
     if stats is None:
         stats = torch.empty(4, dtype=torch.int64, device=dev)
-    check(lib.cmve_cos_count(handle(dev), C.byref(a.desc), C.byref(b.desc),
-                             *_count_tail(sides[0], sides[1], band, _nbytes(band), stats)), "cmve_cos_count")
+    entry = "cmve_cos_count_resolved" if resolved else "cmve_cos_count"
+    check(getattr(lib, entry)(handle(dev), C.byref(a.desc), C.byref(b.desc),
+                              *_count_tail(sides[0], sides[1], band, _nbytes(band), stats)), entry)
     (_, _, ritems, _, rpos), (_, _, citems, _, cpos) = sides
     return (None if rpos is None else rpos[:ritems]), (None if cpos is None else cpos[:citems]), stats
 

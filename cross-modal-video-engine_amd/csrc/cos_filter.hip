@@ -12,6 +12,9 @@
 //                       16 rounds at a time into LDS; a round past the tile's longest row (column) list compares
 //                       against the other side's items alone
 //   cosf_fixup_kernel   a wave per band pair: cos64, then every item of row i's and column j's list
+// K27, for a gallery sharded by rows (the same reference lines, one shard's pairs per call): cosf_item_kernel scores an
+// item where its row lives (cmve_cos_item_scores_sharded), and cmve_cos_count_resolved resolves a band list that
+// overflowed on the device -- cosf_gated_zero_kernel, then cosf_fixup_kernel's body over every pair.
 // The lists, the band list, the counters, the NaN items and the host body are filter_count.h's.
 #include "filter_count.h"
 
@@ -272,7 +275,11 @@ __global__ __launch_bounds__(256, 2) void cosf_main_kernel(CosfArgs a) {
 }
 
 // ---- the band pairs on the canonical chain: a wave per pair -------------------------------------------------------------
-template <typename TA, typename TB>
+// DENSE = false: the pairs of the band list (nothing when it overflowed: stats[1] > cap).  DENSE = true (K27, the
+// overflow resolved on the device): nothing unless stats[3] is set, then EVERY pair p -> (p / nb, p % nb) of the
+// cap = na * nb pairs through the same body -- the words of a list large enough, by construction; the re-score
+// counter stays as the overflow left it.
+template <bool DENSE, typename TA, typename TB>
 __global__ __launch_bounds__(256) void cosf_fixup_kernel(const TA* __restrict__ A, int64_t lda,
                                                          const double* __restrict__ ainv, const TB* __restrict__ B,
                                                          int64_t ldb, const double* __restrict__ binv, int64_t d,
@@ -280,34 +287,68 @@ __global__ __launch_bounds__(256) void cosf_fixup_kernel(const TA* __restrict__ 
                                                          const double* __restrict__ row_sc, int32_t* __restrict__ row_pos,
                                                          const int64_t* __restrict__ col_off,
                                                          const double* __restrict__ col_sc, int32_t* __restrict__ col_pos,
-                                                         const int2* __restrict__ band, int64_t cap,
+                                                         const int2* __restrict__ band, int64_t cap, int64_t nb,
                                                          l2f_u64* __restrict__ stats) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int64_t n = (int64_t)gld(stats + 1);
-  if (n > cap) return;  // the list overflowed: the caller redoes the call with the reported need
+  int64_t n;
+  if constexpr (DENSE) {
+    if (gld(stats + 3) == 0ull) return;  // the list held the band: the words stand
+    n = cap;
+  } else {
+    n = (int64_t)gld(stats + 1);
+    if (n > cap) return;  // the list overflowed: the caller redoes the call with the reported need, or resolves it
+  }
   const int64_t step = (int64_t)gridDim.x * 4;
   int64_t done = 0;
   for (int64_t p = (int64_t)blockIdx.x * 4 + w; p < n; p += step, ++done) {  // wave-uniform
-    const int2 ij = band[p];
-    const double s = wave_cos64(A + (int64_t)ij.x * lda, B + (int64_t)ij.y * ldb, gld(ainv + ij.x), gld(binv + ij.y), d,
-                                lane);
+    int64_t i, j;
+    if constexpr (DENSE) {
+      i = p / nb;
+      j = p - i * nb;
+    } else {
+      const int2 ij = band[p];
+      i = ij.x;
+      j = ij.y;
+    }
+    const double s = wave_cos64(A + i * lda, B + j * ldb, gld(ainv + i), gld(binv + j), d, lane);
     if (row_pos) {
-      const int64_t m = row_off[ij.x + 1];
-      for (int64_t q = row_off[ij.x] + lane; q < m; q += 64)
+      const int64_t m = row_off[i + 1];
+      for (int64_t q = row_off[i] + lane; q < m; q += 64)
         if (s > row_sc[q]) gadd(row_pos + q, (int32_t)1);
     }
     if (col_pos) {
-      const int64_t m = col_off[ij.y + 1];
-      for (int64_t q = col_off[ij.y] + lane; q < m; q += 64)
+      const int64_t m = col_off[j + 1];
+      for (int64_t q = col_off[j] + lane; q < m; q += 64)
         if (s > col_sc[q]) gadd(col_pos + q, (int32_t)1);
     }
   }
-  if (lane == 0 && done) gadd(stats + 2, (l2f_u64)done);
+  if (!DENSE && lane == 0 && done) gadd(stats + 2, (l2f_u64)done);
+}
+
+// K27: the band list overflowed -> drop the partial counts before the dense pass.  A NaN item's word is
+// l2f_nan_launch's and no pair ever counts into it (x > NaN is false): it is spared.
+__global__ __launch_bounds__(256) void cosf_gated_zero_kernel(const double* __restrict__ row_sc,
+                                                              int32_t* __restrict__ row_pos, int64_t row_items,
+                                                              const double* __restrict__ col_sc,
+                                                              int32_t* __restrict__ col_pos, int64_t col_items,
+                                                              const l2f_u64* __restrict__ gate) {
+  if (gld(gate) == 0ull) return;
+  const int64_t step = (int64_t)gridDim.x * 256;
+  for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < row_items; p += step) {
+    const double t = row_sc[p];
+    if (t == t) row_pos[p] = 0;
+  }
+  for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < col_items; p += step) {
+    const double t = col_sc[p];
+    if (t == t) col_pos[p] = 0;
+  }
 }
 
 // ---- the items' words: a wave per item ----------------------------------------------------------------------------------
 // item p of list `owner` names row idx[p] of the other side (col_dir: the lists belong to B rows and name A rows); an
-// index outside it scores NaN and reads nothing
+// index outside it scores NaN and reads nothing.  idx_base >= 0 (K27, a gallery sharded by rows): idx holds GLOBAL
+// rows of the other side, of which this call's operand is [idx_base, idx_base + n_other); an item outside it is
+// another shard's and gets the all-zero word, so that the int64 SUM of the shards' words is the owner's.
 template <typename TA, typename TB>
 __global__ __launch_bounds__(256) void cosf_item_kernel(const TA* __restrict__ A, int64_t lda,
                                                         const double* __restrict__ ainv, int64_t na,
@@ -315,7 +356,7 @@ __global__ __launch_bounds__(256) void cosf_item_kernel(const TA* __restrict__ A
                                                         const double* __restrict__ binv, int64_t nb, int64_t d,
                                                         const int64_t* __restrict__ off, const int32_t* __restrict__ idx,
                                                         int64_t n_lists, int64_t n_items, int col_dir,
-                                                        double* __restrict__ out) {
+                                                        int64_t idx_base, double* __restrict__ out) {
   const int lane = threadIdx.x & 63;
   const int64_t p = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (p >= n_items) return;  // wave-uniform
@@ -324,9 +365,10 @@ __global__ __launch_bounds__(256) void cosf_item_kernel(const TA* __restrict__ A
     const int64_t mid = (lo + hi) >> 1;
     if (off[mid + 1] > p) hi = mid; else lo = mid + 1;
   }
-  const int64_t owner = lo, other = (int64_t)idx[p];
+  const bool sharded = idx_base >= 0;
+  const int64_t owner = lo, other = (int64_t)idx[p] - (sharded ? idx_base : 0);
   const int64_t i = col_dir ? other : owner, j = col_dir ? owner : other;
-  double s = (double)NAN;
+  double s = sharded ? 0.0 : (double)NAN;
   if (owner < n_lists && i >= 0 && i < na && j >= 0 && j < nb)
     s = wave_cos64(A + i * lda, B + j * ldb, gld(ainv + i), gld(binv + j), d, lane);
   if (lane == 0) out[p] = s;
@@ -337,24 +379,40 @@ __global__ __launch_bounds__(256) void cosf_item_kernel(const TA* __restrict__ A
 
 using namespace cmve;
 
-extern "C" int cmve_cos_item_scores(cmve_handle_t h, const cmve_rows_t* a, const cmve_rows_t* b, const int64_t* off,
-                                    const int32_t* idx, int64_t n_lists, int64_t n_items, int32_t col_dir,
-                                    double* out) {
-  CMVE_REQUIRE(h && a && b && off, "cmve_cos_item_scores: NULL argument");
-  if (int rc = l2f_check_sets("cmve_cos_item_scores", a, b)) return rc;
-  CMVE_REQUIRE(n_items >= 0 && n_items < (1ll << 31) * 4, "cmve_cos_item_scores: bad item count (%lld)",
-               (long long)n_items);
-  CMVE_REQUIRE(col_dir == 0 || col_dir == 1, "cmve_cos_item_scores: col_dir must be 0 or 1");
-  CMVE_REQUIRE(n_lists == (col_dir ? b->n : a->n), "cmve_cos_item_scores: %lld lists for the %lld rows that own them",
+// cmve_cos_item_scores (idx_base < 0: an index outside the other set scores NaN) and cmve_cos_item_scores_sharded
+// (idx_base >= 0: global indices, the zero word outside this call's operand): one argument list, one launch
+static int cos_item_scores_run(const char* name, cmve_handle_t h, const cmve_rows_t* a, const cmve_rows_t* b,
+                               const int64_t* off, const int32_t* idx, int64_t n_lists, int64_t n_items,
+                               int32_t col_dir, int64_t idx_base, double* out) {
+  CMVE_REQUIRE(h && a && b && off, "%s: NULL argument", name);
+  if (int rc = l2f_check_sets(name, a, b)) return rc;
+  CMVE_REQUIRE(n_items >= 0 && n_items < (1ll << 31) * 4, "%s: bad item count (%lld)", name, (long long)n_items);
+  CMVE_REQUIRE(col_dir == 0 || col_dir == 1, "%s: col_dir must be 0 or 1", name);
+  CMVE_REQUIRE(n_lists == (col_dir ? b->n : a->n), "%s: %lld lists for the %lld rows that own them", name,
                (long long)n_lists, (long long)(col_dir ? b->n : a->n));
-  CMVE_REQUIRE(n_items == 0 || (idx && out), "cmve_cos_item_scores: NULL argument");
+  CMVE_REQUIRE(n_items == 0 || (idx && out), "%s: NULL argument", name);
   if (n_items == 0) return CMVE_OK;
   PWR_TYPES(a->raw_dtype, b->raw_dtype, TA, TB, {
     hipLaunchKernelGGL((cosf_item_kernel<TA, TB>), dim3((unsigned)((n_items + 3) / 4)), dim3(256), 0, h->stream,
                        (const TA*)a->raw, a->raw_ld, a->inv_norm, a->n, (const TB*)b->raw, b->raw_ld, b->inv_norm,
-                       b->n, a->d, off, idx, n_lists, n_items, (int)col_dir, out);
+                       b->n, a->d, off, idx, n_lists, n_items, (int)col_dir, idx_base, out);
   })
-  return check_launch("cos_item_scores");
+  return check_launch(name + 5);  // (without "cmve_")
+}
+
+extern "C" int cmve_cos_item_scores(cmve_handle_t h, const cmve_rows_t* a, const cmve_rows_t* b, const int64_t* off,
+                                    const int32_t* idx, int64_t n_lists, int64_t n_items, int32_t col_dir,
+                                    double* out) {
+  return cos_item_scores_run("cmve_cos_item_scores", h, a, b, off, idx, n_lists, n_items, col_dir, -1, out);
+}
+
+extern "C" int cmve_cos_item_scores_sharded(cmve_handle_t h, const cmve_rows_t* a, const cmve_rows_t* b,
+                                            const int64_t* off, const int32_t* idx, int64_t n_lists, int64_t n_items,
+                                            int32_t col_dir, int64_t idx_base, double* out) {
+  CMVE_REQUIRE(idx_base >= 0, "cmve_cos_item_scores_sharded: idx_base must not be negative (%lld)",
+               (long long)idx_base);
+  return cos_item_scores_run("cmve_cos_item_scores_sharded", h, a, b, off, idx, n_lists, n_items, col_dir, idx_base,
+                             out);
 }
 
 extern "C" int cmve_cos_count_workspace(const cmve_rows_t* a, const cmve_rows_t* b, int64_t band_cap, int64_t* bytes) {
@@ -368,17 +426,23 @@ extern "C" int cmve_cos_count_workspace(const cmve_rows_t* a, const cmve_rows_t*
   return CMVE_OK;
 }
 
-extern "C" int cmve_cos_count(cmve_handle_t h, const cmve_rows_t* a, const cmve_rows_t* b, const int64_t* row_off,
-                              const double* row_sc, int64_t row_items, int64_t row_n, int32_t* row_pos,
-                              const int64_t* col_off, const double* col_sc, int64_t col_items, int64_t col_n,
-                              int32_t* col_pos, void* ws, int64_t ws_bytes, int64_t* stats) {
-  const char* name = "cmve_cos_count";
+// cmve_cos_count and cmve_cos_count_resolved: the sets' own checks, the main launch and K26's fix-up launch of
+// flt_count_run; `resolved` adds K27's two launches gated on the overflow word
+static int cos_count_run(const char* name, bool resolved, cmve_handle_t h, const cmve_rows_t* a, const cmve_rows_t* b,
+                         const FltLists& lists, void* ws, int64_t ws_bytes, int64_t* stats) {
   CMVE_REQUIRE(h && a && b && stats, "%s: NULL argument", name);
   const FltRows rows{a->raw, a->raw_dtype, a->raw_ld, a->n, b->raw, b->raw_dtype, b->raw_ld, b->n, a->d};
+  // the canonical chain over a pair source: the band list, or (DENSE) every pair once the overflow word is set
+#define COSF_FIXUP(DENSE, blocks, l, band_, cap_)                                                                     \
+  PWR_TYPES(a->raw_dtype, b->raw_dtype, TA, TB, {                                                                     \
+    hipLaunchKernelGGL((cosf_fixup_kernel<DENSE, TA, TB>), dim3((unsigned)(blocks)), dim3(256), 0, st,                \
+                       (const TA*)a->raw, a->raw_ld, a->inv_norm, (const TB*)b->raw, b->raw_ld, b->inv_norm, a->d,    \
+                       (l).row_off, (l).row_sc, (l).row_pos, (l).col_off, (l).col_sc, (l).col_pos, band_, cap_,       \
+                       (int64_t)b->n, bd.stats);                                                                      \
+  })
   return flt_count_run(
-      name, "cos_count", h, CMVE_PW_DOT, rows, 1.0, 0.0,
-      {row_off, row_sc, row_items, row_n, row_pos, col_off, col_sc, col_items, col_n, col_pos}, ws, ws_bytes, stats,
-      false,
+      name, resolved ? "cos_count_resolved" : "cos_count", h, CMVE_PW_DOT, rows, 1.0, 0.0, lists, ws, ws_bytes, stats,
+      resolved,
       [&]() -> int {
         if (int rc = l2f_check_sets(name, a, b)) return rc;
         CMVE_REQUIRE(a->err_max && b->err_max, "%s: a set was packed without its err_max words", name);
@@ -394,11 +458,36 @@ extern "C" int cmve_cos_count(cmve_handle_t h, const cmve_rows_t* a, const cmve_
       },
       [&](hipStream_t st, const FltLists& l, const FltBand& bd) {
         const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(16 * device_cus(), (bd.cap + 3) / 4));
-        PWR_TYPES(a->raw_dtype, b->raw_dtype, TA, TB, {
-          hipLaunchKernelGGL((cosf_fixup_kernel<TA, TB>), dim3((unsigned)blocks), dim3(256), 0, st, (const TA*)a->raw,
-                             a->raw_ld, a->inv_norm, (const TB*)b->raw, b->raw_ld, b->inv_norm, a->d, l.row_off,
-                             l.row_sc, l.row_pos, l.col_off, l.col_sc, l.col_pos, (const int2*)bd.band, bd.cap,
-                             bd.stats);
-        })
+        COSF_FIXUP(false, blocks, l, (const int2*)bd.band, bd.cap)
+      },
+      [&](hipStream_t st, const FltLists& l, const FltBand& bd) {
+        // the list overflowed (decided on the device: both launches do nothing otherwise): the partial counts are
+        // dropped -- not the NaN items' words -- and every pair goes through the fix-up's body
+        const int64_t items = std::max(l.row_items, l.col_items), pairs = a->n * b->n;
+        const int zero_blocks = (int)std::max<int64_t>(1, std::min<int64_t>(8 * device_cus(), (items + 255) / 256));
+        hipLaunchKernelGGL(cosf_gated_zero_kernel, dim3((unsigned)zero_blocks), dim3(256), 0, st, l.row_sc, l.row_pos,
+                           l.row_items, l.col_sc, l.col_pos, l.col_items, bd.stats + 3);
+        const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(16 * device_cus(), (pairs + 3) / 4));
+        COSF_FIXUP(true, blocks, l, (const int2*)nullptr, pairs)
       });
+#undef COSF_FIXUP
+}
+
+extern "C" int cmve_cos_count(cmve_handle_t h, const cmve_rows_t* a, const cmve_rows_t* b, const int64_t* row_off,
+                              const double* row_sc, int64_t row_items, int64_t row_n, int32_t* row_pos,
+                              const int64_t* col_off, const double* col_sc, int64_t col_items, int64_t col_n,
+                              int32_t* col_pos, void* ws, int64_t ws_bytes, int64_t* stats) {
+  return cos_count_run("cmve_cos_count", false, h, a, b,
+                       {row_off, row_sc, row_items, row_n, row_pos, col_off, col_sc, col_items, col_n, col_pos}, ws,
+                       ws_bytes, stats);
+}
+
+extern "C" int cmve_cos_count_resolved(cmve_handle_t h, const cmve_rows_t* a, const cmve_rows_t* b,
+                                       const int64_t* row_off, const double* row_sc, int64_t row_items, int64_t row_n,
+                                       int32_t* row_pos, const int64_t* col_off, const double* col_sc,
+                                       int64_t col_items, int64_t col_n, int32_t* col_pos, void* ws, int64_t ws_bytes,
+                                       int64_t* stats) {
+  return cos_count_run("cmve_cos_count_resolved", true, h, a, b,
+                       {row_off, row_sc, row_items, row_n, row_pos, col_off, col_sc, col_items, col_n, col_pos}, ws,
+                       ws_bytes, stats);
 }

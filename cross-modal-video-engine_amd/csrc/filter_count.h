@@ -5,7 +5,7 @@
 //   flt_check_lists      what every count entry asks of the lists (cmve_pairwise_count included)
 //   flt_count_run        the host body: checks, memsets, NaN items, the filter's main launch, fix-up, resolve
 // A filter supplies its own operands' checks and a main launch (K26, the cosine filter of cos_filter.hip, also its
-// fix-up launch: its canonical word is cos64, not a chain of pairwise_tile.h).  The two SAD filters share one kernel body and one
+// fix-up launch and, K27, its resolve launch: its canonical word is cos64, not a chain of pairwise_tile.h).  The two SAD filters share one kernel body and one
 // epilogue (sad_count.h: the same tile, thread layout and occupancy under a small policy); l2f_main_kernel keeps an
 // epilogue of its own (the same algorithm on another thread layout, at 256 VGPRs): written once as a force-inlined
 // template it cost that kernel 6% (DESIGN s4).
@@ -83,11 +83,14 @@ void pwr_count_gated_launch(hipStream_t st, int32_t metric, const FltRows& r, do
 // main_launch(st, args): the filter's main kernel over args.tiles_a x args.tiles_b blocks.  `resolve`: an
 // overflowing list is resolved on the device.  fixup_launch(st, lists, band): the re-score of the band list on the
 // entry's canonical chain -- l2f_fixup_launch with `metric` for the measures of pairwise_tile.h (the overload below),
-// K26's own under cosine (cos_filter.hip, whose words are cos64's).
-template <typename Own, typename Main, typename Fix>
+// K26's own under cosine (cos_filter.hip, whose words are cos64's).  resolve_launch(st, lists, band): the launches
+// that give an overflowed call its words, gated on band.stats[3] -- l2f_resolve_launch with `metric` for those
+// measures (the overload below), K27's own under cosine.
+template <typename Own, typename Main, typename Fix, typename Res>
 static inline int flt_count_run(const char* name, const char* label, cmve_handle_t h, int32_t metric,
                                 const FltRows& r, double alpha, double beta, FltLists l, void* ws, int64_t ws_bytes,
-                                int64_t* stats, bool resolve, Own own_checks, Main main_launch, Fix fixup_launch) {
+                                int64_t* stats, bool resolve, Own own_checks, Main main_launch, Fix fixup_launch,
+                                Res resolve_launch) {
   CMVE_REQUIRE(alpha != 0.0 && std::isfinite(alpha) && std::isfinite(beta),
                "%s: alpha must be finite and non-zero, beta finite (%g, %g)", name, alpha, beta);
   if (int rc = own_checks()) return rc;
@@ -109,7 +112,7 @@ static inline int flt_count_run(const char* name, const char* label, cmve_handle
   const FltBand band{(int2*)ws, ws_bytes / (int64_t)sizeof(int2), (l2f_u64*)stats};
   main_launch(st, FltArgs{r.na, r.nb, alpha, beta, l, band, (int)tiles_a, (int)tiles_b});
   if (band.cap > 0) fixup_launch(st, l, band);
-  if (resolve) l2f_resolve_launch(st, metric, r, alpha, beta, l, band.stats);
+  if (resolve) resolve_launch(st, l, band);
   return check_launch(label);
 }
 
@@ -120,6 +123,9 @@ static inline int flt_count_run(const char* name, const char* label, cmve_handle
   return flt_count_run(name, label, h, metric, r, alpha, beta, l, ws, ws_bytes, stats, resolve, own_checks, main_launch,
                        [&](hipStream_t st, const FltLists& fl, const FltBand& fb) {
                          l2f_fixup_launch(st, metric, r, alpha, beta, fl, fb);
+                       },
+                       [&](hipStream_t st, const FltLists& fl, const FltBand& fb) {
+                         l2f_resolve_launch(st, metric, r, alpha, beta, fl, fb.stats);
                        });
 }
 

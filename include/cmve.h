@@ -895,6 +895,30 @@ int cmve_cos_count(cmve_handle_t h, const cmve_rows_t* a, const cmve_rows_t* b, 
                    const double* col_sc, int64_t col_items, int64_t col_n, int32_t* col_pos, void* ws,
                    int64_t ws_bytes, int64_t* stats);
 
+/* K27: K26 for a gallery sharded by rows (csrc/cos_filter.hip): each call sees one shard's pairs, the shards' words
+ * are summed.  The same reference lines as K26.  Additive entries: the ABI version does not change.
+ *   cmve_cos_item_scores_sharded  (evaluation.py:17-21 + metrics.py:61-102,124-157 = validate.py:15-54)
+ *                      cmve_cos_item_scores with shard ownership, on cmve_pairwise_item_scores' contract: idx holds
+ *                      GLOBAL rows of the other side, of which this call's operand is [idx_base, idx_base + n_other).
+ *                      Item p is scored (cos64) iff 0 <= idx[p] - idx_base < n_other; every other item gets the
+ *                      all-zero 8-byte word, not NaN, so that the int64 SUM over the shards is the owner's word (NaN
+ *                      and -0.0 as they are).  idx_base < 0 is refused before any launch.
+ *   cmve_cos_count_resolved  (evaluation.py:17-21 + metrics.py:61-102,124-157 = validate.py:15-54)
+ *                      cmve_cos_count's arguments and launches, then a band-list overflow resolved ON THE DEVICE:
+ *                      two more launches that read stats[3] and return at once when it is 0; otherwise the partial
+ *                      counts are zeroed (the NaN items' words are kept) and EVERY pair is re-scored with cos64 by
+ *                      the band re-score's own body.  On return row_pos / col_pos hold, word for word, what
+ *                      cmve_cos_count writes with a band list large enough, whether or not the list overflowed.
+ *                      After an overflow stats[3] is still 1, stats[1] the whole need (grow the list for later
+ *                      calls) and stats[2] 0.  Never synchronises, allocates nothing, integer atomics only. */
+int cmve_cos_item_scores_sharded(cmve_handle_t h, const cmve_rows_t* a, const cmve_rows_t* b, const int64_t* off,
+                                 const int32_t* idx, int64_t n_lists, int64_t n_items, int32_t col_dir,
+                                 int64_t idx_base, double* out);
+int cmve_cos_count_resolved(cmve_handle_t h, const cmve_rows_t* a, const cmve_rows_t* b, const int64_t* row_off,
+                            const double* row_sc, int64_t row_items, int64_t row_n, int32_t* row_pos,
+                            const int64_t* col_off, const double* col_sc, int64_t col_items, int64_t col_n,
+                            int32_t* col_pos, void* ws, int64_t ws_bytes, int64_t* stats);
+
 /* K20: cmve_pairwise_topk for CMVE_PW_L2 with fp64 score words at the MFMA rate (csrc/l2_topk.hip).
  * Replaces, as its K18 twin does: LINAS-engine/inference.py:78-80 (cal_error(video_embs, cap_emb, measure) then
  * np.argsort(errors[0])[:topK]) under euclidean / l2 / l2_norm (LINAS-engine/evaluation.py:22-35).
