@@ -461,7 +461,7 @@ inline CandLayout cand_layout(int64_t g_n_pad, int64_t cap) {
   return l;
 }
 constexpr int64_t FIXUP_MAX_BUCKETS_PER_XCD = 4096;  // LDS prefix of the XCD-ordered fix-up
-constexpr int EVAL_EMAX_SHARDS = 64;  // K14: err_max shards per side and plane (eval.hip, sim.hip)
+constexpr int EVAL_EMAX_SHARDS = 64;  // K14: err_max shards per side and plane (eval.hip, sim.hip, api_eval.hip)
 
 // canonical exact score: cos64(x, y) = dot64(raw_x, raw_y) * (inv_x * inv_y), symmetric in (x, y), so
 // the GT-score, fix-up and top-k re-score kernels score a pair bit-identically

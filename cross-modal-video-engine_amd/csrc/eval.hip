@@ -1,5 +1,5 @@
 // K14: one exact two-direction GT-rank evaluation of a resident problem in four launches
-// (cmve_eval_ranks, host side in sim.hip):
+// (cmve_eval_ranks, host side in api_eval.hip):
 //   1. eval_prep_kernel    K1 pack of BOTH sets, the exact fp64 GT score of every row of both
 //                          directions (K5a) and zeroed counters: one wave per row, 4 rows per block
 //                          (every CU busy), no tail; per-block err maxima into 16 atomic-max shards

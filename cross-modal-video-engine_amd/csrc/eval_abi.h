@@ -1,4 +1,4 @@
-// K14 evaluation (eval.hip): the argument blocks shared by its kernels and the host entry (sim.hip).
+// K14 evaluation (eval.hip): the argument blocks shared by its kernels and the host entries (api_eval.hip).
 #pragma once
 #include "cmve_internal.h"
 

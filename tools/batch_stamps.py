@@ -1,5 +1,5 @@
 """Kernel study of a K14 batch (cmve_eval_batch_*): s_memrealtime stamps (100 MHz) of every rank tile of the
-batch's evaluations (a diagnostic build: make study NAME=stamps DEFS=-DCMVE_EVAL_DBG=128, loaded with CMVE_LIB=.../libcmve_stamps.so; timings only) plus the first evaluation's prep and
+batch's evaluations (a diagnostic build: make study NAME=stamps DEFS=-DCMVE_EVAL_DBG=128 -- csrc/api_eval.hip reads it --, loaded with CMVE_LIB=.../libcmve_stamps.so; timings only) plus the first evaluation's prep and
 finish blocks.  Prints medians over 20 batch runs: the launch spans, the per-tile phase durations and the
 tile duration percentiles, in microseconds from the first prep block's start."""
 import ctypes

@@ -1,5 +1,5 @@
 """Kernel study of the K14 evaluation: s_memrealtime stamps (100 MHz) per block of the prep, fix-up and
-finish launches (a diagnostic build: make study NAME=stamps DEFS=-DCMVE_EVAL_DBG=128, loaded with CMVE_LIB; timings only; the rank GEMM carries none).
+finish launches (a diagnostic build: make study NAME=stamps DEFS=-DCMVE_EVAL_DBG=128 -- csrc/api_eval.hip reads it --, loaded with CMVE_LIB; timings only; the rank GEMM carries none).
 Prints, per launch, the first / last block start and the first / last block end, in microseconds from
 the first prep block's start, median over 30 evaluations."""
 import ctypes
