@@ -530,7 +530,8 @@ void sim_kernel(
           for (int j = 0; j < TN; ++j) {
             const int col = cbase + j * 16;
             const float v = acc[i][j][r] + colv[0][j];
-            if (col < a.ng) outp[(int64_t)row * a.ldo + col] = relu ? fmaxf(v, 0.f) : v;
+            // torch.relu: a NaN passes (NaN <= 0 is false; fmaxf would give 0), as in ctrain.hip's act kernels
+            if (col < a.ng) outp[(int64_t)row * a.ldo + col] = (relu && v <= 0.f) ? 0.f : v;
           }
         }
     } else if constexpr (EPI == EPI_LINEAR) {
@@ -548,7 +549,7 @@ void sim_kernel(
             const int col = cbase + j * 16;
             if (col >= a.ng) continue;
             float v = acc[i][j][r] + bj[j];
-            if (a.relu == 1) v = fmaxf(v, 0.f);                         // ReLU
+            if (a.relu == 1) v = v <= 0.f ? 0.f : v;                    // ReLU (a NaN passes, as in torch.relu)
             else if (a.relu == 2) v = v / (1.f + expf(-1.702f * v));  // QuickGELU x*sigmoid(1.702x)
             else if (a.relu == 3) v = 1.f / (1.f + expf(-v));         // Sigmoid
             if (a.resid) v = a.resid[(int64_t)row * a.ldr + col] + v;

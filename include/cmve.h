@@ -140,6 +140,8 @@ int cmve_sim_store(cmve_handle_t h, const cmve_rows_t* q, const cmve_rows_t* g, 
  * BN eval as a per-column affine v * bn_scale + bn_shift (both NULL = no BN).  x [N, K] and
  * w [F_out, K] (torch nn.Linear layout) are packed with CMVE_PACK_RAW; mode CMVE_SIM_BF16X3
  * gives ~1e-6 relative error (the fp32 reference's own rounding is ~1e-7).  out fp32 [N, F_out].
+ * A NaN passes through every activation (ReLU included, as in torch.relu): a NaN row of x gives
+ * a NaN output row, a NaN row of w a NaN output column.
  */
 int cmve_linear(cmve_handle_t h, const cmve_rows_t* x, const cmve_rows_t* w, int32_t mode,
                 const float* bias, const float* bn_scale, const float* bn_shift,

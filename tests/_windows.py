@@ -1,6 +1,7 @@
-"""Canary-buffer windows, the bound check and the restatements of score_error_bound and the directed fp32
-roundings shared by the C-ABI edge tests (test_gpu_head_edges.py, test_gpu_fusion_edges.py,
-test_gpu_pack_edges.py, test_gpu_topk_edges.py).  A plain module, not a test file."""
+"""Canary-buffer windows, the bound check and the restatements of score_error_bound, the directed fp32
+roundings and the GEMM's geometry rule shared by the C-ABI edge tests (test_gpu_head_edges.py,
+test_gpu_fusion_edges.py, test_gpu_pack_edges.py, test_gpu_topk_edges.py, test_gpu_gemm_edges.py).  A plain
+module, not a test file."""
 import numpy as np
 import torch
 
@@ -73,3 +74,14 @@ def _E(ea, eb, d_pad, mode):
     u = 1.0 / 8388608.0
     gamma = n * u / (1.0 - n * u)
     return ea + (1.0 + ea) * eb + gamma * (1.0 + ea) * (1.0 + eb) + 1e-12
+
+
+def _phased(nq_pad, ng_pad):
+    """sim_uses_phased (sim.hip): the persistent G256 kernel."""
+    return nq_pad % 256 == 0 and ng_pad % 256 == 0 and (nq_pad // 256) * (ng_pad // 256) >= 512
+
+
+def _g64(nq_pad, ng_pad):
+    """sim_uses_g64 (sim.hip): the G64 ring kernel; neither: G128."""
+    return not _phased(nq_pad, ng_pad) and (nq_pad // 128) * (ng_pad // 128) < 128 and nq_pad % 64 == 0 and \
+        ng_pad % 64 == 0

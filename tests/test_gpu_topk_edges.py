@@ -24,7 +24,7 @@ import numpy as np
 import pytest
 import torch
 
-from _windows import Pad, _E, _f32_down
+from _windows import Pad, _E, _f32_down, _phased, _g64
 
 pytestmark = pytest.mark.gpu
 
@@ -730,15 +730,6 @@ def _check_batch(q, g, mode, k, cos=None, what="", complete=True):
         _assert_rows(i2, s2, ridx[un], rsc[un], f"{what} (completed by cmve_topk)")
     st["idx"] = idx
     return un, st
-
-
-def _phased(nq_pad, ng_pad):
-    return nq_pad % 256 == 0 and ng_pad % 256 == 0 and (nq_pad // 256) * (ng_pad // 256) >= 512
-
-
-def _g64(nq_pad, ng_pad):
-    return not _phased(nq_pad, ng_pad) and (nq_pad // 128) * (ng_pad // 128) < 128 and nq_pad % 64 == 0 and \
-        ng_pad % 64 == 0
 
 
 @functools.lru_cache(maxsize=None)
